@@ -2,6 +2,13 @@
 """Benchmark of the Pi-block rollout hot path.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload gs2d_512|gs3d_128|lo2d_512] [--T T]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times exactly K steps and prints one JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...).  --full adds everything else the line used to carry: the per-kernel roofline (the sweep timed alone), the
+CPU baselines, the module-path / loss / physics add-ons, the 3D-GS 128^3 half of the metric and the slab-sharded series.
+--dump-outputs DIR writes what the timed path returned in its last step (the trajectory's final frame plus a fixed, seeded
+sample of the whole trajectory, dL/dh0, the parameter-block gradient) as DIR/<name>.npy; the inputs are the same in every run.
 
 One "step" (the unit of --steps) is ONE full rollout pass of the hot path over one synthetic
 problem: T Pi-block time steps forward + the T-step reverse sweep with a dense dL/dtraj already
@@ -179,9 +186,10 @@ def ensure_library(local_rank):
         time.sleep(1.0)
 
 
-def measure_workload(pa, dev, dist, rank, world, name, steps, warmup, reaction, opts, T=0):
+def measure_workload(pa, dev, dist, rank, world, name, steps, warmup, reaction, opts, T=0, full=True):
     """Time `steps` rollout passes (T Pi-block time steps forward + the full backward each) of workload `name`.
-    Returns the measurement as a dict (value, ms_per_step, per-kernel roofline, ...) and the live tensors for add-ons."""
+    Returns the measurement as a dict (value, ms_per_step, with `full` the per-kernel roofline, ...) and the live tensors
+    for add-ons and --dump-outputs."""
     family, shape, hc, dtype, T_def, golden = WORKLOADS[name]
     T = T or T_def
     sd = load_params(golden)
@@ -232,6 +240,28 @@ def measure_workload(pa, dev, dist, rank, world, name, steps, warmup, reaction, 
     bwd_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))
     value = world * steps * T / elapsed
 
+    # which kernel families ran, asked from the library itself (percnn_pi_debug_plan: its own dispatch rules)
+    from percnn_amd import _lib as _pl
+    plan = _pl.rollout_plan(0 if reaction == "poly" else hc, shape, esz, ",".join(f"{k}={v}" for k, v in opts.items()) or None)
+    K, Kf = plan["bwd_steps_per_launch"], plan["fwd_steps_per_launch"]
+    res = {
+        "value": value, "unit": "steps/s", "steps": steps, "warmup": warmup, "ms_per_step": elapsed / steps * 1e3,
+        "timed_region_s": elapsed,
+        "dtype": "f32" if dtype == torch.float32 else "f64",
+        "config": {"workload": f"{name}: {family} {'x'.join(map(str, shape))}, 2 species, Hc={hc}, "
+                               f"T={T} forward+backward rollout per step, dense dL/dtraj",
+                   "reaction": reaction,
+                   "parallelism": "single GPU" if world == 1 else f"{world} independent replicas (no collective)",
+                   "points": npts, "T": T, "time_steps_per_launch": K, "kernel_plan": plan},
+        "fwd_us_per_time_step": fwd_ms * 1e3 / T, "bwd_us_per_time_step": bwd_ms * 1e3 / T,
+        "fwd_only_steps_per_sec": T / (fwd_ms * 1e-3),
+    }
+    # what the last timed pass handed its caller (the trajectory is filled in place), for --dump-outputs
+    live = {"cell": cell, "family": family, "traj": traj, "gtraj": gtraj, "P": P, "T": T, "fwd_ms": fwd_ms, "sd": sd,
+            "shape": shape, "esz": esz, "npts": npts, "g0": g0, "pg": pg}
+    if not full:
+        return res, live
+
     # ---- per-kernel roofline, measured live with HIP events on the launch stream ------------------
     # The backward is two kernels where the schedule is split: the sequential adjoint sweep and ONE time-parallel
     # gradient reduction.  The sweep is timed alone through a PER-CALL option (no process-wide state is touched).
@@ -245,11 +275,6 @@ def measure_workload(pa, dev, dist, rank, world, name, steps, warmup, reaction, 
     torch.cuda.synchronize()
     sweep_ms = e0.elapsed_time(e1) / reps
     red_ms = max(bwd_ms - sweep_ms, 1e-6)
-
-    # which kernel families ran, asked from the library itself (percnn_pi_debug_plan: its own dispatch rules)
-    from percnn_amd import _lib as _pl
-    plan = _pl.rollout_plan(0 if reaction == "poly" else hc, shape, esz, ",".join(f"{k}={v}" for k, v in opts.items()) or None)
-    K, Kf = plan["bwd_steps_per_launch"], plan["fwd_steps_per_launch"]
     tiled = plan["bwd"] == "tile2d"
     poly = reaction == "poly"
     # algorithmic bytes per point and time step: fwd read+write state = 2*C*s;
@@ -344,31 +369,40 @@ def measure_workload(pa, dev, dist, rank, world, name, steps, warmup, reaction, 
         traffic_source = (f"profiles/traffic_{name}.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of this command at T = "
                           f"{tj.get('_T', 100)}, collected {tj.get('_date', 'in round 5')} in separate passes on MI355X and committed "
                           "(not re-measured in this run; per-group / per-step figures are scaled to this run's T)")
-    res = {
-        "value": value, "unit": "steps/s", "steps": steps, "warmup": warmup, "ms_per_step": elapsed / steps * 1e3,
-        "timed_region_s": elapsed,
-        "dtype": "f32" if dtype == torch.float32 else "f64",
-        "config": {"workload": f"{name}: {family} {'x'.join(map(str, shape))}, 2 species, Hc={hc}, "
-                               f"T={T} forward+backward rollout per step, dense dL/dtraj",
-                   "reaction": reaction,
-                   "parallelism": "single GPU" if world == 1 else f"{world} independent replicas (no collective)",
-                   "points": npts, "T": T, "time_steps_per_launch": K, "kernel_plan": plan},
-        "roofline": {"bound": "hbm", "kernel": dom["kernel"], "achieved": dom["achieved"], "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": dom["frac"], "traffic": traffic, "traffic_source": traffic_source,
-                     "algorithmic_bytes_per_launch": dom["algorithmic_bytes_per_launch"],
-                     "avg_launch_us": dom["avg_launch_us"], "clock": clock,
-                     # the roofline SURVEY 8(d) prices the path against is HBM; what the counters say actually limits the kernel:
-                     "limiter": dom.get("limiter"),
-                     "frac_of_copy_ceiling": dom["frac_of_copy_ceiling"], "copy_ceiling": HBM_COPY_CEILING_GBS,
-                     "rocprofv3_avg_launch_us": dom.get("rocprofv3_avg_launch_us"), "frac_by_rocprofv3": dom.get("frac_by_rocprofv3"),
-                     "rocprofv3_source": (rp.get("source") if dom.get("rocprofv3_avg_launch_us") else None),
-                     "all_kernels": kernels},
-        "fwd_us_per_time_step": fwd_ms * 1e3 / T, "bwd_us_per_time_step": bwd_ms * 1e3 / T,
-        "fwd_only_steps_per_sec": T / (fwd_ms * 1e-3),
-    }
-    live = {"cell": cell, "family": family, "traj": traj, "gtraj": gtraj, "P": P, "T": T, "fwd_ms": fwd_ms, "sd": sd,
-            "shape": shape, "esz": esz, "npts": npts}
+    res["roofline"] = {"bound": "hbm", "kernel": dom["kernel"], "achieved": dom["achieved"], "peak": HBM_PEAK_GBS,
+                       "unit": "GB/s", "frac": dom["frac"], "traffic": traffic, "traffic_source": traffic_source,
+                       "algorithmic_bytes_per_launch": dom["algorithmic_bytes_per_launch"],
+                       "avg_launch_us": dom["avg_launch_us"], "clock": clock,
+                       # the roofline SURVEY 8(d) prices the path against is HBM; what the counters say actually limits the kernel:
+                       "limiter": dom.get("limiter"),
+                       "frac_of_copy_ceiling": dom["frac_of_copy_ceiling"], "copy_ceiling": HBM_COPY_CEILING_GBS,
+                       "rocprofv3_avg_launch_us": dom.get("rocprofv3_avg_launch_us"), "frac_by_rocprofv3": dom.get("frac_by_rocprofv3"),
+                       "rocprofv3_source": (rp.get("source") if dom.get("rocprofv3_avg_launch_us") else None),
+                       "all_kernels": kernels}
     return res, live
+
+
+def dump_outputs(path, arrays, budget_bytes=64 << 20):
+    """--dump-outputs: each array as path/<name>.npy, float32 or float64 as computed, at most `budget_bytes` in all."""
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    total = sum(a.nbytes for a in host.values())
+    if total > budget_bytes:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {budget_bytes})")
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def trajectory_outputs(traj, g0, pg, sample=1 << 20):
+    """What a caller of the timed path receives: the trajectory (filled in place; its final frame whole, plus a fixed, seeded
+    sample of `sample` points of the whole buffer), dL/dh0 and the parameter-block gradient."""
+    n = traj.numel()
+    idx = np.unique(np.random.default_rng(0).integers(0, n, size=min(n, sample)))
+    return {"traj_final": traj[-1], "traj_sample": traj.reshape(-1)[torch.from_numpy(idx).to(traj.device)],
+            "grad_h0": g0, "grad_param_block": pg}
 
 
 
@@ -543,14 +577,26 @@ def main():
                     help="headline measurement only (profiling runs: keeps per-kernel averages free of the add-on passes)")
     ap.add_argument("--no-also", action="store_true", help="skip the second half of the BASELINE metric (3D-GS 128^3)")
     ap.add_argument("--slab-timeout", type=float, default=420.0)
+    ap.add_argument("--slab-in-process", action="store_true",
+                    help="run the slab series inside each rank instead of an isolated child process per rank (one-GPU test "
+                         "runs of many ranks: half the processes holding the device)")
     ap.add_argument("--slab-child", action="store_true", help=argparse.SUPPRESS)   # see slab_extra_isolated
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline (sweep timed alone), CPU baselines, add-ons, the 3D-GS "
+                         "128^3 half of the metric, the slab series at N = 1 (--no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if a.gpus > 1 and world != a.gpus:
         raise SystemExit(f"--gpus {a.gpus} needs torch.distributed.run with {a.gpus} ranks (WORLD_SIZE={world})")
+    if a.dump_outputs and world > 1:
+        raise SystemExit("bench.py: --dump-outputs needs a single-process run (--gpus 1)")
     # PERCNN_BENCH_ONE_GPU=1: every rank on cuda:0, gloo as the control plane (RCCL refuses two ranks on one device) -- how
     # tests/test_slab_dist_gpu.py::test_bench_two_ranks_on_one_gpu proves the N > 1 control flow of this file on a 1-GPU box
     one_gpu = bool(int(os.environ.get("PERCNN_BENCH_ONE_GPU", "0")))
@@ -590,19 +636,21 @@ def main():
         pa.set_option(k, int(v))                      # the CLI's explicit process-wide defaults for this run
     opts = dict(kv.split("=") for kv in a.opt)
 
-    res, live = measure_workload(pa, dev, dist, rank, world, a.workload, a.steps, a.warmup, a.reaction, opts, a.T)
+    res, live = measure_workload(pa, dev, dist, rank, world, a.workload, a.steps, a.warmup, a.reaction, opts, a.T, full=a.full)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, trajectory_outputs(live["traj"], live["g0"], live["pg"]))
     out = {"metric": "pi_block_rollout_fwd_bwd_steps_per_sec", "value": res["value"], "unit": "steps/s",
            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": res["ms_per_step"],
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": res["dtype"], "data": "synthetic",
-           "config": res["config"], "roofline": res["roofline"], "timed_region_s": res["timed_region_s"],
+           "config": res["config"], **({"roofline": res["roofline"]} if a.full else {}), "timed_region_s": res["timed_region_s"],
            "fwd_us_per_time_step": res["fwd_us_per_time_step"], "bwd_us_per_time_step": res["bwd_us_per_time_step"],
            "fwd_only_steps_per_sec": res["fwd_only_steps_per_sec"]}
     family, sd, shape, T = live["family"], live["sd"], live["shape"], live["T"]
     cpu_threads = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(family, sd, shape)
         cpu_threads = out["cpu_baseline"]["cores"]
-    if world == 1 and not a.no_extras:
+    if world == 1 and a.full and not a.no_extras:
         try:
             out["physics_residual"] = physics_extra(pa, live["cell"], family, live["traj"], live["esz"], live["npts"])
         except Exception as e:                       # an add-on measurement must never cost the headline line
@@ -618,7 +666,7 @@ def main():
             out["sqerr_loss_in_sweep"] = {"error": repr(e)[:200]}
     del live, res
     torch.cuda.empty_cache()
-    if world == 1 and not a.no_extras:
+    if world == 1 and a.full and not a.no_extras:
         try:
             out["module_path"] = module_path_extra(pa, family, sd, shape, T, dev, a.reaction)
         except Exception as e:
@@ -636,7 +684,7 @@ def main():
             torch.cuda.empty_cache()
 
     # ---- the other half of BASELINE.json's metric ("2D-GS 512^2 & 3D-GS 128^3") in the same line --------------------
-    if a.workload == "gs2d_512" and not a.no_also and not a.T:
+    if a.full and a.workload == "gs2d_512" and not a.no_also and not a.T:
         try:
             n3 = max(3, a.steps // 4)
             r3, l3 = measure_workload(pa, dev, dist, rank, world, "gs3d_128", n3, max(1, a.warmup // 2), a.reaction, opts)
@@ -668,7 +716,7 @@ def main():
                 flush_c_stdio()                              # RCCL's version banner sits in the C stdio buffer
                 print(json.dumps(out), flush=True)           # -> the JSON line is the last line on stdout
 
-    if world > 1 or a.slab_extra or not a.no_extras:
+    if world > 1 or a.slab_extra or (a.full and not a.no_extras):
         def watchdog():
             if not printed.wait(a.slab_timeout + 60.0):
                 out["slab_3d"] = {"error": f"timed out after {a.slab_timeout + 60.0}s"}
@@ -795,7 +843,32 @@ def stage1_main(a, pa, dev, dist, rank, world):
     fwd_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
     bwd_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))
     value = world * a.steps * T / elapsed
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, trajectory_outputs(traj, g0, pg))
+    out = {
+        "metric": "pi_block_rollout_fwd_bwd_steps_per_sec", "value": value, "unit": "steps/s",
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{a.workload}: Stage-1 Pi-block ({family}; three 5x5 conv branches 2->16 per species) "
+                               f"{shape[0]}x{shape[1]}, T={T} forward+backward rollout per step, dense dL/dtraj",
+                   "parallelism": "single GPU" if world == 1 else f"{world} independent replicas (no collective)",
+                   "points": n, "T": T},
+        "fwd_us_per_time_step": fwd_ms * 1e3 / T, "bwd_us_per_time_step": bwd_ms * 1e3 / T,
+        "fwd_only_steps_per_sec": T / (fwd_ms * 1e-3),
+    }
+    if a.full:
+        stage1_roofline(a, pa, out, traj, gtraj, P, n, T, fwd_ms, bwd_ms)
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
+        out["cpu_baseline"] = stage1_cpu_baseline(family, sd, h0, shape)
+    if dist is not None:
+        dist.destroy_process_group()
+    if rank == 0:
+        flush_c_stdio()
+        print(json.dumps(out), flush=True)
 
+
+def stage1_roofline(a, pa, out, traj, gtraj, P, n, T, fwd_ms, bwd_ms):
+    """--full: the sweep timed alone, which launches were resident, per-kernel MFMA fractions -> out["roofline"]"""
     pa.stage1.set_option("skip_wgrad", 1)            # time the sweep kernel alone
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     pa.stage1.rollout_bwd(traj, gtraj, P)
@@ -840,28 +913,11 @@ def stage1_main(a, pa, dev, dist, rank, world):
         k["frac"] = k["achieved"] / MFMA_F32_PEAK_TFS
         k["share_of_pass"] = k["avg_launch_us"] * k["launches_per_pass"] / ((fwd_ms + bwd_ms) * 1e3)
     dom = max(kernels, key=lambda k: k["share_of_pass"])
-    out = {
-        "metric": "pi_block_rollout_fwd_bwd_steps_per_sec", "value": value, "unit": "steps/s",
-        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{a.workload}: Stage-1 Pi-block ({family}; three 5x5 conv branches 2->16 per species) "
-                               f"{shape[0]}x{shape[1]}, T={T} forward+backward rollout per step, dense dL/dtraj",
-                   "parallelism": "single GPU" if world == 1 else f"{world} independent replicas (no collective)",
-                   "points": n, "T": T, "time_steps_per_launch": T if (fwd_res and adj_res) else 1},
-        "roofline": {"bound": "mfma", "kernel": dom["kernel"], "achieved": dom["achieved"], "peak": MFMA_F32_PEAK_TFS,
-                     "unit": "TFLOP/s", "frac": dom["frac"], "traffic": None,
-                     "algorithmic_flops_per_launch": dom["algorithmic_flops_per_launch"],
-                     "avg_launch_us": dom["avg_launch_us"], "all_kernels": kernels},
-        "fwd_us_per_time_step": fwd_ms * 1e3 / T, "bwd_us_per_time_step": bwd_ms * 1e3 / T,
-        "fwd_only_steps_per_sec": T / (fwd_ms * 1e-3),
-    }
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
-        out["cpu_baseline"] = stage1_cpu_baseline(family, sd, h0, shape)
-    if dist is not None:
-        dist.destroy_process_group()
-    if rank == 0:
-        flush_c_stdio()
-        print(json.dumps(out), flush=True)
+    out["config"]["time_steps_per_launch"] = T if (fwd_res and adj_res) else 1
+    out["roofline"] = {"bound": "mfma", "kernel": dom["kernel"], "achieved": dom["achieved"], "peak": MFMA_F32_PEAK_TFS,
+                       "unit": "TFLOP/s", "frac": dom["frac"], "traffic": None,
+                       "algorithmic_flops_per_launch": dom["algorithmic_flops_per_launch"],
+                       "avg_launch_us": dom["avg_launch_us"], "all_kernels": kernels}
 
 
 def stage1_cpu_baseline(family, sd, h0, shape, budget_s=15.0):
@@ -1008,9 +1064,19 @@ def strided_loss_extra(pa, traj, gtraj, P, T, fwd_ms, reps):
 
 def slab_extra_isolated(a, dev, dist, rank, world, local_rank):
     """Run slab_extra in a child process per rank (its own process group on a fresh port): the halo ring hands RCCL
-    function addresses to the native loop, and a crash or stall in there must not take the headline line with it."""
+    function addresses to the native loop, and a crash or stall in there must not take the headline line with it.
+    --slab-in-process: the same series inside this rank, on the rank's process group (one process per rank instead of two)."""
     import socket
     import subprocess
+    if a.slab_in_process:
+        import percnn_amd as pa
+        os.environ.setdefault("PERCNN_PEER_TIMEOUT_S", "15")      # (the child's bound, see below)
+        one_gpu = bool(int(os.environ.get("PERCNN_BENCH_ONE_GPU", "0")))
+        try:
+            res = sharded_series(dev, dist, rank, world, one_gpu, steps=a.steps, warmup=a.warmup)
+        finally:
+            pa.slab.close_exchangers()
+        return json.loads(json.dumps(res))                       # what the child's line would carry
     if dist is None:                                 # plain `python bench.py`: one rank, no process group in the child either
         env = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK=str(local_rank))
         for k in ("MASTER_ADDR", "MASTER_PORT"):

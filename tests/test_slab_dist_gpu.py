@@ -160,7 +160,8 @@ def test_bench_two_ranks_on_one_gpu(hip_device):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"]
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -204,7 +205,8 @@ def test_bench_eight_ranks_on_one_gpu_at_256cubed(hip_device):
     bench.py --gpus 8`` -- with all eight ranks on cuda:0 (no 8-GPU node exists for the builder): 256^3 cut into
     8 slabs of 32 planes, previous != next neighbour on every rank, the transport probe, both transports, the strong-scaling
     series at the REAL grid sizes with its bit-identity check against the single-domain rollout.  What it cannot show is the
-    wire: eight processes share one device's memory here."""
+    wire: eight processes share one device's memory here.  Each rank runs its slab series itself rather than in a
+    child process (--slab-in-process): eight processes hold the device, not sixteen; the two-rank test covers the children."""
     import json
     import subprocess
     env = dict(os.environ, PERCNN_BENCH_ONE_GPU="1", PERCNN_BENCH_HEADLINE_T="12")     # (T = 100 on the driver's node)
@@ -212,7 +214,7 @@ def test_bench_eight_ranks_on_one_gpu_at_256cubed(hip_device):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1",
-           "--no-cpu-baseline", "--no-also", "--slab-timeout", "900"]
+           "--full", "--no-cpu-baseline", "--no-also", "--slab-timeout", "900", "--slab-in-process"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
