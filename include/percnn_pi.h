@@ -13,6 +13,7 @@
  *   - Plain pointers and sizes only; every data pointer is DEVICE memory owned by the caller.
  *   - State layout: PyTorch-contiguous NCHW / NCDHW with N = 1, i.e. species-major planar
  *     [2][*S]; `shape` lists the spatial extents slowest-first (2D: {H, W}; 3D: {D, H, W}).
+ *     The percnn_pi_batch_* entry points take N = `batch` independent samples, [B][2][*S] (see "Batched rollouts").
  *   - Periodic boundaries on every axis (2dgs:108-109, 3dgs:125-127); every extent >= 2.
  *   - Asynchronous on `stream` (a hipStream_t passed as void*; NULL = default stream); no host
  *     synchronisation and no allocation inside, hence hipGraph-capturable.  Re-entrant: the only
@@ -598,6 +599,44 @@ int percnn_pi_traj_sqerr_f32(const float *traj, const float *target, const unsig
 int percnn_pi_traj_sqerr_f64(const double *traj, const double *target, const unsigned char *frame_mask, int nframes, int ndim,
                              const int64_t *shape, double scale, double *out, void *workspace, size_t workspace_bytes,
                              void *stream);
+
+/* ---- Batched rollouts: B independent trajectories, ONE parameter block ------------------------------------------------------
+ * The reference's RCNNCell / RCNN run unchanged on a batch of initial conditions [B,2,*S] (train_2drd.py:105-121 is padding,
+ * convolutions and elementwise ops); these entry points do the same in the launches of one sample: the batch is an extra grid
+ * dimension of the launch-per-group kernels (2D tile kernels, direct step kernels), not a loop of calls.
+ *   state        [B][2][*S]                     trajectory, g_traj, adjoint: [T+1][B][2][*S], frame-major -- reshaped to
+ *                                               [(T+1)*B, 2, *S] exactly torch.cat(tuple(outputs), dim=0) of batched frames
+ *   g_h0         [B][2][*S]                     param_grad: ONE block, ACCUMULATED (+=) sum over all samples
+ *   frame_mask   T+1 host bytes, applied to every sample
+ * Arguments otherwise as the unbatched namesakes, plus `batch` after `shape` and a nullable `options` string (grammar of the
+ * *_opt entry points).  Every state field of sample b is bit-identical to the unbatched entry point on that sample alone;
+ * param_grad equals the sum of the per-sample gradients to reduction round-off and is bit-identical from run to run.
+ * Validation before any launch: batch < 1 (or > 65535), the advective block (hc == -1) with batch > 1 or bad options ->
+ * PERCNN_PI_EINVAL; a workspace below *_workspace_bytes -> PERCNN_PI_EWORKSPACE; PERCNN_PI_ETOOLARGE is judged per sample.
+ * batch == 1 is the unbatched entry point (same kernels, same workspace size).  The resident ("tile_persist", "fwd_persist",
+ * "res3d"), 3D brick and plane-streaming kernels have no batched flavour and are not dispatched for batch > 1. */
+size_t percnn_pi_batch_bwd_workspace_bytes(int hc, int ndim, const int64_t *shape, int batch, int elem_size);
+size_t percnn_pi_batch_rollout_bwd_workspace_bytes(int hc, int ndim, const int64_t *shape, int batch, int T, int elem_size);
+int percnn_pi_batch_step_fwd_f32(const float *h, float *out, const float *params, int hc, int ndim, const int64_t *shape,
+                                 int batch, const char *options, void *stream);
+int percnn_pi_batch_step_fwd_f64(const double *h, double *out, const double *params, int hc, int ndim, const int64_t *shape,
+                                 int batch, const char *options, void *stream);
+int percnn_pi_batch_step_bwd_f32(const float *h, const float *g_out, const float *g_inject, float *g_in, double *param_grad,
+                                 void *workspace, size_t workspace_bytes, const float *params, int hc, int ndim,
+                                 const int64_t *shape, int batch, const char *options, void *stream);
+int percnn_pi_batch_step_bwd_f64(const double *h, const double *g_out, const double *g_inject, double *g_in, double *param_grad,
+                                 void *workspace, size_t workspace_bytes, const double *params, int hc, int ndim,
+                                 const int64_t *shape, int batch, const char *options, void *stream);
+int percnn_pi_batch_rollout_fwd_f32(float *traj, const float *params, int hc, int ndim, const int64_t *shape, int batch,
+                                    int T, const char *options, void *stream);
+int percnn_pi_batch_rollout_fwd_f64(double *traj, const double *params, int hc, int ndim, const int64_t *shape, int batch,
+                                    int T, const char *options, void *stream);
+int percnn_pi_batch_rollout_bwd_f32(const float *traj, const float *g_traj, const unsigned char *frame_mask, float *g_h0,
+                                    double *param_grad, void *workspace, size_t workspace_bytes, const float *params, int hc,
+                                    int ndim, const int64_t *shape, int batch, int T, const char *options, void *stream);
+int percnn_pi_batch_rollout_bwd_f64(const double *traj, const double *g_traj, const unsigned char *frame_mask, double *g_h0,
+                                    double *param_grad, void *workspace, size_t workspace_bytes, const double *params, int hc,
+                                    int ndim, const int64_t *shape, int batch, int T, const char *options, void *stream);
 
 #ifdef __cplusplus
 }

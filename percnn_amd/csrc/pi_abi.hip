@@ -2713,6 +2713,298 @@ int rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* mask, 
 }
 
 
+// ---- batched rollouts: B independent trajectories, one parameter block (include/percnn_pi.h "Batched") ------------------------
+// The batch is the y dimension of the launch-per-group kernels (pi_fwd2d_tile_batch_kernel, pi_adj2d_tile_batch_kernel,
+// pi_fwd_batch_kernel, pi_bwd_batch_kernel): every workgroup runs the unbatched kernel's body on one sample, so every state field
+// of sample b is the unbatched result of that sample alone, bit for bit.  Partial rows: one per (sample, workgroup), reduced in
+// one fixed order.  The resident, brick and plane-streaming kernels have no batched flavour and are never dispatched here.
+constexpr int MAX_BATCH = 65535;                            // grid y
+
+int batch_problem(int hc, int ndim, const int64_t* shape, int batch, Problem& p, const char* options, bool launches = true)
+{
+    if (batch < 1 || batch > MAX_BATCH || (batch > 1 && hc == -1)) return PERCNN_PI_EINVAL;   // no batched advective block
+    if (int rc = make_problem(hc, ndim, shape, false, p, options, launches)) return rc;
+    if ((int64_t)batch * p.n > (int64_t(1) << 40)) return PERCNN_PI_EINVAL;
+    return 0;
+}
+
+// tile vs direct: the per-sample rules of tile_eligible, with the size limits of the "tile = 1" rule applied to the points of
+// the whole batch (the tile kernels pay while the launches are latency-bound: 100^2 x 64 still is)
+template <typename T>
+bool batch_tile(const Problem& p, int batch, std::initializer_list<const void*> ptrs, bool adjoint)
+{
+    if (!tile_eligible<T>(p, ptrs, adjoint)) return false;
+    if (p.opt.tile == 1 && (int64_t)batch * p.n >= (adjoint ? (5 << 18) : (3 << 20))) return false;
+    return true;
+}
+
+template <typename T, int HC, int K, int NT, int BY = TILE_B, int BX = TILE_B>
+hipError_t launch_fwd_tile_b(T* frame_t, const T* P, const Problem& p, int batch, hipStream_t st)
+{
+    using TL = pi::Tile<K, BX, BY>;
+    const pi::TileGeom g = make_tile_geom(p, BY, BX);
+    const unsigned grid = (unsigned)(((p.n0 + BY - 1) / BY) * g.tiles_x);
+    const size_t lds = (size_t)4 * TL::PLANE * sizeof(T) + 32 /* lds_pad0/1 */ + (size_t)p.opt.lds_pad;
+    auto* k = pi::pi_fwd2d_tile_batch_kernel<T, HC, K, BX, BY, NT>;
+    if (hipError_t e = allow_lds(k, lds)) return e;
+    hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(NT), lds, st, frame_t, (long)batch * 2 * p.n, (long)(2 * p.n), P, g);
+    return hipGetLastError();
+}
+
+template <typename T, int HC, int K, int NT, int BY = TILE_B, bool MOM = false, int BX = TILE_B>
+hipError_t launch_adj_tile_b(const T* hframe_t, const T* gframe_t, T* aframe_t, unsigned inj_mask, T* g_h0, int steps_to_zero,
+                             double* partials, const T* P, const Problem& p, int batch, hipStream_t st)
+{
+    using TL = pi::Tile<K, BX, BY>;
+    const pi::TileGeom g = make_tile_geom(p, BY, BX);
+    const unsigned grid = (unsigned)(((p.n0 + BY - 1) / BY) * g.tiles_x);
+    size_t lds = (size_t)4 * TL::PLANE * sizeof(T) + 32 /* lds_pad0/1 */;
+    if (MOM && sizeof(T) == 4) {                // as launch_adj_tile
+        const size_t tail = (size_t)(2 * (NT / pi::WAVE) + 20 + 20 * (NT / pi::WAVE)) * sizeof(double) +
+                            (size_t)20 * (NT + 16) * sizeof(T);
+        if (tail > lds) lds = tail;
+    }
+    if (MOM && sizeof(T) == 8)
+        lds = pi::tile_state_bytes<T, K, BX, BY>() + (size_t)20 * NT * sizeof(double);
+    lds += (size_t)p.opt.lds_pad;
+    auto* k = pi::pi_adj2d_tile_batch_kernel<T, HC, K, BX, BY, NT, MOM>;
+    if (hipError_t e = allow_lds(k, lds)) return e;
+    hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(NT), lds, st, hframe_t, gframe_t, aframe_t, (long)batch * 2 * p.n,
+                       (long)(2 * p.n), inj_mask, g_h0, steps_to_zero, partials, pi::nparams(p.hc), P, g);
+    return hipGetLastError();
+}
+
+// the tile variant fwd_tile / adj_tile pick for one sample, on all samples
+template <typename T>
+hipError_t fwd_tile_b(T* frame_t, const T* P, const Problem& p, int batch, hipStream_t st)
+{
+    if constexpr (sizeof(T) == 4) {
+        switch (tile_wide_for<T>(p, false)) {
+            case 1: return launch_fwd_tile_b<T, pi::POLY, 4, 640, 40, 32>(frame_t, P, p, batch, st);
+            case 2: return launch_fwd_tile_b<T, pi::POLY, 4, 768, 40, 40>(frame_t, P, p, batch, st);
+            default: break;
+        }
+    }
+#define CALL_FTB(HC, K, NT, ...) launch_fwd_tile_b<T, HC, K, NT, ##__VA_ARGS__>(frame_t, P, p, batch, st)
+    PI_TILE_DISPATCH(CALL_FTB);
+#undef CALL_FTB
+}
+
+template <typename T>
+hipError_t adj_tile_b(const T* hframe_t, const T* gframe_t, T* aframe_t, unsigned inj_mask, T* g_h0, int steps_to_zero,
+                      double* partials, const T* P, const Problem& p, int batch, hipStream_t st)
+{
+    if constexpr (sizeof(T) == 4) {
+        const bool fused = tile_fuse_ok<T>(p);
+#define CALL_WIDE_B(NT, BY, BX, MOM) launch_adj_tile_b<T, pi::POLY, 4, NT, BY, MOM, BX>(hframe_t, gframe_t, aframe_t, inj_mask, \
+                                                                                      g_h0, steps_to_zero, partials, P, p, batch, st)
+        switch (tile_wide_for<T>(p, true)) {
+            case 1: return fused ? CALL_WIDE_B(640, 40, 32, true) : CALL_WIDE_B(640, 40, 32, false);
+            case 2: return fused ? CALL_WIDE_B(768, 40, 40, true) : CALL_WIDE_B(768, 40, 40, false);
+            default: break;
+        }
+#undef CALL_WIDE_B
+    }
+    if (tile_fuse_ok<T>(p))
+        return launch_adj_tile_b<T, pi::POLY, 4, 512, TILE_B, true>(hframe_t, gframe_t, aframe_t, inj_mask, g_h0, steps_to_zero,
+                                                                    partials, P, p, batch, st);
+#define CALL_ATB(HC, K, NT, ...) launch_adj_tile_b<T, HC, K, NT, ##__VA_ARGS__>(hframe_t, gframe_t, aframe_t, inj_mask, g_h0, \
+                                                                               steps_to_zero, partials, P, p, batch, st)
+    PI_TILE_DISPATCH(CALL_ATB);
+#undef CALL_ATB
+}
+
+template <typename T, int NDIM, int HC, int VEC>
+hipError_t launch_fwd_b(const T* h, T* out, const T* P, const Problem& p, int batch, hipStream_t st)
+{
+    Geom g = make_geom(p);
+    const int block = direct_block(p, g, VEC);
+    if (g.rows <= 0) return hipSuccess;
+    if (!set_blockmap(g, NDIM, VEC, block, sizeof(T), p.opt.l2_tile_kb * 1024, 1, (long)p.opt.l2_tile_min_kb * 1024, p.opt.lane_x))
+        return (hipError_t)PERCNN_PI_ETOOLARGE;
+    g.xwin = 0;
+    hipLaunchKernelGGL((pi::pi_fwd_batch_kernel<T, NDIM, HC, VEC>), dim3(g.nblk, (unsigned)batch), dim3(block), 0, st, h, out, P,
+                       g, p.hc, (long)(2 * p.n));
+    return hipGetLastError();
+}
+
+template <typename T, int NDIM, int HC, int VEC, bool WGRAD>
+hipError_t launch_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* partials, const T* P, const Problem& p, int batch,
+                        hipStream_t st, unsigned* rows_out)
+{
+    Geom g = make_geom(p);
+    const int block = direct_block(p, g, VEC);
+    const unsigned grid = bwd_grid(p, VEC, sizeof(T), 1);
+    if (g.rows <= 0) return hipSuccess;
+    if (!grid || !set_blockmap(g, NDIM, VEC, block, sizeof(T), p.opt.l2_tile_kb * 1024, 1, (long)p.opt.l2_tile_min_kb * 1024, p.opt.lane_x))
+        return (hipError_t)PERCNN_PI_ETOOLARGE;
+    const size_t lds = align_up((size_t)(block / pi::WAVE) * pi::nparams(p.hc) * sizeof(T), 16) +
+                       (size_t)(block / pi::WAVE) * 2 * sizeof(double) +
+                       ((WGRAD && HC == pi::POLY) ? (size_t)20 * (block + 8) * sizeof(T) : 0);
+    auto* k = pi::pi_bwd_batch_kernel<T, NDIM, HC, VEC, WGRAD>;
+    if (hipError_t e = allow_lds(k, lds)) return e;
+    hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(block), lds, st, h, G, inj, Gp, partials, P, g, p.hc, (long)(2 * p.n));
+    if (rows_out) *rows_out = grid * (unsigned)batch;
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t step_fwd_b(const T* h, T* out, const T* P, const Problem& p, int batch, hipStream_t st)
+{
+    const int vec = pick_vec<T>(p, {h, out});
+#define CALL_FWDB(NDIM, HC, VEC) launch_fwd_b<T, NDIM, HC, VEC>(h, out, P, p, batch, st)
+    PI_DISPATCH(CALL_FWDB);
+#undef CALL_FWDB
+}
+
+template <typename T, bool WGRAD>
+hipError_t step_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* partials, const T* P, const Problem& p, int batch,
+                      hipStream_t st, unsigned* rows_out)
+{
+    const int vec = pick_vec<T>(p, {h, G, inj, Gp});
+#define CALL_BWDB(NDIM, HC, VEC) launch_bwd_b<T, NDIM, HC, VEC, WGRAD>(h, G, inj, Gp, partials, P, p, batch, st, rows_out)
+    PI_DISPATCH(CALL_BWDB);
+#undef CALL_BWDB
+}
+
+size_t batch_partials_bytes(const Problem& p, int batch) { return (size_t)batch * partials_bytes_for(p.hc); }
+
+size_t batch_step_workspace_bytes(const Problem& p, int batch, int elem)
+{
+    return 2 * align_up((size_t)batch * 2 * p.n * elem, 256) + batch_partials_bytes(p, batch);
+}
+
+size_t batch_rollout_workspace_bytes(const Problem& p, int batch, int T_steps, int elem)
+{
+    return align_up((size_t)(T_steps + 1) * batch * 2 * p.n * elem, 256) + batch_partials_bytes(p, batch);
+}
+
+template <typename T>
+int batch_step_fwd_impl(const T* h, T* out, const T* P, int hc, int ndim, const int64_t* shape, int batch, const char* options,
+                        void* stream)
+{
+    if (batch == 1) return step_fwd_impl<T>(h, out, P, hc, ndim, shape, stream, false, 2, 0, options);
+    Problem p;
+    if (int rc = batch_problem(hc, ndim, shape, batch, p, options)) return rc;
+    if (!h || !out || !P || h == out) return PERCNN_PI_EINVAL;
+    return (int)step_fwd_b<T>(h, out, P, p, batch, static_cast<hipStream_t>(stream));
+}
+
+template <typename T>
+int batch_step_bwd_impl(const T* h, const T* g_out, const T* g_inj, T* g_in, double* param_grad, void* ws, size_t ws_bytes,
+                        const T* P, int hc, int ndim, const int64_t* shape, int batch, const char* options, void* stream)
+{
+    if (batch == 1)
+        return step_bwd_impl<T>(h, g_out, g_inj, g_in, param_grad, ws, ws_bytes, P, hc, ndim, shape, stream, false, 2, 0, -1, -1,
+                                options);
+    Problem p;
+    if (int rc = batch_problem(hc, ndim, shape, batch, p, options)) return rc;
+    if (!h || !g_out || !g_in || !param_grad || !P || g_in == g_out) return PERCNN_PI_EINVAL;
+    if (!ws || ws_bytes < batch_step_workspace_bytes(p, batch, sizeof(T)) || (reinterpret_cast<uintptr_t>(ws) % 16))
+        return PERCNN_PI_EWORKSPACE;
+    auto st = static_cast<hipStream_t>(stream);
+    Workspace w;
+    w.partials = reinterpret_cast<double*>(static_cast<unsigned char*>(ws) + 2 * align_up((size_t)batch * 2 * p.n * sizeof(T), 256));
+    w.partials_bytes = batch_partials_bytes(p, batch);
+    if (hipError_t e = hipMemsetAsync(w.partials, 0, w.partials_bytes, st)) return (int)e;
+    unsigned rows = 0;
+    if (hipError_t e = step_bwd_b<T, true>(h, g_out, g_inj, g_in, w.partials, P, p, batch, st, &rows)) return (int)e;
+    return (int)finish_grads(w, rows, hc, param_grad, st);
+}
+
+template <typename T>
+int batch_rollout_fwd_impl(T* traj, const T* P, int hc, int ndim, const int64_t* shape, int batch, int T_steps,
+                           const char* options, void* stream)
+{
+    if (batch == 1) return rollout_fwd_impl<T>(traj, P, hc, ndim, shape, T_steps, stream, options);
+    Problem p;
+    if (int rc = batch_problem(hc, ndim, shape, batch, p, options)) return rc;
+    if (!traj || !P || T_steps < 0) return PERCNN_PI_EINVAL;
+    auto st = static_cast<hipStream_t>(stream);
+    const size_t frame = (size_t)batch * 2 * p.n;          // frame t of all samples: [B][2][*S]
+    int t = 0;
+    if (batch_tile<T>(p, batch, {traj}, false)) {
+        const int K = (p.opt.tile_k == 8 && p.hc != 0) ? 4 : p.opt.tile_k;
+        for (; t + K <= T_steps; t += K)
+            if (hipError_t e = fwd_tile_b<T>(traj + (size_t)t * frame, P, p, batch, st)) return (int)e;
+    }
+    for (; t < T_steps; ++t)
+        if (hipError_t e = step_fwd_b<T>(traj + (size_t)t * frame, traj + (size_t)(t + 1) * frame, P, p, batch, st)) return (int)e;
+    return 0;
+}
+
+template <typename T>
+int batch_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* mask, T* g_h0, double* param_grad, void* ws,
+                           size_t ws_bytes, const T* P, int hc, int ndim, const int64_t* shape, int batch, int T_steps,
+                           const char* options, void* stream)
+{
+    if (batch == 1)
+        return rollout_bwd_impl<T>(traj, g_traj, mask, g_h0, param_grad, ws, ws_bytes, P, hc, ndim, shape, T_steps, stream, options);
+    Problem p;
+    if (int rc = batch_problem(hc, ndim, shape, batch, p, options)) return rc;
+    if (!traj || !g_traj || !g_h0 || !param_grad || !P || T_steps < 0) return PERCNN_PI_EINVAL;
+    if (!ws || ws_bytes < batch_rollout_workspace_bytes(p, batch, T_steps, sizeof(T)) || (reinterpret_cast<uintptr_t>(ws) % 16))
+        return PERCNN_PI_EWORKSPACE;
+    auto st = static_cast<hipStream_t>(stream);
+    const size_t sample = (size_t)2 * p.n;
+    const size_t frame = (size_t)batch * sample;
+    const size_t frame_bytes = frame * sizeof(T);
+    T* adj = static_cast<T*>(ws);                          // adjoint trajectory [T+1][B][2][*S]
+    Workspace w;
+    w.partials = reinterpret_cast<double*>(static_cast<unsigned char*>(ws) + align_up((size_t)(T_steps + 1) * frame_bytes, 256));
+    w.partials_bytes = batch_partials_bytes(p, batch);
+    auto has = [&](int t) { return !mask || mask[t]; };
+    int t_top = T_steps;
+    while (t_top > 0 && !has(t_top)) --t_top;
+    if (t_top == 0) {
+        if (has(0)) return (int)hipMemcpyAsync(g_h0, g_traj, frame_bytes, hipMemcpyDeviceToDevice, st);
+        return (int)hipMemsetAsync(g_h0, 0, frame_bytes, st);
+    }
+    if (hipError_t e = hipMemsetAsync(w.partials, 0, w.partials_bytes, st)) return (int)e;
+    const bool tile = batch_tile<T>(p, batch, {traj, g_traj, g_h0, adj}, true);
+    const bool fuse = tile ? tile_fuse_ok<T>(p)
+                           : (!p.opt.skip_wgrad && (p.opt.fuse_wgrad == 1 || (p.opt.fuse_wgrad == 2 && hc == 0)));
+    // (the direct sweep with fused sums reads the top frame's dL/dtraj where it lies, as rollout_bwd_impl does)
+    const T* top_in_place = (!tile && fuse) ? g_traj + (size_t)t_top * frame : nullptr;
+    if (!top_in_place)
+        if (hipError_t e = hipMemcpyAsync(adj + (size_t)t_top * frame, g_traj + (size_t)t_top * frame, frame_bytes,
+                                          hipMemcpyDeviceToDevice, st)) return (int)e;
+    unsigned rows = 0;
+    int t_cur = t_top;
+    if (tile) {
+        const int K = (p.opt.tile_k == 8 && p.hc != 0) ? 4 : p.opt.tile_k;
+        rows = (unsigned)tile_count<T>(p, true) * (unsigned)batch;
+        for (; t_cur - K >= 0; t_cur -= K) {
+            unsigned m = 0;
+            for (int q = 0; q < K; ++q) if (has(t_cur - 1 - q)) m |= 1u << q;
+            if (hipError_t e = adj_tile_b<T>(traj + (size_t)t_cur * frame, g_traj + (size_t)t_cur * frame, adj + (size_t)t_cur * frame,
+                                             m, g_h0, t_cur == K ? K : 0, w.partials, P, p, batch, st))
+                return (int)e;
+        }
+    }
+    for (int t = t_cur; t >= 1; --t) {
+        T* dst = (t == 1) ? g_h0 : adj + (size_t)(t - 1) * frame;
+        const T* inj = has(t - 1) ? g_traj + (size_t)(t - 1) * frame : nullptr;
+        const T* gin = (top_in_place && t == t_top) ? top_in_place : adj + (size_t)t * frame;
+        unsigned r2 = 0;
+        hipError_t e = fuse ? step_bwd_b<T, true>(traj + (size_t)(t - 1) * frame, gin, inj, dst, w.partials, P, p, batch, st, &r2)
+                            : step_bwd_b<T, false>(traj + (size_t)(t - 1) * frame, gin, inj, dst, w.partials, P, p, batch, st, &r2);
+        if (e) return (int)e;
+        if (r2 > rows) rows = r2;
+    }
+    if (p.opt.skip_wgrad || fuse) return (int)finish_grads(w, rows, hc, param_grad, st);
+    // time-parallel branch gradients over the flattened frame index f = t * B + b: state frame f pairs with adjoint frame f + B,
+    // i.e. the unbatched kernels' pair (f' - 1, f') with the adjoint base moved B - 1 samples up, over f' in (0, t_top * B]
+    const bool vec_ok = (p.n % pi::vec_width<T>::value == 0) && p.opt.vec != 1 && (reinterpret_cast<uintptr_t>(traj) % 16 == 0);
+    const T* adj_b = adj + (size_t)(batch - 1) * sample;
+    unsigned wrows = 0;
+    hipError_t e = vec_ok ? launch_wgrad<T, pi::vec_width<T>::value>(traj, adj_b, w.partials, P, p, 0, t_top * batch, &wrows, st)
+                          : launch_wgrad<T, 1>(traj, adj_b, w.partials, P, p, 0, t_top * batch, &wrows, st);
+    if (e) return (int)e;
+    return (int)finish_grads(w, rows > wrows ? rows : wrows, hc, param_grad, st);
+}
+
+
 // ---- physics residual over a trajectory (time-parallel; pre-contracted block of the TRUE equation) ----
 pi::FrameGrid make_frame_grid(long nchunks, unsigned frame_slots)
 {
@@ -3618,6 +3910,45 @@ int percnn_pi_persist_fence(void* stream)
 
 PI_EXPORT(f32, float)
 PI_EXPORT(f64, double)
+
+// batched rollouts (include/percnn_pi.h "Batched")
+size_t percnn_pi_batch_bwd_workspace_bytes(int hc, int ndim, const int64_t* shape, int batch, int elem_size)
+{
+    if (batch == 1) return percnn_pi_bwd_workspace_bytes(hc, ndim, shape, elem_size);
+    Problem p;
+    if (batch_problem(hc, ndim, shape, batch, p, nullptr, false) || (elem_size != 4 && elem_size != 8)) return 0;
+    return batch_step_workspace_bytes(p, batch, elem_size);
+}
+
+size_t percnn_pi_batch_rollout_bwd_workspace_bytes(int hc, int ndim, const int64_t* shape, int batch, int T_steps, int elem_size)
+{
+    if (batch == 1) return percnn_pi_rollout_bwd_workspace_bytes(hc, ndim, shape, T_steps, elem_size);
+    Problem p;
+    if (batch_problem(hc, ndim, shape, batch, p, nullptr, false) || (elem_size != 4 && elem_size != 8) || T_steps < 0) return 0;
+    return batch_rollout_workspace_bytes(p, batch, T_steps, elem_size);
+}
+
+#define PI_EXPORT_BATCH(SUF, T)                                                                                     \
+    int percnn_pi_batch_step_fwd_##SUF(const T* h, T* out, const T* params, int hc, int ndim, const int64_t* shape, \
+                                       int batch, const char* options, void* stream)                                \
+    { return batch_step_fwd_impl<T>(h, out, params, hc, ndim, shape, batch, options, stream); }                     \
+    int percnn_pi_batch_step_bwd_##SUF(const T* h, const T* g_out, const T* g_inject, T* g_in, double* param_grad, \
+                                       void* workspace, size_t workspace_bytes, const T* params, int hc, int ndim, \
+                                       const int64_t* shape, int batch, const char* options, void* stream)          \
+    { return batch_step_bwd_impl<T>(h, g_out, g_inject, g_in, param_grad, workspace, workspace_bytes, params, hc,  \
+                                    ndim, shape, batch, options, stream); }                                         \
+    int percnn_pi_batch_rollout_fwd_##SUF(T* traj, const T* params, int hc, int ndim, const int64_t* shape,         \
+                                          int batch, int T_steps, const char* options, void* stream)                \
+    { return batch_rollout_fwd_impl<T>(traj, params, hc, ndim, shape, batch, T_steps, options, stream); }           \
+    int percnn_pi_batch_rollout_bwd_##SUF(const T* traj, const T* g_traj, const unsigned char* frame_mask, T* g_h0, \
+                                          double* param_grad, void* workspace, size_t workspace_bytes,             \
+                                          const T* params, int hc, int ndim, const int64_t* shape, int batch,      \
+                                          int T_steps, const char* options, void* stream)                           \
+    { return batch_rollout_bwd_impl<T>(traj, g_traj, frame_mask, g_h0, param_grad, workspace, workspace_bytes,     \
+                                       params, hc, ndim, shape, batch, T_steps, options, stream); }
+
+PI_EXPORT_BATCH(f32, float)
+PI_EXPORT_BATCH(f64, double)
 
 // squared-error losses differentiated inside the sweep (include/percnn_pi.h)
 #define PI_EXPORT_LOSS(SUF, T)                                                                                      \

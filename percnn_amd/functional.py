@@ -849,9 +849,10 @@ def _cat_of_frames(seq, dim) -> Optional[torch.Tensor]:
     for j, f in enumerate(seq):
         if type(f) is not Frame or f._pi_stacked is not st or f._pi_index != i0 + j:
             return None
-    if i0 == 0 and n == st.shape[0]:
+    b = seq[0].shape[0]                                     # rows per frame: 1, or B of a batched rollout
+    if i0 == 0 and n * b == st.shape[0]:
         return st                                           # every frame: the buffer itself, no node in between
-    return st[i0:i0 + n]
+    return st[i0 * b:(i0 + n) * b]
 
 
 def link_frames(frames: Sequence[torch.Tensor], stacked: torch.Tensor) -> None:
@@ -909,6 +910,52 @@ class PiRolloutFramesFunction(torch.autograd.Function):
 
 def pi_rollout_frames(h0: torch.Tensor, P: torch.Tensor, steps: int, frames: Sequence[int], with_stacked: bool = False):
     out = PiRolloutFramesFunction.apply(h0, P, int(steps), tuple(frames))
+    return out if with_stacked else out[:-1]
+
+
+class PiRolloutBatchedFramesFunction(torch.autograd.Function):
+    """``PiRolloutFramesFunction`` for a batched initial state [B,2,*S]: one ``torch.ops.percnn.pi_rollout_batched`` call, the
+    frames are [B,2,*S] views of its [T+1,B,2,*S] buffer, the LAST output is that buffer as [(T+1)*B,2,*S] -- what
+    ``torch.cat(tuple(outputs), dim=0)`` of the batched frames is (train_2drd.py:394).  The backward runs ONE batched rollout
+    backward on the dense dL/dtraj."""
+
+    @staticmethod
+    def forward(ctx, h0, P, steps, frames):
+        _native()
+        P = P.contiguous()
+        traj = torch.ops.percnn.pi_rollout_batched(h0, P, steps, "")
+        ctx.save_for_backward(traj, P)
+        ctx.frames = tuple(int(k) for k in frames)
+        ctx.set_materialize_grads(False)
+        views = traj.unbind(0)
+        outs = []
+        for k in ctx.frames:
+            f = views[k].as_subclass(Frame)
+            f._pi_index = k
+            outs.append(f)
+        return tuple(outs) + (traj.view((-1,) + tuple(traj.shape[2:])),)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        traj, P = ctx.saved_tensors
+        g_stacked, grads = grads[-1], grads[:-1]
+        if g_stacked is None and all(g is None for g in grads):
+            return None, None, None, None
+        if g_stacked is not None:
+            g_traj = g_stacked.reshape(traj.shape)
+            if any(g is not None for g in grads):
+                g_traj = g_traj.clone()
+        else:
+            g_traj = torch.zeros_like(traj)
+        for k, g in zip(ctx.frames, grads):
+            if g is not None:
+                g_traj[k].add_(g)
+        g_h0, pg = torch.ops.percnn.pi_rollout_batched_backward(traj, P, g_traj.contiguous(), "")
+        return g_h0, pg, None, None
+
+
+def pi_rollout_batched_frames(h0: torch.Tensor, P: torch.Tensor, steps: int, frames: Sequence[int], with_stacked: bool = False):
+    out = PiRolloutBatchedFramesFunction.apply(h0, P, int(steps), tuple(frames))
     return out if with_stacked else out[:-1]
 
 
@@ -1023,3 +1070,18 @@ def pi_rollout(h0: torch.Tensor, P: torch.Tensor, steps: int, options=None) -> t
     """T fused steps -> trajectory [T+1,2,*S] through ``torch.ops.percnn.pi_rollout``."""
     _native()
     return torch.ops.percnn.pi_rollout(h0, P, int(steps), _options_str(options))
+
+
+def pi_step_batched(h: torch.Tensor, P: torch.Tensor, options=None) -> torch.Tensor:
+    """One fused step of B independent states [B,2,*S] with ONE parameter block: ``torch.ops.percnn.pi_step_batched`` (batch as a
+    grid dimension of the step kernels; sample b bit-identical to ``pi_step`` on that sample alone)."""
+    _native()
+    return torch.ops.percnn.pi_step_batched(h, P, _options_str(options))
+
+
+def pi_rollout_batched(h0: torch.Tensor, P: torch.Tensor, steps: int, options=None) -> torch.Tensor:
+    """T fused steps of B independent trajectories: h0 [B,2,*S] -> [T+1,B,2,*S] (frame-major; ``.flatten(0, 1)`` is the
+    reference's ``torch.cat(tuple(outputs), dim=0)`` of batched frames) through ``torch.ops.percnn.pi_rollout_batched``;
+    the parameter gradient is the sum over the samples."""
+    _native()
+    return torch.ops.percnn.pi_rollout_batched(h0, P, int(steps), _options_str(options))

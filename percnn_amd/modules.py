@@ -377,6 +377,9 @@ class RCNNCell(nn.Module):
 
     # -- reference interface -------------------------------------------------------------------
     def forward(self, h):
+        if h.dim() in (4, 5) and h.shape[0] > 1:           # B independent samples [B,2,*S], one block (compiled path too)
+            ch = F_pi.pi_step_batched(h, self.param_block())
+            return ch, ch
         if torch.compiler.is_compiling():
             ch = F_pi.pi_step(h, self.param_block())       # the registered operator is what a graph holds
             return ch, ch
@@ -802,10 +805,24 @@ class RCNN(nn.Module):
             return cell.param_block(fresh=True)
         return cell.param_block()
 
+    def _batched(self) -> bool:
+        """a batched initial state [B,2,*S], B > 1 (B independent trajectories, one parameter block)"""
+        h = self.init_state
+        return h is not None and h.dim() in (4, 5) and h.shape[0] > 1
+
+    def _check_batchable(self, what: str) -> None:
+        if hasattr(self.cell, "rollout") or isinstance(self.cell, Stage3BurgersCell):
+            raise ValueError(f"{what}: batched initial states (B > 1) need a cell on the Pi-block kernels; "
+                             f"{type(self.cell).__name__} has no batched path")
+
     def trajectory(self) -> torch.Tensor:
-        """[step+1, 2, *S]: every state of the rollout (what callers cat together, train_2drd.py:394)."""
+        """[step+1, 2, *S]: every state of the rollout (what callers cat together, train_2drd.py:394); batched initial state
+        [B,2,*S]: [step+1, B, 2, *S]."""
         if hasattr(self, "UpconvBlock"):
             self.init_state = self.UpconvBlock(self.init_state_low)
+        if self._batched():
+            self._check_batchable("RCNN.trajectory()")
+            return F_pi.pi_rollout_batched(self.init_state, self._block(), self.step)
         if hasattr(self.cell, "rollout"):                   # cells with their own kernels (Stage-1 block)
             return self.cell.rollout(self.init_state, self.step)
         return F_pi.pi_rollout(self.init_state, self._block(), self.step)
@@ -819,6 +836,8 @@ class RCNN(nn.Module):
             raise ValueError("observe() indexes the dense output list: effective_step must be list(range(step))")
         if hasattr(self, "UpconvBlock"):
             self.init_state = self.UpconvBlock(self.init_state_low)
+        if self._batched():
+            raise ValueError("observe() takes one trajectory: batched initial states (B > 1) go through forward() / trajectory()")
         t_idx = list(range(self.step + 1))[t_slice]
         ndim = self.init_state.dim() - 2
         if hasattr(self.cell, "rollout_observe"):           # cells with their own kernels (Stage-1 block)
@@ -841,6 +860,8 @@ class RCNN(nn.Module):
           its result.
 
         The full (detached) trajectory is kept in ``self.last_trajectory``."""
+        if self._batched() or (hasattr(self, "UpconvBlock") and self.init_state_low is not None and self.init_state_low.shape[0] > 1):
+            raise ValueError("loss_mse() takes one trajectory: batched initial states (B > 1) go through forward() / trajectory()")
         if space_stride != 1:
             pred = self.observe(t_slice, space_stride)
             t = torch.zeros_like(pred) if target is None else target
@@ -881,7 +902,10 @@ class RCNN(nn.Module):
         if self.step >= 2:
             frames.append(self.step - 1)                    # second_last_state rides along as one more output
         stacked = None
-        if hasattr(self.cell, "rollout_frames"):            # cells with their own kernels (Stage-1 block)
+        if self._batched():                                 # B trajectories: frames [B,2,*S], stacked [(step+1)*B,2,*S]
+            self._check_batchable("RCNN.forward()")
+            outs = F_pi.pi_rollout_batched_frames(self.init_state, self._block(), self.step, frames, with_stacked=True)
+        elif hasattr(self.cell, "rollout_frames"):          # cells with their own kernels (Stage-1 block)
             outs = self.cell.rollout_frames(self.init_state, self.step, frames, with_stacked=True)
         else:
             outs = F_pi.pi_rollout_frames(self.init_state, self._block(), self.step, frames, with_stacked=True)

@@ -14,6 +14,8 @@ so the operators pass ``torch.library.opcheck`` and trace under ``torch.compile(
     percnn::pi_step_backward(Tensor h, Tensor params, Tensor g_out, str options="") -> (Tensor, Tensor)
     percnn::pi_rollout(Tensor h0, Tensor params, int steps, str options="") -> Tensor
     percnn::pi_rollout_backward(Tensor traj, Tensor params, Tensor g_traj, str options="") -> (Tensor, Tensor)
+    percnn::pi_step_batched / pi_rollout_batched (+ *_backward): the same on B independent samples [B,2,*S] (trajectory
+            [T+1,B,2,*S]), one parameter block
     percnn::pi_rollout_observe(Tensor h0, Tensor params, int steps, int[] t_idx, int[] strides, str options="")
             -> (Tensor pred, Tensor traj)
     percnn::pi_rollout_observe_backward(Tensor traj, Tensor params, Tensor g_pred, int[] t_idx, int[] strides,
@@ -157,6 +159,23 @@ def load_native() -> None:
     @torch.library.register_fake(f"{_lib_ns}::pi_rollout_backward")
     def _(traj, params, g_traj, options=""):
         return traj.new_empty((1,) + tuple(traj.shape[1:])), torch.empty_like(params)
+
+    # batched: h [B,2,*S], trajectory [T+1,B,2,*S]
+    @torch.library.register_fake(f"{_lib_ns}::pi_step_batched")
+    def _(h, params, options=""):
+        return torch.empty_like(h, memory_format=torch.contiguous_format)
+
+    @torch.library.register_fake(f"{_lib_ns}::pi_step_batched_backward")
+    def _(h, params, g_out, options=""):
+        return torch.empty_like(h, memory_format=torch.contiguous_format), torch.empty_like(params)
+
+    @torch.library.register_fake(f"{_lib_ns}::pi_rollout_batched")
+    def _(h0, params, steps, options=""):
+        return h0.new_empty((steps + 1,) + tuple(h0.shape))
+
+    @torch.library.register_fake(f"{_lib_ns}::pi_rollout_batched_backward")
+    def _(traj, params, g_traj, options=""):
+        return traj.new_empty(tuple(traj.shape[1:])), torch.empty_like(params)
 
     _native_loaded = True
 
