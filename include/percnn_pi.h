@@ -638,6 +638,46 @@ int percnn_pi_batch_rollout_bwd_f64(const double *traj, const double *g_traj, co
                                     double *param_grad, void *workspace, size_t workspace_bytes, const double *params, int hc,
                                     int ndim, const int64_t *shape, int batch, int T, const char *options, void *stream);
 
+/* ---- Ensembles: B independent trajectories, ONE parameter block PER SAMPLE ----------------------------------------------------
+ * A parameter study (a Gray-Scott (f, k) map, a seed ensemble of trained cells, B checkpoints on the same initial conditions)
+ * varies the block.  These entry points take the signatures of percnn_pi_batch_* with
+ *   params       [B][np]                        np = the length of one block (all of one kind: same hc); dt, the stencil taps
+ *                                               and every other slot may differ between samples
+ *   param_grad   double [B][np]                 row b: sample b's gradient, ACCUMULATED (+=), NOT summed over the samples
+ * and everything else as there (states [B][2][*S], trajectories [T+1][B][2][*S] frame-major, frame_mask applied to every
+ * sample).  Every state and adjoint field of sample b is bit-identical to the unbatched entry point on (h0[b], params[b]); row b
+ * of param_grad equals that call's gradient to reduction round-off and is bit-identical from run to run.  The kernels are the
+ * batched path's in an ensemble flavour: the workgroups of sample b read block b, and every partial gradient row of sample b lies
+ * in its own range (one stride for all launches of a call), summed per sample in a fixed order.
+ * Validation before any launch: batch < 1 (or > 65535), the advective block (hc == -1), NULL pointers, an output that aliases
+ * an input, or bad options -> PERCNN_PI_EINVAL; a workspace below *_workspace_bytes -> PERCNN_PI_EWORKSPACE.  batch == 1 is the
+ * unbatched entry point on params[0] (same kernels, same workspace size).  The workspace queries return 0 for invalid problems
+ * (the advective block included).  Resident, 3D brick and plane-streaming kernels are not dispatched for batch > 1. */
+size_t percnn_pi_ensemble_bwd_workspace_bytes(int hc, int ndim, const int64_t *shape, int batch, int elem_size);
+size_t percnn_pi_ensemble_rollout_bwd_workspace_bytes(int hc, int ndim, const int64_t *shape, int batch, int T, int elem_size);
+int percnn_pi_ensemble_step_fwd_f32(const float *h, float *out, const float *params, int hc, int ndim, const int64_t *shape,
+                                    int batch, const char *options, void *stream);
+int percnn_pi_ensemble_step_fwd_f64(const double *h, double *out, const double *params, int hc, int ndim,
+                                    const int64_t *shape, int batch, const char *options, void *stream);
+int percnn_pi_ensemble_step_bwd_f32(const float *h, const float *g_out, const float *g_inject, float *g_in, double *param_grad,
+                                    void *workspace, size_t workspace_bytes, const float *params, int hc, int ndim,
+                                    const int64_t *shape, int batch, const char *options, void *stream);
+int percnn_pi_ensemble_step_bwd_f64(const double *h, const double *g_out, const double *g_inject, double *g_in,
+                                    double *param_grad, void *workspace, size_t workspace_bytes, const double *params, int hc,
+                                    int ndim, const int64_t *shape, int batch, const char *options, void *stream);
+int percnn_pi_ensemble_rollout_fwd_f32(float *traj, const float *params, int hc, int ndim, const int64_t *shape, int batch,
+                                       int T, const char *options, void *stream);
+int percnn_pi_ensemble_rollout_fwd_f64(double *traj, const double *params, int hc, int ndim, const int64_t *shape, int batch,
+                                       int T, const char *options, void *stream);
+int percnn_pi_ensemble_rollout_bwd_f32(const float *traj, const float *g_traj, const unsigned char *frame_mask, float *g_h0,
+                                       double *param_grad, void *workspace, size_t workspace_bytes, const float *params,
+                                       int hc, int ndim, const int64_t *shape, int batch, int T, const char *options,
+                                       void *stream);
+int percnn_pi_ensemble_rollout_bwd_f64(const double *traj, const double *g_traj, const unsigned char *frame_mask,
+                                       double *g_h0, double *param_grad, void *workspace, size_t workspace_bytes,
+                                       const double *params, int hc, int ndim, const int64_t *shape, int batch, int T,
+                                       const char *options, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,8 +14,9 @@ loss;  ``synthetic`` initial states for benchmarks / tests.
 """
 from ._lib import build, lib, set_option, LIB_PATH  # noqa: F401
 from .functional import (pi_step, pi_rollout, pack_params, contract_block, param_count, rollout_fwd_, rollout_bwd,  # noqa: F401
-                         step_fwd, step_bwd, PiStepFunction, PiRolloutFunction, pi_step_batched, pi_rollout_batched)
-from .modules import RCNNCell, RCNN, Upscaler, Stage3LambdaOmegaCell, Stage3BurgersCell, gs2d_cell, gs3d_cell, lo2d_cell, laplace_stencil  # noqa: F401
+                         step_fwd, step_bwd, PiStepFunction, PiRolloutFunction, pi_step_batched, pi_rollout_batched,
+                         pi_step_ensemble, pi_rollout_ensemble)
+from .modules import RCNNCell, RCNN, Upscaler, Stage3LambdaOmegaCell, Stage3BurgersCell, gs2d_cell, gs3d_cell, lo2d_cell, laplace_stencil, CellEnsemble  # noqa: F401
 
 from . import ops  # noqa: F401  (registers torch.ops.percnn.*)
 from . import slab, synthetic, physics, stage1  # noqa: F401

@@ -65,8 +65,10 @@ EXPORTS = [
                 "slab_step_fwd_range", "slab_step_bwd_range", "slab_rollout_fwd", "slab_rollout_bwd", "residual_fwd",
                 "residual_bwd", "contract_fwd", "contract_bwd", "step_fwd_opt", "step_bwd_opt", "rollout_fwd_opt",
                 "rollout_bwd_opt", "rollout_bwd_sqerr", "traj_sqerr", "step_bwd_rows", "bwd_rows_finish", "rollout_bwd_top",
-                "batch_step_fwd", "batch_step_bwd", "batch_rollout_fwd", "batch_rollout_bwd")] + [
+                "batch_step_fwd", "batch_step_bwd", "batch_rollout_fwd", "batch_rollout_bwd", "ensemble_step_fwd",
+                "ensemble_step_bwd", "ensemble_rollout_fwd", "ensemble_rollout_bwd")] + [
     "percnn_pi_batch_bwd_workspace_bytes", "percnn_pi_batch_rollout_bwd_workspace_bytes",
+    "percnn_pi_ensemble_bwd_workspace_bytes", "percnn_pi_ensemble_rollout_bwd_workspace_bytes",
     "percnn_pi_s1_param_count", "percnn_pi_s1_step_fwd_f32", "percnn_pi_s1_rollout_fwd_f32",
     "percnn_pi_s1_rollout_bwd_workspace_bytes", "percnn_pi_s1_rollout_bwd_f32", "percnn_pi_s1_set_option",
     "percnn_pi_conv3d_k5c8_f32", "percnn_pi_conv3d_k5c8_wgrad_workspace_bytes", "percnn_pi_conv3d_k5c8_wgrad_f32",
@@ -254,10 +256,22 @@ def lib() -> ctypes.CDLL:
         f.restype, f.argtypes = ci, [vp, vp, ci, ci, i64p, ci, ci, cs, vp]
         f = getattr(L, f"percnn_pi_batch_rollout_bwd_{suf}")
         f.restype, f.argtypes = ci, [vp, vp, cs, vp, vp, vp, sz, vp, ci, ci, i64p, ci, ci, cs, vp]
+        f = getattr(L, f"percnn_pi_ensemble_step_fwd_{suf}")
+        f.restype, f.argtypes = ci, [vp, vp, vp, ci, ci, i64p, ci, cs, vp]
+        f = getattr(L, f"percnn_pi_ensemble_step_bwd_{suf}")
+        f.restype, f.argtypes = ci, [vp, vp, vp, vp, vp, vp, sz, vp, ci, ci, i64p, ci, cs, vp]
+        f = getattr(L, f"percnn_pi_ensemble_rollout_fwd_{suf}")
+        f.restype, f.argtypes = ci, [vp, vp, ci, ci, i64p, ci, ci, cs, vp]
+        f = getattr(L, f"percnn_pi_ensemble_rollout_bwd_{suf}")
+        f.restype, f.argtypes = ci, [vp, vp, cs, vp, vp, vp, sz, vp, ci, ci, i64p, ci, ci, cs, vp]
     L.percnn_pi_batch_bwd_workspace_bytes.restype = sz
     L.percnn_pi_batch_bwd_workspace_bytes.argtypes = [ci, ci, i64p, ci, ci]
     L.percnn_pi_batch_rollout_bwd_workspace_bytes.restype = sz
     L.percnn_pi_batch_rollout_bwd_workspace_bytes.argtypes = [ci, ci, i64p, ci, ci, ci]
+    L.percnn_pi_ensemble_bwd_workspace_bytes.restype = sz
+    L.percnn_pi_ensemble_bwd_workspace_bytes.argtypes = [ci, ci, i64p, ci, ci]
+    L.percnn_pi_ensemble_rollout_bwd_workspace_bytes.restype = sz
+    L.percnn_pi_ensemble_rollout_bwd_workspace_bytes.argtypes = [ci, ci, i64p, ci, ci, ci]
     L.percnn_pi_residual_sqloss_workspace_bytes.restype, L.percnn_pi_residual_sqloss_workspace_bytes.argtypes = sz, []
     L.percnn_pi_s1_param_count.restype = sz
     L.percnn_pi_s1_param_count.argtypes = []

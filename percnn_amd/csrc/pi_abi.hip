@@ -2728,6 +2728,9 @@ int batch_problem(int hc, int ndim, const int64_t* shape, int batch, Problem& p,
     return 0;
 }
 
+// Launchers below: ens_rows = -1 runs the batched kernels (one block P); ens_rows >= 0 the ensemble kernels of the same
+// shape (P [B][np], partial rows at sample * ens_rows; "ensembles" further down).
+
 // tile vs direct: the per-sample rules of tile_eligible, with the size limits of the "tile = 1" rule applied to the points of
 // the whole batch (the tile kernels pay while the launches are latency-bound: 100^2 x 64 still is)
 template <typename T>
@@ -2739,12 +2742,19 @@ bool batch_tile(const Problem& p, int batch, std::initializer_list<const void*> 
 }
 
 template <typename T, int HC, int K, int NT, int BY = TILE_B, int BX = TILE_B>
-hipError_t launch_fwd_tile_b(T* frame_t, const T* P, const Problem& p, int batch, hipStream_t st)
+hipError_t launch_fwd_tile_b(T* frame_t, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows = -1)
 {
     using TL = pi::Tile<K, BX, BY>;
     const pi::TileGeom g = make_tile_geom(p, BY, BX);
     const unsigned grid = (unsigned)(((p.n0 + BY - 1) / BY) * g.tiles_x);
     const size_t lds = (size_t)4 * TL::PLANE * sizeof(T) + 32 /* lds_pad0/1 */ + (size_t)p.opt.lds_pad;
+    if (ens_rows >= 0) {
+        auto* k = pi::pi_fwd2d_tile_ens_kernel<T, HC, K, BX, BY, NT>;
+        if (hipError_t e = allow_lds(k, lds)) return e;
+        hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(NT), lds, st, frame_t, (long)batch * 2 * p.n, (long)(2 * p.n), P, g,
+                           pi::nparams(p.hc));
+        return hipGetLastError();
+    }
     auto* k = pi::pi_fwd2d_tile_batch_kernel<T, HC, K, BX, BY, NT>;
     if (hipError_t e = allow_lds(k, lds)) return e;
     hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(NT), lds, st, frame_t, (long)batch * 2 * p.n, (long)(2 * p.n), P, g);
@@ -2753,7 +2763,7 @@ hipError_t launch_fwd_tile_b(T* frame_t, const T* P, const Problem& p, int batch
 
 template <typename T, int HC, int K, int NT, int BY = TILE_B, bool MOM = false, int BX = TILE_B>
 hipError_t launch_adj_tile_b(const T* hframe_t, const T* gframe_t, T* aframe_t, unsigned inj_mask, T* g_h0, int steps_to_zero,
-                             double* partials, const T* P, const Problem& p, int batch, hipStream_t st)
+                             double* partials, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows = -1)
 {
     using TL = pi::Tile<K, BX, BY>;
     const pi::TileGeom g = make_tile_geom(p, BY, BX);
@@ -2767,6 +2777,13 @@ hipError_t launch_adj_tile_b(const T* hframe_t, const T* gframe_t, T* aframe_t, 
     if (MOM && sizeof(T) == 8)
         lds = pi::tile_state_bytes<T, K, BX, BY>() + (size_t)20 * NT * sizeof(double);
     lds += (size_t)p.opt.lds_pad;
+    if (ens_rows >= 0) {
+        auto* k = pi::pi_adj2d_tile_ens_kernel<T, HC, K, BX, BY, NT, MOM>;
+        if (hipError_t e = allow_lds(k, lds)) return e;
+        hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(NT), lds, st, hframe_t, gframe_t, aframe_t, (long)batch * 2 * p.n,
+                           (long)(2 * p.n), inj_mask, g_h0, steps_to_zero, partials, pi::nparams(p.hc), P, g, ens_rows);
+        return hipGetLastError();
+    }
     auto* k = pi::pi_adj2d_tile_batch_kernel<T, HC, K, BX, BY, NT, MOM>;
     if (hipError_t e = allow_lds(k, lds)) return e;
     hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(NT), lds, st, hframe_t, gframe_t, aframe_t, (long)batch * 2 * p.n,
@@ -2776,28 +2793,29 @@ hipError_t launch_adj_tile_b(const T* hframe_t, const T* gframe_t, T* aframe_t, 
 
 // the tile variant fwd_tile / adj_tile pick for one sample, on all samples
 template <typename T>
-hipError_t fwd_tile_b(T* frame_t, const T* P, const Problem& p, int batch, hipStream_t st)
+hipError_t fwd_tile_b(T* frame_t, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows = -1)
 {
     if constexpr (sizeof(T) == 4) {
         switch (tile_wide_for<T>(p, false)) {
-            case 1: return launch_fwd_tile_b<T, pi::POLY, 4, 640, 40, 32>(frame_t, P, p, batch, st);
-            case 2: return launch_fwd_tile_b<T, pi::POLY, 4, 768, 40, 40>(frame_t, P, p, batch, st);
+            case 1: return launch_fwd_tile_b<T, pi::POLY, 4, 640, 40, 32>(frame_t, P, p, batch, st, ens_rows);
+            case 2: return launch_fwd_tile_b<T, pi::POLY, 4, 768, 40, 40>(frame_t, P, p, batch, st, ens_rows);
             default: break;
         }
     }
-#define CALL_FTB(HC, K, NT, ...) launch_fwd_tile_b<T, HC, K, NT, ##__VA_ARGS__>(frame_t, P, p, batch, st)
+#define CALL_FTB(HC, K, NT, ...) launch_fwd_tile_b<T, HC, K, NT, ##__VA_ARGS__>(frame_t, P, p, batch, st, ens_rows)
     PI_TILE_DISPATCH(CALL_FTB);
 #undef CALL_FTB
 }
 
 template <typename T>
 hipError_t adj_tile_b(const T* hframe_t, const T* gframe_t, T* aframe_t, unsigned inj_mask, T* g_h0, int steps_to_zero,
-                      double* partials, const T* P, const Problem& p, int batch, hipStream_t st)
+                      double* partials, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows = -1)
 {
     if constexpr (sizeof(T) == 4) {
         const bool fused = tile_fuse_ok<T>(p);
 #define CALL_WIDE_B(NT, BY, BX, MOM) launch_adj_tile_b<T, pi::POLY, 4, NT, BY, MOM, BX>(hframe_t, gframe_t, aframe_t, inj_mask, \
-                                                                                      g_h0, steps_to_zero, partials, P, p, batch, st)
+                                                                                      g_h0, steps_to_zero, partials, P, p, batch, st, \
+                                                                                      ens_rows)
         switch (tile_wide_for<T>(p, true)) {
             case 1: return fused ? CALL_WIDE_B(640, 40, 32, true) : CALL_WIDE_B(640, 40, 32, false);
             case 2: return fused ? CALL_WIDE_B(768, 40, 40, true) : CALL_WIDE_B(768, 40, 40, false);
@@ -2807,15 +2825,15 @@ hipError_t adj_tile_b(const T* hframe_t, const T* gframe_t, T* aframe_t, unsigne
     }
     if (tile_fuse_ok<T>(p))
         return launch_adj_tile_b<T, pi::POLY, 4, 512, TILE_B, true>(hframe_t, gframe_t, aframe_t, inj_mask, g_h0, steps_to_zero,
-                                                                    partials, P, p, batch, st);
+                                                                    partials, P, p, batch, st, ens_rows);
 #define CALL_ATB(HC, K, NT, ...) launch_adj_tile_b<T, HC, K, NT, ##__VA_ARGS__>(hframe_t, gframe_t, aframe_t, inj_mask, g_h0, \
-                                                                               steps_to_zero, partials, P, p, batch, st)
+                                                                               steps_to_zero, partials, P, p, batch, st, ens_rows)
     PI_TILE_DISPATCH(CALL_ATB);
 #undef CALL_ATB
 }
 
 template <typename T, int NDIM, int HC, int VEC>
-hipError_t launch_fwd_b(const T* h, T* out, const T* P, const Problem& p, int batch, hipStream_t st)
+hipError_t launch_fwd_b(const T* h, T* out, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows = -1)
 {
     Geom g = make_geom(p);
     const int block = direct_block(p, g, VEC);
@@ -2823,6 +2841,11 @@ hipError_t launch_fwd_b(const T* h, T* out, const T* P, const Problem& p, int ba
     if (!set_blockmap(g, NDIM, VEC, block, sizeof(T), p.opt.l2_tile_kb * 1024, 1, (long)p.opt.l2_tile_min_kb * 1024, p.opt.lane_x))
         return (hipError_t)PERCNN_PI_ETOOLARGE;
     g.xwin = 0;
+    if (ens_rows >= 0) {
+        hipLaunchKernelGGL((pi::pi_fwd_ens_kernel<T, NDIM, HC, VEC>), dim3(g.nblk, (unsigned)batch), dim3(block), 0, st, h, out, P,
+                           g, p.hc, (long)(2 * p.n), pi::nparams(p.hc));
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL((pi::pi_fwd_batch_kernel<T, NDIM, HC, VEC>), dim3(g.nblk, (unsigned)batch), dim3(block), 0, st, h, out, P,
                        g, p.hc, (long)(2 * p.n));
     return hipGetLastError();
@@ -2830,7 +2853,7 @@ hipError_t launch_fwd_b(const T* h, T* out, const T* P, const Problem& p, int ba
 
 template <typename T, int NDIM, int HC, int VEC, bool WGRAD>
 hipError_t launch_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* partials, const T* P, const Problem& p, int batch,
-                        hipStream_t st, unsigned* rows_out)
+                        hipStream_t st, unsigned* rows_out, int ens_rows = -1)
 {
     Geom g = make_geom(p);
     const int block = direct_block(p, g, VEC);
@@ -2841,6 +2864,14 @@ hipError_t launch_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* par
     const size_t lds = align_up((size_t)(block / pi::WAVE) * pi::nparams(p.hc) * sizeof(T), 16) +
                        (size_t)(block / pi::WAVE) * 2 * sizeof(double) +
                        ((WGRAD && HC == pi::POLY) ? (size_t)20 * (block + 8) * sizeof(T) : 0);
+    if (ens_rows >= 0) {
+        if (grid > (unsigned)ens_rows) return (hipError_t)PERCNN_PI_ETOOLARGE;   // ens_rows bounds every launch (ens_rows_for)
+        auto* k = pi::pi_bwd_ens_kernel<T, NDIM, HC, VEC, WGRAD>;
+        if (hipError_t e = allow_lds(k, lds)) return e;
+        hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(block), lds, st, h, G, inj, Gp, partials, P, g, p.hc,
+                           (long)(2 * p.n), ens_rows);
+        return hipGetLastError();
+    }
     auto* k = pi::pi_bwd_batch_kernel<T, NDIM, HC, VEC, WGRAD>;
     if (hipError_t e = allow_lds(k, lds)) return e;
     hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(block), lds, st, h, G, inj, Gp, partials, P, g, p.hc, (long)(2 * p.n));
@@ -2849,20 +2880,20 @@ hipError_t launch_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* par
 }
 
 template <typename T>
-hipError_t step_fwd_b(const T* h, T* out, const T* P, const Problem& p, int batch, hipStream_t st)
+hipError_t step_fwd_b(const T* h, T* out, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows = -1)
 {
     const int vec = pick_vec<T>(p, {h, out});
-#define CALL_FWDB(NDIM, HC, VEC) launch_fwd_b<T, NDIM, HC, VEC>(h, out, P, p, batch, st)
+#define CALL_FWDB(NDIM, HC, VEC) launch_fwd_b<T, NDIM, HC, VEC>(h, out, P, p, batch, st, ens_rows)
     PI_DISPATCH(CALL_FWDB);
 #undef CALL_FWDB
 }
 
 template <typename T, bool WGRAD>
 hipError_t step_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* partials, const T* P, const Problem& p, int batch,
-                      hipStream_t st, unsigned* rows_out)
+                      hipStream_t st, unsigned* rows_out, int ens_rows = -1)
 {
     const int vec = pick_vec<T>(p, {h, G, inj, Gp});
-#define CALL_BWDB(NDIM, HC, VEC) launch_bwd_b<T, NDIM, HC, VEC, WGRAD>(h, G, inj, Gp, partials, P, p, batch, st, rows_out)
+#define CALL_BWDB(NDIM, HC, VEC) launch_bwd_b<T, NDIM, HC, VEC, WGRAD>(h, G, inj, Gp, partials, P, p, batch, st, rows_out, ens_rows)
     PI_DISPATCH(CALL_BWDB);
 #undef CALL_BWDB
 }
@@ -3002,6 +3033,209 @@ int batch_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* 
                           : launch_wgrad<T, 1>(traj, adj_b, w.partials, P, p, 0, t_top * batch, &wrows, st);
     if (e) return (int)e;
     return (int)finish_grads(w, rows > wrows ? rows : wrows, hc, param_grad, st);
+}
+
+
+// ---- ensembles: B independent trajectories, one parameter block per sample (include/percnn_pi.h "Ensembles") ---------------
+// The launches of the batched path with the ensemble kernels (pi_*_ens_kernel): workgroup (x, b) reads block P + b * np.  Every
+// partial gradient row of sample b lies in [b * rows, (b + 1) * rows) -- `rows` is one bound for every launch of a call
+// (ens_rows_for) -- and pi_reduce_partials_ens_kernel sums the rows of each sample alone, in a fixed order, into param_grad[b].
+int ens_problem(int hc, int ndim, const int64_t* shape, int batch, Problem& p, const char* options, bool launches = true)
+{
+    if (hc == -1) return PERCNN_PI_EINVAL;                  // the advective block has no ensemble flavour
+    return batch_problem(hc, ndim, shape, batch, p, options, launches);
+}
+
+// workgroups per sample of the ensemble gradient pass: launch_wgrad's count for the steps of the whole batch, split over the
+// samples (the same number of workgroups and chunks per lane as the batched pass over the flattened frame index)
+long ens_wgrad_blocks(const Problem& p, int batch, int t_top, int vec)
+{
+    const long total = (long)t_top * batch * (p.n / vec);
+    long nb = (total + 256L * 16 - 1) / (256L * 16);
+    if (nb > p.opt.wgrad_blocks) nb = p.opt.wgrad_blocks;
+    nb = (nb + batch - 1) / batch;
+    return nb < 1 ? 1 : nb;
+}
+
+// partial rows per sample: the most that any launch of the call writes for one sample -- the tile sweep one per tile, the direct
+// sweep its grid (either lane width), the gradient pass two per workgroup (t_top = 0: no gradient pass).  Each of these is at
+// most MAX_BWD_BLOCKS, so B rows of the unbatched workspace's partials hold them.
+template <typename T>
+int ens_rows_for(const Problem& p, int batch, bool tile, int t_top)
+{
+    long r = tile ? tile_count<T>(p, true) : 0;
+    for (int v : {1, (int)pi::vec_width<T>::value}) {
+        const long d = bwd_grid(p, v, sizeof(T), 1);
+        if (d > r) r = d;
+        if (t_top > 0 && 2 * ens_wgrad_blocks(p, batch, t_top, v) > r) r = 2 * ens_wgrad_blocks(p, batch, t_top, v);
+    }
+    return (int)(r < MAX_BWD_BLOCKS ? r : MAX_BWD_BLOCKS);
+}
+
+hipError_t ens_finish_grads(const double* partials, int rows, int batch, int hc, double* param_grad, hipStream_t st)
+{
+    const int np = pi::nparams(hc);
+    hipLaunchKernelGGL(pi::pi_reduce_partials_ens_kernel, dim3(np, (unsigned)batch), dim3(pi::WAVE), 0, st, partials, rows, np,
+                       param_grad);
+    return hipGetLastError();
+}
+
+// time-parallel branch gradients of all samples, ONE launch per hidden-channel group (sample = grid z; launch_wgrad_pass)
+template <typename T, int JC, int NS, int VEC>
+hipError_t launch_wgrad_ens_pass(const T* traj, const T* adj, double* partials, const T* P, const Problem& p, int batch, int t_top,
+                                 int j0, unsigned nb, int rows, hipStream_t st)
+{
+    const int block = 256;
+    const size_t lds = (size_t)(block / pi::WAVE) * NS * (10 * JC + 1) * sizeof(T);
+    hipLaunchKernelGGL((pi::pi_wgrad_ens_kernel<T, JC, NS, VEC>), dim3(nb, NS == 2 ? 1 : 2, (unsigned)batch), dim3(block), lds, st,
+                       traj, adj, partials, P, (long)p.n, (long)p.n, 0L, 0, t_top, p.hc, j0, (long)batch * 2 * p.n, rows);
+    return hipGetLastError();
+}
+
+// steps (0, t_top] of every sample: state frame t-1 and adjoint frame t of sample b at (t-1) * B + b and t * B + b (launch_wgrad)
+template <typename T, int VEC>
+hipError_t launch_wgrad_ens(const T* traj, const T* adj, double* partials, const T* P, const Problem& p, int batch, int t_top,
+                            int rows, hipStream_t st)
+{
+    const unsigned nb = (unsigned)ens_wgrad_blocks(p, batch, t_top, VEC);
+    if (p.hc == 0) {                                           // pre-contracted mode: coefficient moments
+        const size_t lds = (size_t)(256 / pi::WAVE) * 20 * sizeof(T);
+        hipLaunchKernelGGL((pi::pi_moments_ens_kernel<T, VEC>), dim3(nb, (unsigned)batch), dim3(256), lds, st, traj, adj, partials,
+                           P, (long)p.n, (long)p.n, 0L, 0, t_top, (long)batch * 2 * p.n, rows);
+        return hipGetLastError();
+    }
+    if (p.hc == 2) return launch_wgrad_ens_pass<T, 2, 2, VEC>(traj, adj, partials, P, p, batch, t_top, 0, nb, rows, st);
+    if (p.hc == 4) return launch_wgrad_ens_pass<T, 4, 2, VEC>(traj, adj, partials, P, p, batch, t_top, 0, nb, rows, st);
+    const int jc = p.hc % 8 == 0 ? 8 : p.hc % 4 == 0 ? 4 : p.hc % 2 == 0 ? 2 : 1;
+    for (int j0 = 0; j0 < p.hc; j0 += jc) {
+        hipError_t e;
+        switch (jc) {
+            case 8:  e = launch_wgrad_ens_pass<T, 8, 1, VEC>(traj, adj, partials, P, p, batch, t_top, j0, nb, rows, st); break;
+            case 4:  e = launch_wgrad_ens_pass<T, 4, 1, VEC>(traj, adj, partials, P, p, batch, t_top, j0, nb, rows, st); break;
+            case 2:  e = launch_wgrad_ens_pass<T, 2, 1, VEC>(traj, adj, partials, P, p, batch, t_top, j0, nb, rows, st); break;
+            default: e = launch_wgrad_ens_pass<T, 1, 1, VEC>(traj, adj, partials, P, p, batch, t_top, j0, nb, rows, st); break;
+        }
+        if (e) return e;
+    }
+    return hipSuccess;
+}
+
+template <typename T>
+int ens_step_fwd_impl(const T* h, T* out, const T* P, int hc, int ndim, const int64_t* shape, int batch, const char* options,
+                      void* stream)
+{
+    Problem p;
+    if (int rc = ens_problem(hc, ndim, shape, batch, p, options)) return rc;
+    if (!h || !out || !P || h == out || P == out) return PERCNN_PI_EINVAL;
+    if (batch == 1) return step_fwd_impl<T>(h, out, P, hc, ndim, shape, stream, false, 2, 0, options);
+    return (int)step_fwd_b<T>(h, out, P, p, batch, static_cast<hipStream_t>(stream), 0);
+}
+
+template <typename T>
+int ens_step_bwd_impl(const T* h, const T* g_out, const T* g_inj, T* g_in, double* param_grad, void* ws, size_t ws_bytes,
+                      const T* P, int hc, int ndim, const int64_t* shape, int batch, const char* options, void* stream)
+{
+    Problem p;
+    if (int rc = ens_problem(hc, ndim, shape, batch, p, options)) return rc;
+    if (!h || !g_out || !g_in || !param_grad || !P || g_in == g_out || g_in == h || g_in == g_inj || g_in == P)
+        return PERCNN_PI_EINVAL;
+    if (batch == 1)
+        return step_bwd_impl<T>(h, g_out, g_inj, g_in, param_grad, ws, ws_bytes, P, hc, ndim, shape, stream, false, 2, 0, -1, -1,
+                                options);
+    if (!ws || ws_bytes < batch_step_workspace_bytes(p, batch, sizeof(T)) || (reinterpret_cast<uintptr_t>(ws) % 16))
+        return PERCNN_PI_EWORKSPACE;
+    auto st = static_cast<hipStream_t>(stream);
+    double* partials = reinterpret_cast<double*>(static_cast<unsigned char*>(ws) +
+                                                 2 * align_up((size_t)batch * 2 * p.n * sizeof(T), 256));
+    const int rows = ens_rows_for<T>(p, batch, false, 0);
+    if (hipError_t e = hipMemsetAsync(partials, 0, (size_t)batch * rows * pi::nparams(hc) * sizeof(double), st)) return (int)e;
+    if (hipError_t e = step_bwd_b<T, true>(h, g_out, g_inj, g_in, partials, P, p, batch, st, nullptr, rows)) return (int)e;
+    return (int)ens_finish_grads(partials, rows, batch, hc, param_grad, st);
+}
+
+template <typename T>
+int ens_rollout_fwd_impl(T* traj, const T* P, int hc, int ndim, const int64_t* shape, int batch, int T_steps, const char* options,
+                         void* stream)
+{
+    Problem p;
+    if (int rc = ens_problem(hc, ndim, shape, batch, p, options)) return rc;
+    if (!traj || !P || T_steps < 0 || P == traj) return PERCNN_PI_EINVAL;
+    if (batch == 1) return rollout_fwd_impl<T>(traj, P, hc, ndim, shape, T_steps, stream, options);
+    auto st = static_cast<hipStream_t>(stream);
+    const size_t frame = (size_t)batch * 2 * p.n;          // frame t of all samples: [B][2][*S]
+    int t = 0;
+    if (batch_tile<T>(p, batch, {traj}, false)) {
+        const int K = (p.opt.tile_k == 8 && p.hc != 0) ? 4 : p.opt.tile_k;
+        for (; t + K <= T_steps; t += K)
+            if (hipError_t e = fwd_tile_b<T>(traj + (size_t)t * frame, P, p, batch, st, 0)) return (int)e;
+    }
+    for (; t < T_steps; ++t)
+        if (hipError_t e = step_fwd_b<T>(traj + (size_t)t * frame, traj + (size_t)(t + 1) * frame, P, p, batch, st, 0)) return (int)e;
+    return 0;
+}
+
+template <typename T>
+int ens_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* mask, T* g_h0, double* param_grad, void* ws,
+                         size_t ws_bytes, const T* P, int hc, int ndim, const int64_t* shape, int batch, int T_steps,
+                         const char* options, void* stream)
+{
+    Problem p;
+    if (int rc = ens_problem(hc, ndim, shape, batch, p, options)) return rc;
+    if (!traj || !g_traj || !g_h0 || !param_grad || !P || T_steps < 0 || g_h0 == traj || g_h0 == g_traj || g_h0 == P)
+        return PERCNN_PI_EINVAL;
+    if (batch == 1)
+        return rollout_bwd_impl<T>(traj, g_traj, mask, g_h0, param_grad, ws, ws_bytes, P, hc, ndim, shape, T_steps, stream, options);
+    if (!ws || ws_bytes < batch_rollout_workspace_bytes(p, batch, T_steps, sizeof(T)) || (reinterpret_cast<uintptr_t>(ws) % 16))
+        return PERCNN_PI_EWORKSPACE;
+    auto st = static_cast<hipStream_t>(stream);
+    const size_t frame = (size_t)batch * 2 * p.n;
+    const size_t frame_bytes = frame * sizeof(T);
+    T* adj = static_cast<T*>(ws);                          // adjoint trajectory [T+1][B][2][*S]
+    double* partials = reinterpret_cast<double*>(static_cast<unsigned char*>(ws) + align_up((size_t)(T_steps + 1) * frame_bytes, 256));
+    auto has = [&](int t) { return !mask || mask[t]; };
+    int t_top = T_steps;
+    while (t_top > 0 && !has(t_top)) --t_top;
+    if (t_top == 0) {
+        if (has(0)) return (int)hipMemcpyAsync(g_h0, g_traj, frame_bytes, hipMemcpyDeviceToDevice, st);
+        return (int)hipMemsetAsync(g_h0, 0, frame_bytes, st);
+    }
+    const bool tile = batch_tile<T>(p, batch, {traj, g_traj, g_h0, adj}, true);
+    const bool fuse = tile ? tile_fuse_ok<T>(p)
+                           : (!p.opt.skip_wgrad && (p.opt.fuse_wgrad == 1 || (p.opt.fuse_wgrad == 2 && hc == 0)));
+    const bool pass = !p.opt.skip_wgrad && !fuse;          // time-parallel gradient pass after the sweep
+    const int rows = ens_rows_for<T>(p, batch, tile, pass ? t_top : 0);
+    if (hipError_t e = hipMemsetAsync(partials, 0, (size_t)batch * rows * pi::nparams(hc) * sizeof(double), st)) return (int)e;
+    // (the direct sweep with fused sums reads the top frame's dL/dtraj where it lies, as rollout_bwd_impl does)
+    const T* top_in_place = (!tile && fuse) ? g_traj + (size_t)t_top * frame : nullptr;
+    if (!top_in_place)
+        if (hipError_t e = hipMemcpyAsync(adj + (size_t)t_top * frame, g_traj + (size_t)t_top * frame, frame_bytes,
+                                          hipMemcpyDeviceToDevice, st)) return (int)e;
+    int t_cur = t_top;
+    if (tile) {
+        const int K = (p.opt.tile_k == 8 && p.hc != 0) ? 4 : p.opt.tile_k;
+        for (; t_cur - K >= 0; t_cur -= K) {
+            unsigned m = 0;
+            for (int q = 0; q < K; ++q) if (has(t_cur - 1 - q)) m |= 1u << q;
+            if (hipError_t e = adj_tile_b<T>(traj + (size_t)t_cur * frame, g_traj + (size_t)t_cur * frame, adj + (size_t)t_cur * frame,
+                                             m, g_h0, t_cur == K ? K : 0, partials, P, p, batch, st, rows))
+                return (int)e;
+        }
+    }
+    for (int t = t_cur; t >= 1; --t) {
+        T* dst = (t == 1) ? g_h0 : adj + (size_t)(t - 1) * frame;
+        const T* inj = has(t - 1) ? g_traj + (size_t)(t - 1) * frame : nullptr;
+        const T* gin = (top_in_place && t == t_top) ? top_in_place : adj + (size_t)t * frame;
+        hipError_t e = fuse ? step_bwd_b<T, true>(traj + (size_t)(t - 1) * frame, gin, inj, dst, partials, P, p, batch, st, nullptr, rows)
+                            : step_bwd_b<T, false>(traj + (size_t)(t - 1) * frame, gin, inj, dst, partials, P, p, batch, st, nullptr, rows);
+        if (e) return (int)e;
+    }
+    if (pass) {
+        const bool vec_ok = (p.n % pi::vec_width<T>::value == 0) && p.opt.vec != 1 && (reinterpret_cast<uintptr_t>(traj) % 16 == 0);
+        hipError_t e = vec_ok ? launch_wgrad_ens<T, pi::vec_width<T>::value>(traj, adj, partials, P, p, batch, t_top, rows, st)
+                              : launch_wgrad_ens<T, 1>(traj, adj, partials, P, p, batch, t_top, rows, st);
+        if (e) return (int)e;
+    }
+    return (int)ens_finish_grads(partials, rows, batch, hc, param_grad, st);
 }
 
 
@@ -3949,6 +4183,41 @@ size_t percnn_pi_batch_rollout_bwd_workspace_bytes(int hc, int ndim, const int64
 
 PI_EXPORT_BATCH(f32, float)
 PI_EXPORT_BATCH(f64, double)
+
+// ensembles (include/percnn_pi.h "Ensembles"): the batched workspace layout, partial rows per sample
+size_t percnn_pi_ensemble_bwd_workspace_bytes(int hc, int ndim, const int64_t* shape, int batch, int elem_size)
+{
+    if (hc == -1) return 0;
+    return percnn_pi_batch_bwd_workspace_bytes(hc, ndim, shape, batch, elem_size);
+}
+
+size_t percnn_pi_ensemble_rollout_bwd_workspace_bytes(int hc, int ndim, const int64_t* shape, int batch, int T_steps, int elem_size)
+{
+    if (hc == -1) return 0;
+    return percnn_pi_batch_rollout_bwd_workspace_bytes(hc, ndim, shape, batch, T_steps, elem_size);
+}
+
+#define PI_EXPORT_ENSEMBLE(SUF, T)                                                                                     \
+    int percnn_pi_ensemble_step_fwd_##SUF(const T* h, T* out, const T* params, int hc, int ndim, const int64_t* shape, \
+                                          int batch, const char* options, void* stream)                                \
+    { return ens_step_fwd_impl<T>(h, out, params, hc, ndim, shape, batch, options, stream); }                          \
+    int percnn_pi_ensemble_step_bwd_##SUF(const T* h, const T* g_out, const T* g_inject, T* g_in, double* param_grad, \
+                                          void* workspace, size_t workspace_bytes, const T* params, int hc, int ndim, \
+                                          const int64_t* shape, int batch, const char* options, void* stream)          \
+    { return ens_step_bwd_impl<T>(h, g_out, g_inject, g_in, param_grad, workspace, workspace_bytes, params, hc, ndim,  \
+                                  shape, batch, options, stream); }                                                    \
+    int percnn_pi_ensemble_rollout_fwd_##SUF(T* traj, const T* params, int hc, int ndim, const int64_t* shape,         \
+                                             int batch, int T_steps, const char* options, void* stream)                \
+    { return ens_rollout_fwd_impl<T>(traj, params, hc, ndim, shape, batch, T_steps, options, stream); }                \
+    int percnn_pi_ensemble_rollout_bwd_##SUF(const T* traj, const T* g_traj, const unsigned char* frame_mask, T* g_h0, \
+                                             double* param_grad, void* workspace, size_t workspace_bytes,             \
+                                             const T* params, int hc, int ndim, const int64_t* shape, int batch,      \
+                                             int T_steps, const char* options, void* stream)                           \
+    { return ens_rollout_bwd_impl<T>(traj, g_traj, frame_mask, g_h0, param_grad, workspace, workspace_bytes, params,   \
+                                     hc, ndim, shape, batch, T_steps, options, stream); }
+
+PI_EXPORT_ENSEMBLE(f32, float)
+PI_EXPORT_ENSEMBLE(f64, double)
 
 // squared-error losses differentiated inside the sweep (include/percnn_pi.h)
 #define PI_EXPORT_LOSS(SUF, T)                                                                                      \

@@ -357,6 +357,137 @@ std::tuple<Tensor, Tensor> pi_rollout_batched_backward_impl(const Tensor& traj, 
     return {g_h0, pg.to(P.scalar_type())};
 }
 
+// ---- ensemble operators: B independent samples [B,2,*S], one parameter block per sample [B,np] (percnn_pi_ensemble_*) -------
+// hidden width of a stack of blocks [B,np] (all of one kind), checked against the batch size of the state
+inline int hc_of_ensemble(const Tensor& P, int64_t B)
+{
+    TORCH_CHECK(P.dim() == 2 && P.size(0) == B, "percnn_amd: ensemble parameter blocks must be [B,np] with B = ", B,
+                " (the state's batch size), got ", P.sizes());
+    const int hc = hc_of(P.select(0, 0));
+    TORCH_CHECK(hc != -1, "percnn_amd: the advective block has no ensemble path");
+    return hc;
+}
+
+Tensor pi_step_ensemble_impl(const Tensor& h, const Tensor& params, std::string options)
+{
+    check_batched_state(h);
+    require(h, "h");
+    require_like(params, h, "params");
+    const int hc = hc_of_ensemble(params, h.size(0));
+    c10::hip::HIPGuard guard(h.device().index());
+    const Tensor x = h.contiguous(), P = params.contiguous();
+    const Shape sh(x, 2);
+    Tensor out = at::empty_like(x);
+    void* st = stream_of(x);
+    const int B = (int)x.size(0);
+    int rc;
+    if (x.scalar_type() == at::kFloat)
+        rc = percnn_pi_ensemble_step_fwd_f32(x.const_data_ptr<float>(), out.mutable_data_ptr<float>(), P.const_data_ptr<float>(),
+                                             hc, sh.ndim, sh.s, B, opt_c(options), st);
+    else
+        rc = percnn_pi_ensemble_step_fwd_f64(x.const_data_ptr<double>(), out.mutable_data_ptr<double>(),
+                                             P.const_data_ptr<double>(), hc, sh.ndim, sh.s, B, opt_c(options), st);
+    check(rc, "ensemble_step_fwd");
+    return out;
+}
+
+std::tuple<Tensor, Tensor> pi_step_ensemble_backward_impl(const Tensor& h, const Tensor& params, const Tensor& g_out,
+                                                          std::string options)
+{
+    check_batched_state(h);
+    require(h, "h");
+    require_like(params, h, "params");
+    require_like(g_out, h, "g_out");
+    TORCH_CHECK(g_out.sizes() == h.sizes(), "percnn_amd: g_out must have the state's shape ", h.sizes(), ", got ", g_out.sizes());
+    const int hc = hc_of_ensemble(params, h.size(0));
+    c10::hip::HIPGuard guard(h.device().index());
+    const Tensor x = h.contiguous(), g = g_out.contiguous(), P = params.contiguous();
+    const Shape sh(x, 2);
+    const int B = (int)x.size(0);
+    Tensor g_in = at::empty_like(x);
+    Tensor pg = at::zeros(P.sizes(), x.options().dtype(at::kDouble));
+    const size_t nbytes = percnn_pi_ensemble_bwd_workspace_bytes(hc, sh.ndim, sh.s, B, (int)x.element_size());
+    TORCH_CHECK(nbytes != 0, "percnn_amd: invalid ensemble problem (shape, batch size or block kind)");
+    Tensor ws = at::empty({(int64_t)nbytes}, x.options().dtype(at::kByte));
+    void* st = stream_of(x);
+    int rc;
+    if (x.scalar_type() == at::kFloat)
+        rc = percnn_pi_ensemble_step_bwd_f32(x.const_data_ptr<float>(), g.const_data_ptr<float>(), nullptr,
+                                             g_in.mutable_data_ptr<float>(), pg.mutable_data_ptr<double>(), ws.mutable_data_ptr(),
+                                             (size_t)ws.numel(), P.const_data_ptr<float>(), hc, sh.ndim, sh.s, B, opt_c(options), st);
+    else
+        rc = percnn_pi_ensemble_step_bwd_f64(x.const_data_ptr<double>(), g.const_data_ptr<double>(), nullptr,
+                                             g_in.mutable_data_ptr<double>(), pg.mutable_data_ptr<double>(), ws.mutable_data_ptr(),
+                                             (size_t)ws.numel(), P.const_data_ptr<double>(), hc, sh.ndim, sh.s, B, opt_c(options),
+                                             st);
+    check(rc, "ensemble_step_bwd");
+    return {g_in, pg.to(P.scalar_type())};
+}
+
+// -> trajectory [T+1, B, 2, *S] (frame 0 = h0)
+Tensor pi_rollout_ensemble_impl(const Tensor& h0, const Tensor& params, int64_t steps, std::string options)
+{
+    check_batched_state(h0);
+    require(h0, "h0");
+    require_like(params, h0, "params");
+    TORCH_CHECK(steps >= 0, "percnn_amd: steps must be >= 0");
+    const int hc = hc_of_ensemble(params, h0.size(0));
+    c10::hip::HIPGuard guard(h0.device().index());
+    const Tensor P = params.contiguous();
+    std::vector<int64_t> sizes{steps + 1};
+    for (int64_t s : h0.sizes()) sizes.push_back(s);
+    Tensor traj = at::empty(sizes, h0.options());
+    traj.select(0, 0).copy_(h0);
+    const Shape sh(traj, 3);
+    void* st = stream_of(traj);
+    const int B = (int)h0.size(0);
+    int rc;
+    if (traj.scalar_type() == at::kFloat)
+        rc = percnn_pi_ensemble_rollout_fwd_f32(traj.mutable_data_ptr<float>(), P.const_data_ptr<float>(), hc, sh.ndim, sh.s, B,
+                                                (int)steps, opt_c(options), st);
+    else
+        rc = percnn_pi_ensemble_rollout_fwd_f64(traj.mutable_data_ptr<double>(), P.const_data_ptr<double>(), hc, sh.ndim, sh.s, B,
+                                                (int)steps, opt_c(options), st);
+    check(rc, "ensemble_rollout_fwd");
+    return traj;
+}
+
+std::tuple<Tensor, Tensor> pi_rollout_ensemble_backward_impl(const Tensor& traj, const Tensor& params, const Tensor& g_traj,
+                                                             std::string options)
+{
+    require(traj, "traj");
+    require_like(params, traj, "params");
+    require_like(g_traj, traj, "g_traj");
+    TORCH_CHECK(traj.is_contiguous(), "percnn_amd: traj must be contiguous");
+    TORCH_CHECK((traj.dim() == 5 || traj.dim() == 6) && traj.size(2) == 2 && traj.size(0) >= 1 && traj.size(1) >= 1,
+                "percnn_amd: ensemble traj must be [T+1,B,2,*S]");
+    TORCH_CHECK(g_traj.sizes() == traj.sizes(), "percnn_amd: g_traj must have the trajectory's shape");
+    const int hc = hc_of_ensemble(params, traj.size(1));
+    c10::hip::HIPGuard guard(traj.device().index());
+    const Tensor P = params.contiguous(), g = g_traj.contiguous();
+    const Shape sh(traj, 3);
+    const int T = (int)traj.size(0) - 1, B = (int)traj.size(1);
+    Tensor g_h0 = at::empty(traj.sizes().slice(1), traj.options());
+    Tensor pg = at::zeros(P.sizes(), traj.options().dtype(at::kDouble));
+    const size_t nbytes = percnn_pi_ensemble_rollout_bwd_workspace_bytes(hc, sh.ndim, sh.s, B, T, (int)traj.element_size());
+    TORCH_CHECK(nbytes != 0, "percnn_amd: invalid ensemble problem (shape, batch size or block kind)");
+    Tensor ws = at::empty({(int64_t)nbytes}, traj.options().dtype(at::kByte));
+    void* st = stream_of(traj);
+    int rc;
+    if (traj.scalar_type() == at::kFloat)
+        rc = percnn_pi_ensemble_rollout_bwd_f32(traj.const_data_ptr<float>(), g.const_data_ptr<float>(), nullptr,
+                                                g_h0.mutable_data_ptr<float>(), pg.mutable_data_ptr<double>(),
+                                                ws.mutable_data_ptr(), (size_t)ws.numel(), P.const_data_ptr<float>(), hc, sh.ndim,
+                                                sh.s, B, T, opt_c(options), st);
+    else
+        rc = percnn_pi_ensemble_rollout_bwd_f64(traj.const_data_ptr<double>(), g.const_data_ptr<double>(), nullptr,
+                                                g_h0.mutable_data_ptr<double>(), pg.mutable_data_ptr<double>(),
+                                                ws.mutable_data_ptr(), (size_t)ws.numel(), P.const_data_ptr<double>(), hc, sh.ndim,
+                                                sh.s, B, T, opt_c(options), st);
+    check(rc, "ensemble_rollout_bwd");
+    return {g_h0, pg.to(P.scalar_type())};
+}
+
 // ---- autograd formulas of the registered operators ----------------------------------------------------------------------
 struct PiStepFn : public torch::autograd::Function<PiStepFn> {
     static Tensor forward(AutogradContext* ctx, const Tensor& h, const Tensor& params, std::string options)
@@ -453,6 +584,56 @@ struct PiRolloutBatchedFn : public torch::autograd::Function<PiRolloutBatchedFn>
 Tensor pi_rollout_batched_autograd(const Tensor& h0, const Tensor& params, int64_t steps, std::string options)
 {
     return PiRolloutBatchedFn::apply(h0, params, steps, options);
+}
+
+struct PiStepEnsembleFn : public torch::autograd::Function<PiStepEnsembleFn> {
+    static Tensor forward(AutogradContext* ctx, const Tensor& h, const Tensor& params, std::string options)
+    {
+        at::AutoDispatchBelowADInplaceOrView below;
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("percnn::pi_step_ensemble", "")
+                             .typed<Tensor(const Tensor&, const Tensor&, std::string)>();
+        Tensor out = op.call(h, params, options);
+        ctx->save_for_backward({h, params});
+        ctx->saved_data["options"] = options;
+        return out;
+    }
+    static variable_list backward(AutogradContext* ctx, variable_list grads)
+    {
+        const auto saved = ctx->get_saved_variables();
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("percnn::pi_step_ensemble_backward", "")
+                             .typed<std::tuple<Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, std::string)>();
+        auto [g_in, g_p] = op.call(saved[0], saved[1], grads[0], ctx->saved_data["options"].toStringRef());
+        return {g_in, g_p, Tensor()};
+    }
+};
+Tensor pi_step_ensemble_autograd(const Tensor& h, const Tensor& params, std::string options)
+{
+    return PiStepEnsembleFn::apply(h, params, options);
+}
+
+struct PiRolloutEnsembleFn : public torch::autograd::Function<PiRolloutEnsembleFn> {
+    static Tensor forward(AutogradContext* ctx, const Tensor& h0, const Tensor& params, int64_t steps, std::string options)
+    {
+        at::AutoDispatchBelowADInplaceOrView below;
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("percnn::pi_rollout_ensemble", "")
+                             .typed<Tensor(const Tensor&, const Tensor&, int64_t, std::string)>();
+        Tensor traj = op.call(h0, params, steps, options);
+        ctx->save_for_backward({traj, params});
+        ctx->saved_data["options"] = options;
+        return traj;
+    }
+    static variable_list backward(AutogradContext* ctx, variable_list grads)
+    {
+        const auto saved = ctx->get_saved_variables();
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("percnn::pi_rollout_ensemble_backward", "")
+                             .typed<std::tuple<Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, std::string)>();
+        auto [g_h0, g_p] = op.call(saved[0], saved[1], grads[0], ctx->saved_data["options"].toStringRef());
+        return {g_h0, g_p, Tensor(), Tensor()};
+    }
+};
+Tensor pi_rollout_ensemble_autograd(const Tensor& h0, const Tensor& params, int64_t steps, std::string options)
+{
+    return PiRolloutEnsembleFn::apply(h0, params, steps, options);
 }
 
 // ---- eager fast path of a reference-style step loop -----------------------------------------------------------------------
@@ -985,6 +1166,10 @@ TORCH_LIBRARY_FRAGMENT(percnn, m)
     m.def("pi_step_batched_backward(Tensor h, Tensor params, Tensor g_out, str options=\"\") -> (Tensor, Tensor)");
     m.def("pi_rollout_batched(Tensor h0, Tensor params, SymInt steps, str options=\"\") -> Tensor");
     m.def("pi_rollout_batched_backward(Tensor traj, Tensor params, Tensor g_traj, str options=\"\") -> (Tensor, Tensor)");
+    m.def("pi_step_ensemble(Tensor h, Tensor params, str options=\"\") -> Tensor");
+    m.def("pi_step_ensemble_backward(Tensor h, Tensor params, Tensor g_out, str options=\"\") -> (Tensor, Tensor)");
+    m.def("pi_rollout_ensemble(Tensor h0, Tensor params, SymInt steps, str options=\"\") -> Tensor");
+    m.def("pi_rollout_ensemble_backward(Tensor traj, Tensor params, Tensor g_traj, str options=\"\") -> (Tensor, Tensor)");
     m.class_<GradSink>("GradSink").def(torch::init<Tensor>());
     m.class_<BlockState>("BlockState").def(torch::init<Tensor>());
 }
@@ -999,6 +1184,10 @@ TORCH_LIBRARY_IMPL(percnn, CUDA, m)
     m.impl("pi_step_batched_backward", pi_step_batched_backward_impl);
     m.impl("pi_rollout_batched", pi_rollout_batched_impl);
     m.impl("pi_rollout_batched_backward", pi_rollout_batched_backward_impl);
+    m.impl("pi_step_ensemble", pi_step_ensemble_impl);
+    m.impl("pi_step_ensemble_backward", pi_step_ensemble_backward_impl);
+    m.impl("pi_rollout_ensemble", pi_rollout_ensemble_impl);
+    m.impl("pi_rollout_ensemble_backward", pi_rollout_ensemble_backward_impl);
 }
 
 // CPU tensors fail loudly (there is no CPU path), with the package's message instead of the dispatcher's
@@ -1012,6 +1201,10 @@ TORCH_LIBRARY_IMPL(percnn, CPU, m)
     m.impl("pi_step_batched_backward", pi_step_batched_backward_impl);
     m.impl("pi_rollout_batched", pi_rollout_batched_impl);
     m.impl("pi_rollout_batched_backward", pi_rollout_batched_backward_impl);
+    m.impl("pi_step_ensemble", pi_step_ensemble_impl);
+    m.impl("pi_step_ensemble_backward", pi_step_ensemble_backward_impl);
+    m.impl("pi_rollout_ensemble", pi_rollout_ensemble_impl);
+    m.impl("pi_rollout_ensemble_backward", pi_rollout_ensemble_backward_impl);
 }
 
 TORCH_LIBRARY_IMPL(percnn, Autograd, m)
@@ -1020,6 +1213,8 @@ TORCH_LIBRARY_IMPL(percnn, Autograd, m)
     m.impl("pi_rollout", pi_rollout_autograd);
     m.impl("pi_step_batched", pi_step_batched_autograd);
     m.impl("pi_rollout_batched", pi_rollout_batched_autograd);
+    m.impl("pi_step_ensemble", pi_step_ensemble_autograd);
+    m.impl("pi_rollout_ensemble", pi_rollout_ensemble_autograd);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)

@@ -959,6 +959,51 @@ def pi_rollout_batched_frames(h0: torch.Tensor, P: torch.Tensor, steps: int, fra
     return out if with_stacked else out[:-1]
 
 
+class PiRolloutEnsembleFramesFunction(torch.autograd.Function):
+    """``PiRolloutBatchedFramesFunction`` with one parameter block per sample, P [B,np]: one
+    ``torch.ops.percnn.pi_rollout_ensemble`` call; frames and the stacked last output as there.  The backward runs ONE ensemble
+    rollout backward on the dense dL/dtraj and returns the [B,np] parameter gradient."""
+
+    @staticmethod
+    def forward(ctx, h0, P, steps, frames):
+        _native()
+        P = P.contiguous()
+        traj = torch.ops.percnn.pi_rollout_ensemble(h0, P, steps, "")
+        ctx.save_for_backward(traj, P)
+        ctx.frames = tuple(int(k) for k in frames)
+        ctx.set_materialize_grads(False)
+        views = traj.unbind(0)
+        outs = []
+        for k in ctx.frames:
+            f = views[k].as_subclass(Frame)
+            f._pi_index = k
+            outs.append(f)
+        return tuple(outs) + (traj.view((-1,) + tuple(traj.shape[2:])),)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        traj, P = ctx.saved_tensors
+        g_stacked, grads = grads[-1], grads[:-1]
+        if g_stacked is None and all(g is None for g in grads):
+            return None, None, None, None
+        if g_stacked is not None:
+            g_traj = g_stacked.reshape(traj.shape)
+            if any(g is not None for g in grads):
+                g_traj = g_traj.clone()
+        else:
+            g_traj = torch.zeros_like(traj)
+        for k, g in zip(ctx.frames, grads):
+            if g is not None:
+                g_traj[k].add_(g)
+        g_h0, pg = torch.ops.percnn.pi_rollout_ensemble_backward(traj, P, g_traj.contiguous(), "")
+        return g_h0, pg, None, None
+
+
+def pi_rollout_ensemble_frames(h0: torch.Tensor, P: torch.Tensor, steps: int, frames: Sequence[int], with_stacked: bool = False):
+    out = PiRolloutEnsembleFramesFunction.apply(h0, P, int(steps), tuple(frames))
+    return out if with_stacked else out[:-1]
+
+
 def _progression(t_idx: Sequence[int]):
     """(start, step, n) if t_idx is an increasing arithmetic progression (what a slice of range(T+1) gives), else None"""
     n = len(t_idx)
@@ -1085,3 +1130,17 @@ def pi_rollout_batched(h0: torch.Tensor, P: torch.Tensor, steps: int, options=No
     the parameter gradient is the sum over the samples."""
     _native()
     return torch.ops.percnn.pi_rollout_batched(h0, P, int(steps), _options_str(options))
+
+
+def pi_step_ensemble(h: torch.Tensor, P: torch.Tensor, options=None) -> torch.Tensor:
+    """One fused step of B independent states [B,2,*S], sample b with its own parameter block P[b] (P [B,np], blocks of one
+    kind): ``torch.ops.percnn.pi_step_ensemble``; sample b bit-identical to ``pi_step(h[b:b+1], P[b])``."""
+    _native()
+    return torch.ops.percnn.pi_step_ensemble(h, P, _options_str(options))
+
+
+def pi_rollout_ensemble(h0: torch.Tensor, P: torch.Tensor, steps: int, options=None) -> torch.Tensor:
+    """T fused steps of B independent trajectories, sample b with its own block P[b]: h0 [B,2,*S], P [B,np] -> [T+1,B,2,*S]
+    through ``torch.ops.percnn.pi_rollout_ensemble``.  The parameter gradient is [B,np], one row per sample."""
+    _native()
+    return torch.ops.percnn.pi_rollout_ensemble(h0, P, int(steps), _options_str(options))

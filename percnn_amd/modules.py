@@ -762,6 +762,65 @@ class FrameList(list):
     stacked: Optional[torch.Tensor] = None
 
 
+class CellEnsemble(nn.Module):
+    """B Pi-block cells advanced side by side: sample b of a state [B,2,*S] runs with member b's parameter block (a parameter
+    study -- a Gray-Scott (f, k) map, a seed ensemble of trained cells, B checkpoints on the same initial conditions -- in the
+    launches of one sample; ``torch.ops.percnn.pi_*_ensemble``).  Members are ``RCNNCell`` or ``Stage3LambdaOmegaCell`` of one
+    type, ``ndim``, ``hidden_channels``, dtype and device.  ``state_dict`` keys are ``cells.<i>.<the member's keys>``, so
+    member i loads a reference checkpoint by prefix.  ``RCNN(ensemble, step, effective_step, init_state=[B,2,*S])`` runs B
+    trajectories with B == len(cells); each member's parameters receive the gradient of its own sample."""
+
+    def __init__(self, cells):
+        super().__init__()
+        cells = list(cells)
+        if not cells:
+            raise ValueError("CellEnsemble needs at least one cell")
+        for c in cells:
+            if type(c) not in (RCNNCell, Stage3LambdaOmegaCell):
+                raise ValueError(f"CellEnsemble: {type(c).__name__} is not a Pi-block cell (RCNNCell, Stage3LambdaOmegaCell); "
+                                 f"Stage-1 and Burgers cells have no ensemble path")
+        sigs = {self._signature(c) for c in cells}
+        if len(sigs) != 1:
+            raise ValueError(f"CellEnsemble: members must share type, ndim, hidden_channels, dtype and device; got {sorted(map(str, sigs))}")
+        self.cells = nn.ModuleList(cells)
+        self.ndim = cells[0].ndim
+
+    @staticmethod
+    def _signature(c):
+        w = c.W_laplace.weight if isinstance(c, RCNNCell) else c.laplace_op.filter.weight
+        return type(c).__name__, c.ndim, getattr(c, "hidden_channels", None), w.dtype, w.device
+
+    def __len__(self) -> int:
+        return len(self.cells)
+
+    @staticmethod
+    def _member_block(c, fresh: bool, factored: bool = False) -> torch.Tensor:
+        if not isinstance(c, RCNNCell):
+            return c.param_block()
+        if not factored:
+            return c.param_block(fresh=fresh)
+        keep, c.reaction = c.reaction, "factored"
+        try:
+            return c.param_block(fresh=True)
+        finally:
+            c.reaction = keep
+
+    def param_block(self, fresh: bool = False) -> torch.Tensor:
+        """[B, np]: the members' blocks stacked (differentiable back to each member).  Blocks of one kind: when the poly guard
+        has switched some members to the factored form, every member is packed factored -- the reference's own operation
+        order, never wrong."""
+        blocks = [self._member_block(c, fresh) for c in self.cells]
+        if len({b.numel() for b in blocks}) > 1:
+            blocks = [b if b.numel() != F_pi.NPOLY else self._member_block(c, fresh, factored=True)
+                      for c, b in zip(self.cells, blocks)]
+        return torch.stack(blocks)
+
+    def forward(self, h):
+        """one step of h [B,2,*S], sample b with member b's block"""
+        ch = F_pi.pi_step_ensemble(h, self.param_block())
+        return ch, ch
+
+
 class RCNN(nn.Module):
     """Rollout: ``forward() -> (outputs, second_last_state)`` (train_2drd.py:162-190).
 
@@ -801,7 +860,7 @@ class RCNN(nn.Module):
         """The cell's parameter block for ONE rollout: packed afresh where the cell caches (``RCNNCell.param_block(fresh=True)``
         -- a pack launch per rollout costs nothing and a rollout then never runs on a block made stale by a ``.data`` edit)."""
         cell = self.cell
-        if isinstance(cell, RCNNCell):
+        if isinstance(cell, (RCNNCell, CellEnsemble)):
             return cell.param_block(fresh=True)
         return cell.param_block()
 
@@ -809,6 +868,16 @@ class RCNN(nn.Module):
         """a batched initial state [B,2,*S], B > 1 (B independent trajectories, one parameter block)"""
         h = self.init_state
         return h is not None and h.dim() in (4, 5) and h.shape[0] > 1
+
+    def _ensemble(self, what: str) -> bool:
+        """a CellEnsemble: B trajectories, B == len(cells), sample b with member b's block"""
+        if not isinstance(self.cell, CellEnsemble):
+            return False
+        h = self.init_state
+        if h is None or h.dim() not in (4, 5) or h.shape[0] != len(self.cell):
+            raise ValueError(f"{what}: a CellEnsemble of {len(self.cell)} cells needs an initial state [{len(self.cell)},2,*S], "
+                             f"got {None if h is None else tuple(h.shape)}")
+        return True
 
     def _check_batchable(self, what: str) -> None:
         if hasattr(self.cell, "rollout") or isinstance(self.cell, Stage3BurgersCell):
@@ -820,6 +889,8 @@ class RCNN(nn.Module):
         [B,2,*S]: [step+1, B, 2, *S]."""
         if hasattr(self, "UpconvBlock"):
             self.init_state = self.UpconvBlock(self.init_state_low)
+        if self._ensemble("RCNN.trajectory()"):
+            return F_pi.pi_rollout_ensemble(self.init_state, self._block(), self.step)
         if self._batched():
             self._check_batchable("RCNN.trajectory()")
             return F_pi.pi_rollout_batched(self.init_state, self._block(), self.step)
@@ -836,8 +907,9 @@ class RCNN(nn.Module):
             raise ValueError("observe() indexes the dense output list: effective_step must be list(range(step))")
         if hasattr(self, "UpconvBlock"):
             self.init_state = self.UpconvBlock(self.init_state_low)
-        if self._batched():
-            raise ValueError("observe() takes one trajectory: batched initial states (B > 1) go through forward() / trajectory()")
+        if self._batched() or isinstance(self.cell, CellEnsemble):
+            raise ValueError("observe() takes one trajectory: batched initial states (B > 1) and ensembles go through forward() / "
+                             "trajectory()")
         t_idx = list(range(self.step + 1))[t_slice]
         ndim = self.init_state.dim() - 2
         if hasattr(self.cell, "rollout_observe"):           # cells with their own kernels (Stage-1 block)
@@ -860,7 +932,8 @@ class RCNN(nn.Module):
           its result.
 
         The full (detached) trajectory is kept in ``self.last_trajectory``."""
-        if self._batched() or (hasattr(self, "UpconvBlock") and self.init_state_low is not None and self.init_state_low.shape[0] > 1):
+        if self._batched() or isinstance(self.cell, CellEnsemble) or (
+                hasattr(self, "UpconvBlock") and self.init_state_low is not None and self.init_state_low.shape[0] > 1):
             raise ValueError("loss_mse() takes one trajectory: batched initial states (B > 1) go through forward() / trajectory()")
         if space_stride != 1:
             pred = self.observe(t_slice, space_stride)
@@ -902,7 +975,9 @@ class RCNN(nn.Module):
         if self.step >= 2:
             frames.append(self.step - 1)                    # second_last_state rides along as one more output
         stacked = None
-        if self._batched():                                 # B trajectories: frames [B,2,*S], stacked [(step+1)*B,2,*S]
+        if self._ensemble("RCNN.forward()"):               # B trajectories, B blocks: frames and stacked as batched
+            outs = F_pi.pi_rollout_ensemble_frames(self.init_state, self._block(), self.step, frames, with_stacked=True)
+        elif self._batched():                               # B trajectories: frames [B,2,*S], stacked [(step+1)*B,2,*S]
             self._check_batchable("RCNN.forward()")
             outs = F_pi.pi_rollout_batched_frames(self.init_state, self._block(), self.step, frames, with_stacked=True)
         elif hasattr(self.cell, "rollout_frames"):          # cells with their own kernels (Stage-1 block)

@@ -16,6 +16,8 @@ so the operators pass ``torch.library.opcheck`` and trace under ``torch.compile(
     percnn::pi_rollout_backward(Tensor traj, Tensor params, Tensor g_traj, str options="") -> (Tensor, Tensor)
     percnn::pi_step_batched / pi_rollout_batched (+ *_backward): the same on B independent samples [B,2,*S] (trajectory
             [T+1,B,2,*S]), one parameter block
+    percnn::pi_step_ensemble / pi_rollout_ensemble (+ *_backward): the same with one parameter block per sample, params
+            [B,np]; the parameter gradient is [B,np], one row per sample
     percnn::pi_rollout_observe(Tensor h0, Tensor params, int steps, int[] t_idx, int[] strides, str options="")
             -> (Tensor pred, Tensor traj)
     percnn::pi_rollout_observe_backward(Tensor traj, Tensor params, Tensor g_pred, int[] t_idx, int[] strides,
@@ -175,6 +177,31 @@ def load_native() -> None:
 
     @torch.library.register_fake(f"{_lib_ns}::pi_rollout_batched_backward")
     def _(traj, params, g_traj, options=""):
+        return traj.new_empty(tuple(traj.shape[1:])), torch.empty_like(params)
+
+    # ensembles: h [B,2,*S], params [B,np], trajectory [T+1,B,2,*S], parameter gradient [B,np]
+    def _check_ensemble(params, B):
+        torch._check(params.dim() == 2 and params.shape[0] == B,
+                     lambda: f"percnn_amd: ensemble parameter blocks must be [B,np] with B = {B}, got {tuple(params.shape)}")
+
+    @torch.library.register_fake(f"{_lib_ns}::pi_step_ensemble")
+    def _(h, params, options=""):
+        _check_ensemble(params, h.shape[0])
+        return torch.empty_like(h, memory_format=torch.contiguous_format)
+
+    @torch.library.register_fake(f"{_lib_ns}::pi_step_ensemble_backward")
+    def _(h, params, g_out, options=""):
+        _check_ensemble(params, h.shape[0])
+        return torch.empty_like(h, memory_format=torch.contiguous_format), torch.empty_like(params)
+
+    @torch.library.register_fake(f"{_lib_ns}::pi_rollout_ensemble")
+    def _(h0, params, steps, options=""):
+        _check_ensemble(params, h0.shape[0])
+        return h0.new_empty((steps + 1,) + tuple(h0.shape))
+
+    @torch.library.register_fake(f"{_lib_ns}::pi_rollout_ensemble_backward")
+    def _(traj, params, g_traj, options=""):
+        _check_ensemble(params, traj.shape[1])
         return traj.new_empty(tuple(traj.shape[1:])), torch.empty_like(params)
 
     _native_loaded = True
