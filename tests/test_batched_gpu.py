@@ -2,13 +2,12 @@
 
 Every state field of sample b must be bit-identical to the unbatched entry point on that sample alone; the parameter
 gradient is the sum of the per-sample gradients to reduction round-off."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
-from util import TOL_GRAD, TOL_TRAJ, random_block, rel_l2
+from util import TOL_GRAD, TOL_TRAJ, bits_equal, random_block, rel_l2
+from util import batch_rollout_bwd as _bwd_batched, single_rollout_bwd as _bwd_single
 
 pytestmark = pytest.mark.gpu
 
@@ -34,14 +33,6 @@ def _setup(hc, dtype, shape, B, dev, seed=0):
     rs = np.random.RandomState(seed)
     h0 = torch.from_numpy((0.2 + 0.3 * rs.rand(B, 2, *shape)).astype(dtype)).to(dev)     # a distinct IC per sample
     return h0, P
-
-
-def bits_equal(a, b):
-    """bit-identical (NaN payloads included)"""
-    it = torch.int32 if a.dtype == torch.float32 else torch.int64
-    return a.shape == b.shape and torch.equal(a.contiguous().view(it), b.contiguous().view(it))
-
-
 
 
 @pytest.mark.parametrize("case", FWD_CASES, ids=_case_id)
@@ -76,40 +67,6 @@ def test_batched_forward_matches_oracle(hip_device):
     for b in range(3):
         ref = O.rollout_fwd(h0[b].cpu().numpy(), P.cpu().numpy(), 8, 6)
         assert rel_l2(traj[:, b], ref) < TOL_TRAJ[np.dtype(np.float32)]
-
-
-SUF = {np.float32: "f32", np.float64: "f64"}
-
-
-def _bwd_batched(traj, g, P, hc, shape, B, T, mask):
-    from percnn_amd import _lib
-    L = _lib.lib()
-    dt = traj.dtype
-    esz = traj.element_size()
-    ws = torch.empty(L.percnn_pi_batch_rollout_bwd_workspace_bytes(hc, len(shape), _lib.shape_arg(shape), B, T, esz),
-                     dtype=torch.uint8, device=traj.device)
-    g_h0 = torch.empty((B, 2) + shape, dtype=dt, device=traj.device)
-    pg = torch.zeros(P.numel(), dtype=torch.float64, device=traj.device)
-    f = getattr(L, "percnn_pi_batch_rollout_bwd_" + ("f32" if dt == torch.float32 else "f64"))
-    rc = f(traj.data_ptr(), g.data_ptr(), mask, g_h0.data_ptr(), pg.data_ptr(), ws.data_ptr(), ws.numel(), P.data_ptr(), hc,
-           len(shape), _lib.shape_arg(shape), B, T, None, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0
-    return g_h0, pg
-
-
-def _bwd_single(traj, g, P, hc, shape, T, mask):
-    from percnn_amd import _lib
-    L = _lib.lib()
-    dt = traj.dtype
-    ws = torch.empty(L.percnn_pi_rollout_bwd_workspace_bytes(hc, len(shape), _lib.shape_arg(shape), T, traj.element_size()),
-                     dtype=torch.uint8, device=traj.device)
-    g_h0 = torch.empty((2,) + shape, dtype=dt, device=traj.device)
-    pg = torch.zeros(P.numel(), dtype=torch.float64, device=traj.device)
-    f = getattr(L, "percnn_pi_rollout_bwd_opt_" + ("f32" if dt == torch.float32 else "f64"))
-    rc = f(traj.data_ptr(), g.data_ptr(), mask, g_h0.data_ptr(), pg.data_ptr(), ws.data_ptr(), ws.numel(), P.data_ptr(), hc,
-           len(shape), _lib.shape_arg(shape), T, None, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0
-    return g_h0, pg
 
 
 BWD_CASES = [c for c in FWD_CASES if c[5] > 0] + [("gs2d_poly", 0, np.float32, (128, 128), 3, 24)]

@@ -4,13 +4,12 @@ parameter block per sample [B,np].
 Every state and adjoint field of sample b must be bit-identical to the unbatched entry point on (h0[b], P[b]); gradient row
 b equals that call's parameter gradient to reduction round-off (rel-L2 1e-6 float32 / 1e-10 float64, the bounds of the
 batched tests for the same kind of comparison).  Every block below differs per sample: its own seed and its own dt."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
-from util import TOL_GRAD, TOL_TRAJ, random_block, rel_l2
+from util import TOL_GRAD, TOL_TRAJ, bits_equal, rel_l2
+from util import ensemble_blocks as _blocks, ensemble_rollout_bwd as _bwd_ensemble, ensemble_step_bwd, single_rollout_bwd as _bwd_single
 
 pytestmark = pytest.mark.gpu
 
@@ -27,21 +26,10 @@ FWD_CASES = [
     ("gs2d_poly", 0, np.float32, (100, 100), 4, 0),
     ("gs2d_fact", 8, np.float32, (100, 100), 3, 1),
 ]
-SUF = {torch.float32: "f32", torch.float64: "f64"}
 
 
 def _case_id(c):
     return f"{c[0]}-hc{c[1]}-{'x'.join(map(str, c[3]))}-B{c[4]}-T{c[5]}"
-
-
-def _blocks(hc, ndim, dtype, B, seed):
-    """B distinct blocks: a seed and a dt of their own"""
-    Ps = []
-    for b in range(B):
-        P = random_block(hc, ndim, dtype, seed + 17 * b + 1, scale=0.1)
-        P[0] = 0.1 * (1.0 + 0.125 * b)
-        Ps.append(P)
-    return np.stack(Ps)
 
 
 def _setup(hc, dtype, shape, B, dev, seed=0):
@@ -49,44 +37,6 @@ def _setup(hc, dtype, shape, B, dev, seed=0):
     rs = np.random.RandomState(seed)
     h0 = torch.from_numpy((0.2 + 0.3 * rs.rand(B, 2, *shape)).astype(dtype)).to(dev)
     return h0, P
-
-
-def bits_equal(a, b):
-    """bit-identical (NaN payloads included)"""
-    it = torch.int32 if a.dtype == torch.float32 else torch.int64
-    return a.shape == b.shape and torch.equal(a.contiguous().view(it), b.contiguous().view(it))
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _bwd_ensemble(traj, g, P, hc, shape, B, T, mask):
-    from percnn_amd import _lib
-    L = _lib.lib()
-    ws = torch.empty(L.percnn_pi_ensemble_rollout_bwd_workspace_bytes(hc, len(shape), _lib.shape_arg(shape), B, T,
-                                                                      traj.element_size()), dtype=torch.uint8, device=traj.device)
-    g_h0 = torch.empty((B, 2) + shape, dtype=traj.dtype, device=traj.device)
-    pg = torch.zeros(P.shape, dtype=torch.float64, device=traj.device)
-    f = getattr(L, "percnn_pi_ensemble_rollout_bwd_" + SUF[traj.dtype])
-    rc = f(traj.data_ptr(), g.data_ptr(), mask, g_h0.data_ptr(), pg.data_ptr(), ws.data_ptr(), ws.numel(), P.data_ptr(), hc,
-           len(shape), _lib.shape_arg(shape), B, T, None, _stream())
-    assert rc == 0
-    return g_h0, pg
-
-
-def _bwd_single(traj, g, P, hc, shape, T, mask):
-    from percnn_amd import _lib
-    L = _lib.lib()
-    ws = torch.empty(L.percnn_pi_rollout_bwd_workspace_bytes(hc, len(shape), _lib.shape_arg(shape), T, traj.element_size()),
-                     dtype=torch.uint8, device=traj.device)
-    g_h0 = torch.empty((2,) + shape, dtype=traj.dtype, device=traj.device)
-    pg = torch.zeros(P.numel(), dtype=torch.float64, device=traj.device)
-    f = getattr(L, "percnn_pi_rollout_bwd_opt_" + SUF[traj.dtype])
-    rc = f(traj.data_ptr(), g.data_ptr(), mask, g_h0.data_ptr(), pg.data_ptr(), ws.data_ptr(), ws.numel(), P.data_ptr(), hc,
-           len(shape), _lib.shape_arg(shape), T, None, _stream())
-    assert rc == 0
-    return g_h0, pg
 
 
 @pytest.mark.parametrize("case", FWD_CASES, ids=_case_id)
@@ -129,16 +79,8 @@ def test_ensemble_backward_per_sample(case, masked, hip_device):
         print(f"sample {b}: gradient row rel-L2 {err:.3g}")
         assert err < tol, f"gradient row {b}"
     # the step entry point: per-sample adjoint and gradient row
-    from percnn_amd import _lib
-    L = _lib.lib()
     x, gs = h0.contiguous(), g[1].contiguous()
-    ws = torch.empty(L.percnn_pi_ensemble_bwd_workspace_bytes(hc, len(shape), _lib.shape_arg(shape), B, x.element_size()),
-                     dtype=torch.uint8, device=hip_device)
-    gi = torch.empty_like(x)
-    ps = torch.zeros(P.shape, dtype=torch.float64, device=hip_device)
-    f = getattr(L, "percnn_pi_ensemble_step_bwd_" + SUF[x.dtype])
-    assert f(x.data_ptr(), gs.data_ptr(), None, gi.data_ptr(), ps.data_ptr(), ws.data_ptr(), ws.numel(), P.data_ptr(), hc,
-             len(shape), _lib.shape_arg(shape), B, None, _stream()) == 0
+    gi, ps = ensemble_step_bwd(x, gs, P, hc, shape, B)
     for b in range(B):
         g1, p1 = pa.step_bwd(x[b], gs[b], P[b].contiguous())
         assert bits_equal(gi[b], g1), f"step dL/dh of sample {b}"
