@@ -2714,8 +2714,8 @@ int rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* mask, 
 
 
 // ---- batched rollouts: B independent trajectories, one parameter block (include/percnn_pi.h "Batched") ------------------------
-// The batch is the y dimension of the launch-per-group kernels (pi_fwd2d_tile_batch_kernel, pi_adj2d_tile_batch_kernel,
-// pi_fwd_batch_kernel, pi_bwd_batch_kernel): every workgroup runs the unbatched kernel's body on one sample, so every state field
+// The batch is the y dimension of the launch-per-group kernels (the `long sample` flavours of pi_fwd2d_tile_kernel,
+// pi_adj2d_tile_kernel, pi_fwd_kernel, pi_bwd_kernel): every workgroup runs the kernel's one body on one sample, so every state field
 // of sample b is the unbatched result of that sample alone, bit for bit.  Partial rows: one per (sample, workgroup), reduced in
 // one fixed order.  The resident, brick and plane-streaming kernels have no batched flavour and are never dispatched here.
 constexpr int MAX_BATCH = 65535;                            // grid y
@@ -2728,8 +2728,9 @@ int batch_problem(int hc, int ndim, const int64_t* shape, int batch, Problem& p,
     return 0;
 }
 
-// Launchers below: ens_rows = -1 runs the batched kernels (one block P); ens_rows >= 0 the ensemble kernels of the same
-// shape (P [B][np], partial rows at sample * ens_rows; "ensembles" further down).
+// Launchers below: ens_rows = -1 runs the batched flavour (one block P); ens_rows >= 0 the ensemble flavour of the same
+// shape (P [B][np], partial rows at sample * ens_rows; "ensembles" further down).  They differ in the kernel's trailing
+// arguments alone, so each launcher states its launch once, in `go`.
 
 // tile vs direct: the per-sample rules of tile_eligible, with the size limits of the "tile = 1" rule applied to the points of
 // the whole batch (the tile kernels pay while the launches are latency-bound: 100^2 x 64 still is)
@@ -2748,17 +2749,15 @@ hipError_t launch_fwd_tile_b(T* frame_t, const T* P, const Problem& p, int batch
     const pi::TileGeom g = make_tile_geom(p, BY, BX);
     const unsigned grid = (unsigned)(((p.n0 + BY - 1) / BY) * g.tiles_x);
     const size_t lds = (size_t)4 * TL::PLANE * sizeof(T) + 32 /* lds_pad0/1 */ + (size_t)p.opt.lds_pad;
-    if (ens_rows >= 0) {
-        auto* k = pi::pi_fwd2d_tile_ens_kernel<T, HC, K, BX, BY, NT>;
+    auto go = [&](auto* k, auto... tail) {
         if (hipError_t e = allow_lds(k, lds)) return e;
         hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(NT), lds, st, frame_t, (long)batch * 2 * p.n, (long)(2 * p.n), P, g,
-                           pi::nparams(p.hc));
+                           tail...);
         return hipGetLastError();
-    }
-    auto* k = pi::pi_fwd2d_tile_batch_kernel<T, HC, K, BX, BY, NT>;
-    if (hipError_t e = allow_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(NT), lds, st, frame_t, (long)batch * 2 * p.n, (long)(2 * p.n), P, g);
-    return hipGetLastError();
+    };
+    // the target type picks the trailing pack (`int np`); `long` is the sample stride in the middle of the list
+    void (*ens)(T*, long, long, const T*, pi::TileGeom, int) = pi::pi_fwd2d_tile_kernel<T, HC, K, BX, BY, NT, long>;
+    return ens_rows >= 0 ? go(ens, pi::nparams(p.hc)) : go(pi::pi_fwd2d_tile_kernel<T, HC, K, BX, BY, NT, long>);
 }
 
 template <typename T, int HC, int K, int NT, int BY = TILE_B, bool MOM = false, int BX = TILE_B>
@@ -2777,18 +2776,16 @@ hipError_t launch_adj_tile_b(const T* hframe_t, const T* gframe_t, T* aframe_t, 
     if (MOM && sizeof(T) == 8)
         lds = pi::tile_state_bytes<T, K, BX, BY>() + (size_t)20 * NT * sizeof(double);
     lds += (size_t)p.opt.lds_pad;
-    if (ens_rows >= 0) {
-        auto* k = pi::pi_adj2d_tile_ens_kernel<T, HC, K, BX, BY, NT, MOM>;
+    auto go = [&](auto* k, auto... tail) {
         if (hipError_t e = allow_lds(k, lds)) return e;
         hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(NT), lds, st, hframe_t, gframe_t, aframe_t, (long)batch * 2 * p.n,
-                           (long)(2 * p.n), inj_mask, g_h0, steps_to_zero, partials, pi::nparams(p.hc), P, g, ens_rows);
+                           (long)(2 * p.n), inj_mask, g_h0, steps_to_zero, partials, pi::nparams(p.hc), P, g, tail...);
         return hipGetLastError();
-    }
-    auto* k = pi::pi_adj2d_tile_batch_kernel<T, HC, K, BX, BY, NT, MOM>;
-    if (hipError_t e = allow_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(NT), lds, st, hframe_t, gframe_t, aframe_t, (long)batch * 2 * p.n,
-                       (long)(2 * p.n), inj_mask, g_h0, steps_to_zero, partials, pi::nparams(p.hc), P, g);
-    return hipGetLastError();
+    };
+    // as launch_fwd_tile_b: the target type picks the trailing pack (`int rows`)
+    void (*ens)(const T*, const T*, T*, long, long, unsigned, T*, int, double*, int, const T*, pi::TileGeom, int) =
+        pi::pi_adj2d_tile_kernel<T, HC, K, BX, BY, NT, MOM, long>;
+    return ens_rows >= 0 ? go(ens, ens_rows) : go(pi::pi_adj2d_tile_kernel<T, HC, K, BX, BY, NT, MOM, long>);
 }
 
 // the tile variant fwd_tile / adj_tile pick for one sample, on all samples
@@ -2841,14 +2838,12 @@ hipError_t launch_fwd_b(const T* h, T* out, const T* P, const Problem& p, int ba
     if (!set_blockmap(g, NDIM, VEC, block, sizeof(T), p.opt.l2_tile_kb * 1024, 1, (long)p.opt.l2_tile_min_kb * 1024, p.opt.lane_x))
         return (hipError_t)PERCNN_PI_ETOOLARGE;
     g.xwin = 0;
-    if (ens_rows >= 0) {
-        hipLaunchKernelGGL((pi::pi_fwd_ens_kernel<T, NDIM, HC, VEC>), dim3(g.nblk, (unsigned)batch), dim3(block), 0, st, h, out, P,
-                           g, p.hc, (long)(2 * p.n), pi::nparams(p.hc));
+    auto go = [&](auto* k, auto... tail) {
+        hipLaunchKernelGGL(k, dim3(g.nblk, (unsigned)batch), dim3(block), 0, st, h, out, P, g, p.hc, (long)(2 * p.n), tail...);
         return hipGetLastError();
-    }
-    hipLaunchKernelGGL((pi::pi_fwd_batch_kernel<T, NDIM, HC, VEC>), dim3(g.nblk, (unsigned)batch), dim3(block), 0, st, h, out, P,
-                       g, p.hc, (long)(2 * p.n));
-    return hipGetLastError();
+    };
+    return ens_rows >= 0 ? go(pi::pi_fwd_kernel<T, NDIM, HC, VEC, 1, long, int>, pi::nparams(p.hc))
+                         : go(pi::pi_fwd_kernel<T, NDIM, HC, VEC, 1, long>);
 }
 
 template <typename T, int NDIM, int HC, int VEC, bool WGRAD>
@@ -2864,19 +2859,19 @@ hipError_t launch_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* par
     const size_t lds = align_up((size_t)(block / pi::WAVE) * pi::nparams(p.hc) * sizeof(T), 16) +
                        (size_t)(block / pi::WAVE) * 2 * sizeof(double) +
                        ((WGRAD && HC == pi::POLY) ? (size_t)20 * (block + 8) * sizeof(T) : 0);
+    auto go = [&](auto* k, auto... tail) {
+        if (hipError_t e = allow_lds(k, lds)) return e;
+        hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(block), lds, st, h, G, inj, Gp, partials, P, g, p.hc, (long)(2 * p.n),
+                           tail...);
+        return hipGetLastError();
+    };
     if (ens_rows >= 0) {
         if (grid > (unsigned)ens_rows) return (hipError_t)PERCNN_PI_ETOOLARGE;   // ens_rows bounds every launch (ens_rows_for)
-        auto* k = pi::pi_bwd_ens_kernel<T, NDIM, HC, VEC, WGRAD>;
-        if (hipError_t e = allow_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(block), lds, st, h, G, inj, Gp, partials, P, g, p.hc,
-                           (long)(2 * p.n), ens_rows);
-        return hipGetLastError();
+        return go(pi::pi_bwd_kernel<T, NDIM, HC, VEC, WGRAD, 1, long, int>, ens_rows);
     }
-    auto* k = pi::pi_bwd_batch_kernel<T, NDIM, HC, VEC, WGRAD>;
-    if (hipError_t e = allow_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(block), lds, st, h, G, inj, Gp, partials, P, g, p.hc, (long)(2 * p.n));
-    if (rows_out) *rows_out = grid * (unsigned)batch;
-    return hipGetLastError();
+    const hipError_t e = go(pi::pi_bwd_kernel<T, NDIM, HC, VEC, WGRAD, 1, long>);
+    if (e == hipSuccess && rows_out) *rows_out = grid * (unsigned)batch;
+    return e;
 }
 
 template <typename T>
@@ -3037,9 +3032,9 @@ int batch_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* 
 
 
 // ---- ensembles: B independent trajectories, one parameter block per sample (include/percnn_pi.h "Ensembles") ---------------
-// The launches of the batched path with the ensemble kernels (pi_*_ens_kernel): workgroup (x, b) reads block P + b * np.  Every
+// The launches of the batched path with the kernels' ensemble flavour: workgroup (x, b) reads block P + b * np.  Every
 // partial gradient row of sample b lies in [b * rows, (b + 1) * rows) -- `rows` is one bound for every launch of a call
-// (ens_rows_for) -- and pi_reduce_partials_ens_kernel sums the rows of each sample alone, in a fixed order, into param_grad[b].
+// (ens_rows_for) -- and pi_reduce_partials_kernel<true> sums the rows of each sample alone, in a fixed order, into param_grad[b].
 int ens_problem(int hc, int ndim, const int64_t* shape, int batch, Problem& p, const char* options, bool launches = true)
 {
     if (hc == -1) return PERCNN_PI_EINVAL;                  // the advective block has no ensemble flavour
@@ -3075,7 +3070,7 @@ int ens_rows_for(const Problem& p, int batch, bool tile, int t_top)
 hipError_t ens_finish_grads(const double* partials, int rows, int batch, int hc, double* param_grad, hipStream_t st)
 {
     const int np = pi::nparams(hc);
-    hipLaunchKernelGGL(pi::pi_reduce_partials_ens_kernel, dim3(np, (unsigned)batch), dim3(pi::WAVE), 0, st, partials, rows, np,
+    hipLaunchKernelGGL(pi::pi_reduce_partials_kernel<true>, dim3(np, (unsigned)batch), dim3(pi::WAVE), 0, st, partials, rows, np,
                        param_grad);
     return hipGetLastError();
 }
@@ -3087,7 +3082,7 @@ hipError_t launch_wgrad_ens_pass(const T* traj, const T* adj, double* partials, 
 {
     const int block = 256;
     const size_t lds = (size_t)(block / pi::WAVE) * NS * (10 * JC + 1) * sizeof(T);
-    hipLaunchKernelGGL((pi::pi_wgrad_ens_kernel<T, JC, NS, VEC>), dim3(nb, NS == 2 ? 1 : 2, (unsigned)batch), dim3(block), lds, st,
+    hipLaunchKernelGGL((pi::pi_wgrad_kernel<T, JC, NS, VEC, long, int>), dim3(nb, NS == 2 ? 1 : 2, (unsigned)batch), dim3(block), lds, st,
                        traj, adj, partials, P, (long)p.n, (long)p.n, 0L, 0, t_top, p.hc, j0, (long)batch * 2 * p.n, rows);
     return hipGetLastError();
 }
@@ -3100,7 +3095,7 @@ hipError_t launch_wgrad_ens(const T* traj, const T* adj, double* partials, const
     const unsigned nb = (unsigned)ens_wgrad_blocks(p, batch, t_top, VEC);
     if (p.hc == 0) {                                           // pre-contracted mode: coefficient moments
         const size_t lds = (size_t)(256 / pi::WAVE) * 20 * sizeof(T);
-        hipLaunchKernelGGL((pi::pi_moments_ens_kernel<T, VEC>), dim3(nb, (unsigned)batch), dim3(256), lds, st, traj, adj, partials,
+        hipLaunchKernelGGL((pi::pi_moments_kernel<T, VEC, long, int>), dim3(nb, (unsigned)batch), dim3(256), lds, st, traj, adj, partials,
                            P, (long)p.n, (long)p.n, 0L, 0, t_top, (long)batch * 2 * p.n, rows);
         return hipGetLastError();
     }

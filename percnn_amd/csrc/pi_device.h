@@ -17,6 +17,19 @@ __host__ __device__ constexpr int nparams(int hc) { return hc == 0 ? NPOLY : (hc
 constexpr int WAVE = 64;          // CDNA wavefront
 constexpr int NXCD = 8;           // MI355X: 8 XCDs, block b is dispatched to XCD b % 8
 
+// Flavours of a step kernel (one state / B states, one block: "batched" / B states, B blocks: "ensemble") are ONE __global__
+// template whose argument list carries parameter packs: empty for one state, `long sample` (+ one int) for the others, read
+// with flavour_arg<I>(pack...) under `if constexpr`.  A kernel template and not a __device__ body behind three thin kernels:
+// through a call the __restrict__ kernel arguments lose their meaning, and every kernel came out with another register
+// allocation (instruction counts off by up to 9 %, SGPR spills 2 -> 25 in the RZ = 2 forward); with the packs each flavour's
+// code is, instruction for instruction, what a hand-written kernel with that argument list gives (tools/compare_kernels.py).
+template <int I, typename A, typename... R>
+__device__ __forceinline__ auto flavour_arg(A a, R... r)
+{
+    if constexpr (I == 0) return a;
+    else return flavour_arg<I - 1>(r...);
+}
+
 // 16-byte vector access: 4 x f32 or 2 x f64 per lane -> 1 KiB per wave-instruction
 template <typename T> struct vec_width;
 template <> struct vec_width<float>  { static constexpr int value = 4; };

@@ -375,10 +375,18 @@ struct PlaneWindow {
 // ---------------------------------------------------------------------------------------------
 // forward: out = h + dt * (coef * Lap(h) + Wh4(Wh1(h) * Wh2(h) * Wh3(h)))
 // ---------------------------------------------------------------------------------------------
-template <typename T, int NDIM, int HC, int VEC, int RZ = 1>
+// X... = the flavour (see flavour_arg): none; `long sample` (states [B][2][*S], one block); `long sample, int np` (+ blocks P
+// [B][np]: P moves once by a wave-uniform offset, so the block still arrives through scalar loads).  Grid (workgroups of one
+// sample, B).
+template <typename T, int NDIM, int HC, int VEC, int RZ = 1, typename... X>
 __global__ void __launch_bounds__(256)
-pi_fwd_kernel(const T* __restrict__ h, T* __restrict__ out, const T* __restrict__ P, Geom g, int hc_rt)
+pi_fwd_kernel(const T* __restrict__ h, T* __restrict__ out, const T* __restrict__ P, Geom g, int hc_rt, X... x)
 {
+    if constexpr (sizeof...(X) >= 1) {             // sample blockIdx.y: 64-bit base once, in-sample offsets as unbatched
+        h += (long)blockIdx.y * flavour_arg<0>(x...);
+        out += (long)blockIdx.y * flavour_arg<0>(x...);
+    }
+    if constexpr (sizeof...(X) == 2) P += (long)blockIdx.y * flavour_arg<1>(x...);   // block of sample blockIdx.y
     static_assert(NDIM == 3 || RZ == 1, "plane blocking is a 3D notion");
     const int hc = HC > 0 ? HC : hc_rt;      // unused when HC == POLY
     // one virtual block (plane group, row group, x block) per workgroup, or -- option fwd_blocks -- a bounded grid of
@@ -480,16 +488,26 @@ pi_fwd_kernel(const T* __restrict__ h, T* __restrict__ out, const T* __restrict_
 // Gradient of the diffusion coefficient uses sum_x g*Lap(h) == sum_x LapT(g)*h, so the forward
 // Laplacian is never recomputed.
 // ---------------------------------------------------------------------------------------------
-template <typename T, int NDIM, int HC, int VEC, bool WGRAD, int RZ = 1>
+// X... = the flavour, as pi_fwd_kernel: none; `long sample` (partial row blockIdx.y * gridDim.x + blockIdx.x: the fixed-order row
+// reduction sums the samples in order); `long sample, int rows` (block of sample blockIdx.y, partial row blockIdx.y * rows +
+// blockIdx.x -- `rows` per sample, one stride for every launch of a call, so that the finishing reduction sums each
+// sample's rows alone).
+template <typename T, int NDIM, int HC, int VEC, bool WGRAD, int RZ = 1, typename... X>
 __global__ void __launch_bounds__(256)
 pi_bwd_kernel(const T* __restrict__ h, const T* __restrict__ G, const T* __restrict__ inj, T* __restrict__ Gp,
-              double* __restrict__ partials, const T* __restrict__ P, Geom g, int hc_rt)
+              double* __restrict__ partials, const T* __restrict__ P, Geom g, int hc_rt, X... x)
 {
+    if constexpr (sizeof...(X) >= 1) {
+        const long sbase = (long)blockIdx.y * flavour_arg<0>(x...);  // sample blockIdx.y; partial row per (sample, workgroup)
+        h += sbase; G += sbase; Gp += sbase;
+        if (inj) inj += sbase;
+    }
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T* red = reinterpret_cast<T*>(smem_raw);           // [nwaves][np] running sums of this block
 
     const int hc = HC == POLY ? 0 : (HC > 0 ? HC : hc_rt);
     const int np = nparams(hc);
+    if constexpr (sizeof...(X) == 2) P += (long)blockIdx.y * np;       // block of sample blockIdx.y
     const int nwaves = blockDim.x / WAVE;
     const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
     T* myred = red + wave * np;
@@ -502,763 +520,10 @@ pi_bwd_kernel(const T* __restrict__ h, const T* __restrict__ G, const T* __restr
         if (idx >= np || idx == P_DT || (idx >= P_C0 && idx < P_W)) return false;   // dt, frozen stencil: no gradient
         return WGRAD || idx < P_W;                                                  // sweep-only flavour: coefficients only
     };
-    double* const prow = partials + (long)blockIdx.x * np;
-    const double pold = carries_grad((int)threadIdx.x) ? prow[threadIdx.x] : 0.0;
-    __syncthreads();
-
-    const T dt = P[P_DT];
-
-    double lane_c[2] = {0.0, 0.0};
-    // poly mode with fused gradients: the 20 coefficient moments stay in registers over all chunks of the lane and are
-    // reduced across lanes once per launch (was: 22 wave reductions per chunk)
-    constexpr bool LANE_MOM = WGRAD && HC == POLY;
-    T macc[LANE_MOM ? 2 : 1][LANE_MOM ? 10 : 1];
-    if constexpr (LANE_MOM) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int m = 0; m < 10; ++m) macc[s][m] = T(0);
-    }
-
-    // virtual blocks (plane, row group, x block) of this workgroup: block-uniform trip count (wave-level reductions
-    // inside need whole waves, which a uniform loop guarantees); addressing as in the forward kernel
-    for (unsigned vb = xcd_remap(blockIdx.x, gridDim.x); vb < g.nblk; vb += gridDim.x) {
-        const Lane L = locate<T, NDIM, VEC>(g, vb);
-        const bool valid = L.valid;
-        // 3D: the adjoint state of planes i0-2 .. i0+RZ+1 in registers, shared by the RZ output planes of this pass
-        PlaneWindow<T, VEC, NDIM == 3 ? RZ : 1> win[2];
-        if constexpr (NDIM == 3) {
-            win[0].load(G + g.off, g, L);
-            win[1].load(G + g.ss + g.off, g, L);
-        }
-#pragma unroll
-        for (int jz = 0; jz < RZ; ++jz) {
-        const int iz = L.i0 + jz;
-        if (NDIM == 3 && iz >= g.n0) break;              // partial last plane group (block-uniform)
-        const char* phu = plane_base<T, NDIM>(h + g.off, g, iz);
-        const char* phv = plane_base<T, NDIM>(h + g.ss + g.off, g, iz);
-        const char* pgu = plane_base<T, NDIM>(G + g.off, g, iz);
-        const char* pgv = plane_base<T, NDIM>(G + g.ss + g.off, g, iz);
-        const Pack<T, VEC> u = ldb<T, VEC>(phu, L.eb), v = ldb<T, VEC>(phv, L.eb);
-        Pack<T, VEC> gc[2];
-        T dl[2][VEC];
-        if constexpr (NDIM == 3) {
-            gc[0] = win[0].w[jz + 2];
-            gc[1] = win[1].w[jz + 2];
-            win[0].template planes<-1>(jz, P, dl[0]);
-            win[1].template planes<-1>(jz, P, dl[1]);
-        } else {
-            gc[0] = ldb<T, VEC>(pgu, L.eb);
-            gc[1] = ldb<T, VEC>(pgv, L.eb);
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) { dl[0][i] = P[P_C0] * gc[0].v[i]; dl[1][i] = P[P_C0] * gc[1].v[i]; }
-        }
-        star2_inplane<T, NDIM, VEC, -1>(pgu, P, g, L, gc[0], dl[0]);
-        star2_inplane<T, NDIM, VEC, -1>(pgv, P, g, L, gc[1], dl[1]);
-        const T live = valid ? T(1) : T(0);
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                dl[s][i] = (dl[s][i] * dt) * live;
-                gc[s].v[i] *= live;
-            }
-
-        T du[VEC], dv[VEC];
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) du[i] = dv[i] = T(0);
-
-        if constexpr (HC == POLY) {
-            // monomials shared by both species (only needed for the moment sums)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const T* c = P + P_W + 10 * s;
-                const int gbase = P_W + 10 * s;
-                const Pack<T, VEC>& hs = s == 0 ? u : v;
-                (void)gbase;
-                double acc_c = 0.0;                      // heavily cancelling sum (stencil row-sum ~ 0): keep it in fp64
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) {
-                    const T gr = gc[s].v[i] * dt;
-                    acc_c += (double)(dl[s][i] * hs.v[i]);
-                    T ru, rv;
-                    poly_dr(c, u.v[i], v.v[i], ru, rv);
-                    du[i] = fma_(gr, ru, du[i]);
-                    dv[i] = fma_(gr, rv, dv[i]);
-                    if constexpr (WGRAD) {
-                        T (&acc)[10] = macc[s];
-                        const T uu = u.v[i], vv = v.v[i];
-                        const T u2 = uu * uu, uv = uu * vv, v2 = vv * vv;
-                        acc[0] += gr;
-                        acc[1] = fma_(gr, uu, acc[1]); acc[2] = fma_(gr, vv, acc[2]);
-                        acc[3] = fma_(gr, u2, acc[3]); acc[4] = fma_(gr, uv, acc[4]); acc[5] = fma_(gr, v2, acc[5]);
-                        acc[6] = fma_(gr, u2 * uu, acc[6]); acc[7] = fma_(gr, u2 * vv, acc[7]);
-                        acc[8] = fma_(gr, uu * v2, acc[8]); acc[9] = fma_(gr, v2 * vv, acc[9]);
-                    }
-                }
-                lane_c[s] += acc_c;                      // one cross-lane reduction per launch, not per chunk
-            }
-        } else {
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const T* W = P + P_W + s * species_block(hc);
-            const int gbase = P_W + s * species_block(hc);
-            const Pack<T, VEC>& hs = s == 0 ? u : v;
-            T gr[VEC];
-            double acc_c = 0.0;                          // heavily cancelling sum: fp64
-            T acc_b4 = T(0);
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                gr[i] = gc[s].v[i] * dt;
-                acc_c += (double)(dl[s][i] * hs.v[i]);
-                acc_b4 += gr[i];
-            }
-            if constexpr (WGRAD) {
-                acc_c = wave_sum_to_last(acc_c);
-                acc_b4 = wave_sum_to_last(acc_b4);
-                if (lane == REDUCE_LANE) {
-                    redc[wave * 2 + s] += acc_c;
-                    myred[gbase + 10 * hc] += acc_b4;
-                }
-            } else {
-                lane_c[s] += acc_c;
-            }
-            auto channel = [&](int j) {
-                const T* w = W + 10 * j;
-                const T w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4], w5 = w[5], w6 = w[6], w7 = w[7],
-                        w8 = w[8], w9 = w[9];
-                T acc[10];
-#pragma unroll
-                for (int m = 0; m < 10; ++m) acc[m] = T(0);
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) {
-                    const T a1 = fma_(w0, u.v[i], fma_(w1, v.v[i], w2));
-                    const T a2 = fma_(w3, u.v[i], fma_(w4, v.v[i], w5));
-                    const T a3 = fma_(w6, u.v[i], fma_(w7, v.v[i], w8));
-                    const T p12 = a1 * a2;
-                    const T gw = gr[i] * w9;
-                    const T q1 = gw * (a2 * a3), q2 = gw * (a1 * a3), q3 = gw * p12;
-                    if constexpr (WGRAD) {
-                        acc[9] += gr[i] * (p12 * a3);
-                        acc[0] += q1 * u.v[i]; acc[1] += q1 * v.v[i]; acc[2] += q1;
-                        acc[3] += q2 * u.v[i]; acc[4] += q2 * v.v[i]; acc[5] += q2;
-                        acc[6] += q3 * u.v[i]; acc[7] += q3 * v.v[i]; acc[8] += q3;
-                    }
-                    du[i] = fma_(q1, w0, fma_(q2, w3, fma_(q3, w6, du[i])));
-                    dv[i] = fma_(q1, w1, fma_(q2, w4, fma_(q3, w7, dv[i])));
-                }
-                if constexpr (WGRAD) {
-#pragma unroll
-                    for (int m = 0; m < 10; ++m) acc[m] = wave_sum_to_last(acc[m]);
-                    if (lane == REDUCE_LANE) {
-#pragma unroll
-                        for (int m = 0; m < 10; ++m) myred[gbase + 10 * j + m] += acc[m];
-                    }
-                }
-                        };
-            if constexpr (HC > 0) {                      // compile-time width: fully unrolled
-#pragma unroll
-                for (int j = 0; j < HC; ++j) channel(j);
-            } else {
-                for (int j = 0; j < hc; ++j) channel(j);
-            }
-        }
-
-        }
-
-        if (valid) {
-            Pack<T, VEC> ou, ov;
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                const T tu = P[P_COEF + 0] * dl[0][i] + du[i];
-                const T tv = P[P_COEF + 1] * dl[1][i] + dv[i];
-                ou.v[i] = gc[0].v[i] + tu;
-                ov.v[i] = gc[1].v[i] + tv;
-            }
-            if (inj) {
-                Pack<T, VEC> ju = u, jv = v;
-                if (g.loss.mode != 1) {                                  // mode 1 injects a function of the state alone
-                    ju = ldb<T, VEC>(plane_base<T, NDIM>(inj + g.off, g, iz), L.eb);
-                    jv = ldb<T, VEC>(plane_base<T, NDIM>(inj + g.ss + g.off, g, iz), L.eb);
-                }
-                const T la = g.loss.mode ? loss_factor<T>(g.loss) : T(0);
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) {
-                    ou.v[i] += loss_inject(g.loss.mode, la, u.v[i], ju.v[i]);
-                    ov.v[i] += loss_inject(g.loss.mode, la, v.v[i], jv.v[i]);
-                }
-            }
-            stb<T, VEC>(const_cast<char*>(plane_base<T, NDIM>(Gp + g.off, g, iz)), L.eb, ou);
-            stb<T, VEC>(const_cast<char*>(plane_base<T, NDIM>(Gp + g.ss + g.off, g, iz)), L.eb, ov);
-        }
-        }   // planes of the group
-    }
-
-    if constexpr (!WGRAD || LANE_MOM) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const double r = wave_sum_to_last(lane_c[s]);
-            if (lane == REDUCE_LANE) redc[wave * 2 + s] += r;
-        }
-    }
-    if constexpr (LANE_MOM) {
-        // Block-wide sums of the 20 per-lane moments through an LDS transpose: every thread writes its 20 values, then 8
-        // lanes per moment add NT/8 values each and fold with three DPP steps.  The earlier form (20 six-step DPP wave
-        // reductions per wave) cost 1.6 us of a 21.6 us launch at 128^3 -- measured by removing it (timing experiment) --
-        // because every wave runs it in the tail of the launch, when nothing is left to overlap it with.
-        const int NT = (int)blockDim.x, RS = NT + 8;                 // row stride: + 8 floats -> 8 rows cover all banks
-        T* scr = reinterpret_cast<T*>(smem_raw + (((size_t)nwaves * np * sizeof(T) + 15) / 16 * 16) +
-                                      (size_t)nwaves * 2 * sizeof(double));
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int m = 0; m < 10; ++m) scr[(10 * s + m) * RS + (int)threadIdx.x] = macc[s][m];
-        __syncthreads();
-        for (int base = 0; base < 160; base += NT) {                 // uniform trip count: whole waves run the DPP steps
-            const int task = base + (int)threadIdx.x;
-            const int mm = min(task, 159) >> 3, part = task & 7;
-            T a = T(0);
-            if (task < 160) {
-                // NT / 8 = 8 .. 32 values per lane, NT a multiple of 64: eight loads in flight, four partial sums
-                T a0 = T(0), a1 = T(0), a2 = T(0), a3 = T(0);
-                const T* row = scr + mm * RS + part;
-                for (int k = 0; k < NT; k += 64) {
-                    const T v0 = row[k], v1 = row[k + 8], v2 = row[k + 16], v3 = row[k + 24];
-                    const T v4 = row[k + 32], v5 = row[k + 40], v6 = row[k + 48], v7 = row[k + 56];
-                    a0 += v0; a1 += v1; a2 += v2; a3 += v3;
-                    a0 += v4; a1 += v5; a2 += v6; a3 += v7;
-                }
-                a = (a0 + a1) + (a2 + a3);
-            }
-            a += dpp_mov<0x111, 0xF>(a);                             // row_shr:1, :2, :4 -> lane 7 of each group of 8
-            a += dpp_mov<0x112, 0xF>(a);
-            a += dpp_mov<0x114, 0xF>(a);
-            if (task < 160 && part == 7) red[P_W + mm] = a;          // wave 0's row of `red` (the others stay zero)
-        }
-    }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < np; idx += blockDim.x) {
-        if (!carries_grad(idx)) continue;
-        double s = 0.0;
-        if (idx == P_COEF || idx == P_COEF + 1)
-            for (int w = 0; w < nwaves; ++w) s += redc[w * 2 + idx - P_COEF];
-        else
-            for (int w = 0; w < nwaves; ++w) s += (double)red[w * np + idx];
-        prow[idx] = (idx == (int)threadIdx.x ? pold : prow[idx]) + s;
-    }
-}
-
-// Batched forward step (B independent states [B][2][*S], one parameter block): pi_fwd_kernel's body on sample blockIdx.y of a
-// (workgroups of one sample, B) grid.  A copy, not a shared body: the unbatched kernel's code stays exactly as it was.
-template <typename T, int NDIM, int HC, int VEC>
-__global__ void __launch_bounds__(256)
-pi_fwd_batch_kernel(const T* __restrict__ h, T* __restrict__ out, const T* __restrict__ P, Geom g, int hc_rt, long sample)
-{
-    constexpr int RZ = 1;
-    h += (long)blockIdx.y * sample;                // sample blockIdx.y: 64-bit base once, in-sample offsets as pi_fwd_kernel
-    out += (long)blockIdx.y * sample;
-    static_assert(NDIM == 3 || RZ == 1, "plane blocking is a 3D notion");
-    const int hc = HC > 0 ? HC : hc_rt;      // unused when HC == POLY
-    // one virtual block (plane group, row group, x block) per workgroup, or -- option fwd_blocks -- a bounded grid of
-    // workgroups that walk the virtual blocks in order (measured slower: 384^3 376 -> 416 us)
-    unsigned first = xcd_remap(blockIdx.x, gridDim.x);
-    if (g.xwin) {                                   // all XCDs inside one window of the grid at a time (see launch_fwd)
-        const unsigned base = blockIdx.x / g.xwin * g.xwin;
-        const unsigned len = min(g.xwin, gridDim.x - base);
-        first = base + xcd_remap(blockIdx.x - base, len);
-    }
-    const T dt = P[P_DT];
-    PI_STAMP3(0);
-    for (unsigned vb = first; vb < g.nblk; vb += gridDim.x) {
-        const Lane L = locate<T, NDIM, VEC>(g, vb);
-        if (!L.valid) continue;
-        const T* hs[2] = {h + g.off, h + g.ss + g.off};
-        // 3D: the lane's chunk in planes i0-2 .. i0+RZ+1, both species, requested up front (RZ + 4 loads per species
-        // serve RZ output planes)
-        PlaneWindow<T, VEC, NDIM == 3 ? RZ : 1> win[2];
-        if constexpr (NDIM == 3) {
-            win[0].load(hs[0], g, L);
-            win[1].load(hs[1], g, L);
-        }
-#pragma unroll
-        for (int j = 0; j < RZ; ++j) {
-            const int iz = L.i0 + j;
-            if (NDIM == 3 && iz >= g.n0) break;          // partial last plane group (block-uniform)
-            const char* pu = plane_base<T, NDIM>(hs[0], g, iz);
-            const char* pv = plane_base<T, NDIM>(hs[1], g, iz);
-            Pack<T, VEC> cu, cv;
-            T lap[2][VEC];
-            if constexpr (NDIM == 3) {
-                cu = win[0].w[j + 2];
-                cv = win[1].w[j + 2];
-                win[0].template planes<+1>(j, P, lap[0]);
-                win[1].template planes<+1>(j, P, lap[1]);
-            } else {
-                cu = ldb<T, VEC>(pu, L.eb);
-                cv = ldb<T, VEC>(pv, L.eb);
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) { lap[0][i] = P[P_C0] * cu.v[i]; lap[1][i] = P[P_C0] * cv.v[i]; }
-            }
-            star2_inplane<T, NDIM, VEC, +1>(pu, P, g, L, cu, lap[0]);
-            star2_inplane<T, NDIM, VEC, +1>(pv, P, g, L, cv, lap[1]);
-
-            // The species / hidden-channel loops stay ROLLED on purpose: a fully unrolled body is several KiB
-            // of straight-line code that every wave executes exactly once, and at one wave per SIMD the
-            // kernel then runs at instruction-fetch speed (measured ~16 cycles per VALU op).  The rolled
-            // body is ~40 instructions, I$-resident, with next channel's 10 scalars prefetched into SGPRs.
-#pragma clang loop unroll(disable)
-            for (int s = 0; s < 2; ++s) {
-                T rr[VEC];
-                if constexpr (HC == POLY) {
-                    const T* c = P + P_W + 10 * s;
-#pragma unroll
-                    for (int i = 0; i < VEC; ++i) rr[i] = poly_r(c, cu.v[i], cv.v[i]);
-                } else {
-                    const T* W = P + P_W + s * species_block(hc);
-#pragma unroll
-                    for (int i = 0; i < VEC; ++i) rr[i] = W[10 * hc];
-                    W10<T> nx = load_w10(W);
-#pragma clang loop unroll(disable)
-                    for (int jj = 0; jj < hc; ++jj) {
-                        const W10<T> c = nx;
-                        if (jj + 1 < hc) nx = load_w10(W + 10 * (jj + 1));
-#pragma unroll
-                        for (int i = 0; i < VEC; ++i) {
-                            const T a1 = fma_(c.w[0], cu.v[i], fma_(c.w[1], cv.v[i], c.w[2]));
-                            const T a2 = fma_(c.w[3], cu.v[i], fma_(c.w[4], cv.v[i], c.w[5]));
-                            const T a3 = fma_(c.w[6], cu.v[i], fma_(c.w[7], cv.v[i], c.w[8]));
-                            rr[i] = fma_(c.w[9], (a1 * a2) * a3, rr[i]);
-                        }
-                    }
-                }
-                const T coef = P[P_COEF + s];
-                Pack<T, VEC> o;
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) {
-                    const T hv = s == 0 ? cu.v[i] : cv.v[i];
-                    const T lp = s == 0 ? lap[0][i] : lap[1][i];
-                    const T res = coef * lp + rr[i];            // two roundings (train_2drd.py:115)
-                    const T inc = res * dt;                     // two roundings (train_2drd.py:117)
-                    o.v[i] = hv + inc;
-                }
-                char* po = const_cast<char*>(plane_base<T, NDIM>(out + s * g.ss + g.off, g, iz));
-                stb<T, VEC>(po, L.eb, o);
-            }
-            PI_STAMP3(4 + (j > 0));
-        }
-    }
-    PI_STAMP3(7);
-}
-
-// Batched adjoint step: pi_bwd_kernel's body on sample blockIdx.y of a (workgroups of one sample, B) grid, partial row
-// blockIdx.y * gridDim.x + blockIdx.x (the fixed-order row reduction sums the samples in order).  A copy, as above.
-template <typename T, int NDIM, int HC, int VEC, bool WGRAD>
-__global__ void __launch_bounds__(256)
-pi_bwd_batch_kernel(const T* __restrict__ h, const T* __restrict__ G, const T* __restrict__ inj, T* __restrict__ Gp,
-                    double* __restrict__ partials, const T* __restrict__ P, Geom g, int hc_rt, long sample)
-{
-    constexpr int RZ = 1;
-    const long sbase = (long)blockIdx.y * sample;  // sample blockIdx.y; partial row per (sample, workgroup)
-    h += sbase; G += sbase; Gp += sbase;
-    if (inj) inj += sbase;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T* red = reinterpret_cast<T*>(smem_raw);           // [nwaves][np] running sums of this block
-
-    const int hc = HC == POLY ? 0 : (HC > 0 ? HC : hc_rt);
-    const int np = nparams(hc);
-    const int nwaves = blockDim.x / WAVE;
-    const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
-    T* myred = red + wave * np;
-    double* redc = reinterpret_cast<double*>(smem_raw + ((size_t)nwaves * np * sizeof(T) + 15) / 16 * 16);   // [nwaves][2]
-    for (int i = threadIdx.x; i < nwaves * np; i += blockDim.x) red[i] = T(0);
-    if (threadIdx.x < 2 * nwaves) redc[threadIdx.x] = 0.0;
-    // running partial of this workgroup's row: requested NOW, needed at the very end (a dependent load -> add -> store
-    // in the tail of every launch otherwise; same fix as in the tile sweep)
-    auto carries_grad = [&](int idx) {
-        if (idx >= np || idx == P_DT || (idx >= P_C0 && idx < P_W)) return false;   // dt, frozen stencil: no gradient
-        return WGRAD || idx < P_W;                                                  // sweep-only flavour: coefficients only
-    };
-    double* const prow = partials + ((long)blockIdx.y * gridDim.x + blockIdx.x) * np;
-    const double pold = carries_grad((int)threadIdx.x) ? prow[threadIdx.x] : 0.0;
-    __syncthreads();
-
-    const T dt = P[P_DT];
-
-    double lane_c[2] = {0.0, 0.0};
-    // poly mode with fused gradients: the 20 coefficient moments stay in registers over all chunks of the lane and are
-    // reduced across lanes once per launch (was: 22 wave reductions per chunk)
-    constexpr bool LANE_MOM = WGRAD && HC == POLY;
-    T macc[LANE_MOM ? 2 : 1][LANE_MOM ? 10 : 1];
-    if constexpr (LANE_MOM) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int m = 0; m < 10; ++m) macc[s][m] = T(0);
-    }
-
-    // virtual blocks (plane, row group, x block) of this workgroup: block-uniform trip count (wave-level reductions
-    // inside need whole waves, which a uniform loop guarantees); addressing as in the forward kernel
-    for (unsigned vb = xcd_remap(blockIdx.x, gridDim.x); vb < g.nblk; vb += gridDim.x) {
-        const Lane L = locate<T, NDIM, VEC>(g, vb);
-        const bool valid = L.valid;
-        // 3D: the adjoint state of planes i0-2 .. i0+RZ+1 in registers, shared by the RZ output planes of this pass
-        PlaneWindow<T, VEC, NDIM == 3 ? RZ : 1> win[2];
-        if constexpr (NDIM == 3) {
-            win[0].load(G + g.off, g, L);
-            win[1].load(G + g.ss + g.off, g, L);
-        }
-#pragma unroll
-        for (int jz = 0; jz < RZ; ++jz) {
-        const int iz = L.i0 + jz;
-        if (NDIM == 3 && iz >= g.n0) break;              // partial last plane group (block-uniform)
-        const char* phu = plane_base<T, NDIM>(h + g.off, g, iz);
-        const char* phv = plane_base<T, NDIM>(h + g.ss + g.off, g, iz);
-        const char* pgu = plane_base<T, NDIM>(G + g.off, g, iz);
-        const char* pgv = plane_base<T, NDIM>(G + g.ss + g.off, g, iz);
-        const Pack<T, VEC> u = ldb<T, VEC>(phu, L.eb), v = ldb<T, VEC>(phv, L.eb);
-        Pack<T, VEC> gc[2];
-        T dl[2][VEC];
-        if constexpr (NDIM == 3) {
-            gc[0] = win[0].w[jz + 2];
-            gc[1] = win[1].w[jz + 2];
-            win[0].template planes<-1>(jz, P, dl[0]);
-            win[1].template planes<-1>(jz, P, dl[1]);
-        } else {
-            gc[0] = ldb<T, VEC>(pgu, L.eb);
-            gc[1] = ldb<T, VEC>(pgv, L.eb);
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) { dl[0][i] = P[P_C0] * gc[0].v[i]; dl[1][i] = P[P_C0] * gc[1].v[i]; }
-        }
-        star2_inplane<T, NDIM, VEC, -1>(pgu, P, g, L, gc[0], dl[0]);
-        star2_inplane<T, NDIM, VEC, -1>(pgv, P, g, L, gc[1], dl[1]);
-        const T live = valid ? T(1) : T(0);
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                dl[s][i] = (dl[s][i] * dt) * live;
-                gc[s].v[i] *= live;
-            }
-
-        T du[VEC], dv[VEC];
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) du[i] = dv[i] = T(0);
-
-        if constexpr (HC == POLY) {
-            // monomials shared by both species (only needed for the moment sums)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const T* c = P + P_W + 10 * s;
-                const int gbase = P_W + 10 * s;
-                const Pack<T, VEC>& hs = s == 0 ? u : v;
-                (void)gbase;
-                double acc_c = 0.0;                      // heavily cancelling sum (stencil row-sum ~ 0): keep it in fp64
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) {
-                    const T gr = gc[s].v[i] * dt;
-                    acc_c += (double)(dl[s][i] * hs.v[i]);
-                    T ru, rv;
-                    poly_dr(c, u.v[i], v.v[i], ru, rv);
-                    du[i] = fma_(gr, ru, du[i]);
-                    dv[i] = fma_(gr, rv, dv[i]);
-                    if constexpr (WGRAD) {
-                        T (&acc)[10] = macc[s];
-                        const T uu = u.v[i], vv = v.v[i];
-                        const T u2 = uu * uu, uv = uu * vv, v2 = vv * vv;
-                        acc[0] += gr;
-                        acc[1] = fma_(gr, uu, acc[1]); acc[2] = fma_(gr, vv, acc[2]);
-                        acc[3] = fma_(gr, u2, acc[3]); acc[4] = fma_(gr, uv, acc[4]); acc[5] = fma_(gr, v2, acc[5]);
-                        acc[6] = fma_(gr, u2 * uu, acc[6]); acc[7] = fma_(gr, u2 * vv, acc[7]);
-                        acc[8] = fma_(gr, uu * v2, acc[8]); acc[9] = fma_(gr, v2 * vv, acc[9]);
-                    }
-                }
-                lane_c[s] += acc_c;                      // one cross-lane reduction per launch, not per chunk
-            }
-        } else {
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const T* W = P + P_W + s * species_block(hc);
-            const int gbase = P_W + s * species_block(hc);
-            const Pack<T, VEC>& hs = s == 0 ? u : v;
-            T gr[VEC];
-            double acc_c = 0.0;                          // heavily cancelling sum: fp64
-            T acc_b4 = T(0);
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                gr[i] = gc[s].v[i] * dt;
-                acc_c += (double)(dl[s][i] * hs.v[i]);
-                acc_b4 += gr[i];
-            }
-            if constexpr (WGRAD) {
-                acc_c = wave_sum_to_last(acc_c);
-                acc_b4 = wave_sum_to_last(acc_b4);
-                if (lane == REDUCE_LANE) {
-                    redc[wave * 2 + s] += acc_c;
-                    myred[gbase + 10 * hc] += acc_b4;
-                }
-            } else {
-                lane_c[s] += acc_c;
-            }
-            auto channel = [&](int j) {
-                const T* w = W + 10 * j;
-                const T w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4], w5 = w[5], w6 = w[6], w7 = w[7],
-                        w8 = w[8], w9 = w[9];
-                T acc[10];
-#pragma unroll
-                for (int m = 0; m < 10; ++m) acc[m] = T(0);
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) {
-                    const T a1 = fma_(w0, u.v[i], fma_(w1, v.v[i], w2));
-                    const T a2 = fma_(w3, u.v[i], fma_(w4, v.v[i], w5));
-                    const T a3 = fma_(w6, u.v[i], fma_(w7, v.v[i], w8));
-                    const T p12 = a1 * a2;
-                    const T gw = gr[i] * w9;
-                    const T q1 = gw * (a2 * a3), q2 = gw * (a1 * a3), q3 = gw * p12;
-                    if constexpr (WGRAD) {
-                        acc[9] += gr[i] * (p12 * a3);
-                        acc[0] += q1 * u.v[i]; acc[1] += q1 * v.v[i]; acc[2] += q1;
-                        acc[3] += q2 * u.v[i]; acc[4] += q2 * v.v[i]; acc[5] += q2;
-                        acc[6] += q3 * u.v[i]; acc[7] += q3 * v.v[i]; acc[8] += q3;
-                    }
-                    du[i] = fma_(q1, w0, fma_(q2, w3, fma_(q3, w6, du[i])));
-                    dv[i] = fma_(q1, w1, fma_(q2, w4, fma_(q3, w7, dv[i])));
-                }
-                if constexpr (WGRAD) {
-#pragma unroll
-                    for (int m = 0; m < 10; ++m) acc[m] = wave_sum_to_last(acc[m]);
-                    if (lane == REDUCE_LANE) {
-#pragma unroll
-                        for (int m = 0; m < 10; ++m) myred[gbase + 10 * j + m] += acc[m];
-                    }
-                }
-                        };
-            if constexpr (HC > 0) {                      // compile-time width: fully unrolled
-#pragma unroll
-                for (int j = 0; j < HC; ++j) channel(j);
-            } else {
-                for (int j = 0; j < hc; ++j) channel(j);
-            }
-        }
-
-        }
-
-        if (valid) {
-            Pack<T, VEC> ou, ov;
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                const T tu = P[P_COEF + 0] * dl[0][i] + du[i];
-                const T tv = P[P_COEF + 1] * dl[1][i] + dv[i];
-                ou.v[i] = gc[0].v[i] + tu;
-                ov.v[i] = gc[1].v[i] + tv;
-            }
-            if (inj) {
-                Pack<T, VEC> ju = u, jv = v;
-                if (g.loss.mode != 1) {                                  // mode 1 injects a function of the state alone
-                    ju = ldb<T, VEC>(plane_base<T, NDIM>(inj + g.off, g, iz), L.eb);
-                    jv = ldb<T, VEC>(plane_base<T, NDIM>(inj + g.ss + g.off, g, iz), L.eb);
-                }
-                const T la = g.loss.mode ? loss_factor<T>(g.loss) : T(0);
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) {
-                    ou.v[i] += loss_inject(g.loss.mode, la, u.v[i], ju.v[i]);
-                    ov.v[i] += loss_inject(g.loss.mode, la, v.v[i], jv.v[i]);
-                }
-            }
-            stb<T, VEC>(const_cast<char*>(plane_base<T, NDIM>(Gp + g.off, g, iz)), L.eb, ou);
-            stb<T, VEC>(const_cast<char*>(plane_base<T, NDIM>(Gp + g.ss + g.off, g, iz)), L.eb, ov);
-        }
-        }   // planes of the group
-    }
-
-    if constexpr (!WGRAD || LANE_MOM) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const double r = wave_sum_to_last(lane_c[s]);
-            if (lane == REDUCE_LANE) redc[wave * 2 + s] += r;
-        }
-    }
-    if constexpr (LANE_MOM) {
-        // Block-wide sums of the 20 per-lane moments through an LDS transpose: every thread writes its 20 values, then 8
-        // lanes per moment add NT/8 values each and fold with three DPP steps.  The earlier form (20 six-step DPP wave
-        // reductions per wave) cost 1.6 us of a 21.6 us launch at 128^3 -- measured by removing it (timing experiment) --
-        // because every wave runs it in the tail of the launch, when nothing is left to overlap it with.
-        const int NT = (int)blockDim.x, RS = NT + 8;                 // row stride: + 8 floats -> 8 rows cover all banks
-        T* scr = reinterpret_cast<T*>(smem_raw + (((size_t)nwaves * np * sizeof(T) + 15) / 16 * 16) +
-                                      (size_t)nwaves * 2 * sizeof(double));
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int m = 0; m < 10; ++m) scr[(10 * s + m) * RS + (int)threadIdx.x] = macc[s][m];
-        __syncthreads();
-        for (int base = 0; base < 160; base += NT) {                 // uniform trip count: whole waves run the DPP steps
-            const int task = base + (int)threadIdx.x;
-            const int mm = min(task, 159) >> 3, part = task & 7;
-            T a = T(0);
-            if (task < 160) {
-                // NT / 8 = 8 .. 32 values per lane, NT a multiple of 64: eight loads in flight, four partial sums
-                T a0 = T(0), a1 = T(0), a2 = T(0), a3 = T(0);
-                const T* row = scr + mm * RS + part;
-                for (int k = 0; k < NT; k += 64) {
-                    const T v0 = row[k], v1 = row[k + 8], v2 = row[k + 16], v3 = row[k + 24];
-                    const T v4 = row[k + 32], v5 = row[k + 40], v6 = row[k + 48], v7 = row[k + 56];
-                    a0 += v0; a1 += v1; a2 += v2; a3 += v3;
-                    a0 += v4; a1 += v5; a2 += v6; a3 += v7;
-                }
-                a = (a0 + a1) + (a2 + a3);
-            }
-            a += dpp_mov<0x111, 0xF>(a);                             // row_shr:1, :2, :4 -> lane 7 of each group of 8
-            a += dpp_mov<0x112, 0xF>(a);
-            a += dpp_mov<0x114, 0xF>(a);
-            if (task < 160 && part == 7) red[P_W + mm] = a;          // wave 0's row of `red` (the others stay zero)
-        }
-    }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < np; idx += blockDim.x) {
-        if (!carries_grad(idx)) continue;
-        double s = 0.0;
-        if (idx == P_COEF || idx == P_COEF + 1)
-            for (int w = 0; w < nwaves; ++w) s += redc[w * 2 + idx - P_COEF];
-        else
-            for (int w = 0; w < nwaves; ++w) s += (double)red[w * np + idx];
-        prow[idx] = (idx == (int)threadIdx.x ? pold : prow[idx]) + s;
-    }
-}
-
-// Ensemble forward step (B independent states [B][2][*S], parameter blocks P [B][np]): pi_fwd_batch_kernel with the block
-// of sample blockIdx.y.  P moves once by a wave-uniform offset, so the block still arrives through scalar loads.  A copy:
-// the batched kernel's code stays exactly as it was.
-template <typename T, int NDIM, int HC, int VEC>
-__global__ void __launch_bounds__(256)
-pi_fwd_ens_kernel(const T* __restrict__ h, T* __restrict__ out, const T* __restrict__ P, Geom g, int hc_rt, long sample, int np)
-{
-    constexpr int RZ = 1;
-    h += (long)blockIdx.y * sample;                // sample blockIdx.y: 64-bit base once, in-sample offsets as pi_fwd_kernel
-    out += (long)blockIdx.y * sample;
-    P += (long)blockIdx.y * np;                    // block of sample blockIdx.y
-    static_assert(NDIM == 3 || RZ == 1, "plane blocking is a 3D notion");
-    const int hc = HC > 0 ? HC : hc_rt;      // unused when HC == POLY
-    // one virtual block (plane group, row group, x block) per workgroup, or -- option fwd_blocks -- a bounded grid of
-    // workgroups that walk the virtual blocks in order (measured slower: 384^3 376 -> 416 us)
-    unsigned first = xcd_remap(blockIdx.x, gridDim.x);
-    if (g.xwin) {                                   // all XCDs inside one window of the grid at a time (see launch_fwd)
-        const unsigned base = blockIdx.x / g.xwin * g.xwin;
-        const unsigned len = min(g.xwin, gridDim.x - base);
-        first = base + xcd_remap(blockIdx.x - base, len);
-    }
-    const T dt = P[P_DT];
-    PI_STAMP3(0);
-    for (unsigned vb = first; vb < g.nblk; vb += gridDim.x) {
-        const Lane L = locate<T, NDIM, VEC>(g, vb);
-        if (!L.valid) continue;
-        const T* hs[2] = {h + g.off, h + g.ss + g.off};
-        // 3D: the lane's chunk in planes i0-2 .. i0+RZ+1, both species, requested up front (RZ + 4 loads per species
-        // serve RZ output planes)
-        PlaneWindow<T, VEC, NDIM == 3 ? RZ : 1> win[2];
-        if constexpr (NDIM == 3) {
-            win[0].load(hs[0], g, L);
-            win[1].load(hs[1], g, L);
-        }
-#pragma unroll
-        for (int j = 0; j < RZ; ++j) {
-            const int iz = L.i0 + j;
-            if (NDIM == 3 && iz >= g.n0) break;          // partial last plane group (block-uniform)
-            const char* pu = plane_base<T, NDIM>(hs[0], g, iz);
-            const char* pv = plane_base<T, NDIM>(hs[1], g, iz);
-            Pack<T, VEC> cu, cv;
-            T lap[2][VEC];
-            if constexpr (NDIM == 3) {
-                cu = win[0].w[j + 2];
-                cv = win[1].w[j + 2];
-                win[0].template planes<+1>(j, P, lap[0]);
-                win[1].template planes<+1>(j, P, lap[1]);
-            } else {
-                cu = ldb<T, VEC>(pu, L.eb);
-                cv = ldb<T, VEC>(pv, L.eb);
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) { lap[0][i] = P[P_C0] * cu.v[i]; lap[1][i] = P[P_C0] * cv.v[i]; }
-            }
-            star2_inplane<T, NDIM, VEC, +1>(pu, P, g, L, cu, lap[0]);
-            star2_inplane<T, NDIM, VEC, +1>(pv, P, g, L, cv, lap[1]);
-
-            // The species / hidden-channel loops stay ROLLED on purpose: a fully unrolled body is several KiB
-            // of straight-line code that every wave executes exactly once, and at one wave per SIMD the
-            // kernel then runs at instruction-fetch speed (measured ~16 cycles per VALU op).  The rolled
-            // body is ~40 instructions, I$-resident, with next channel's 10 scalars prefetched into SGPRs.
-#pragma clang loop unroll(disable)
-            for (int s = 0; s < 2; ++s) {
-                T rr[VEC];
-                if constexpr (HC == POLY) {
-                    const T* c = P + P_W + 10 * s;
-#pragma unroll
-                    for (int i = 0; i < VEC; ++i) rr[i] = poly_r(c, cu.v[i], cv.v[i]);
-                } else {
-                    const T* W = P + P_W + s * species_block(hc);
-#pragma unroll
-                    for (int i = 0; i < VEC; ++i) rr[i] = W[10 * hc];
-                    W10<T> nx = load_w10(W);
-#pragma clang loop unroll(disable)
-                    for (int jj = 0; jj < hc; ++jj) {
-                        const W10<T> c = nx;
-                        if (jj + 1 < hc) nx = load_w10(W + 10 * (jj + 1));
-#pragma unroll
-                        for (int i = 0; i < VEC; ++i) {
-                            const T a1 = fma_(c.w[0], cu.v[i], fma_(c.w[1], cv.v[i], c.w[2]));
-                            const T a2 = fma_(c.w[3], cu.v[i], fma_(c.w[4], cv.v[i], c.w[5]));
-                            const T a3 = fma_(c.w[6], cu.v[i], fma_(c.w[7], cv.v[i], c.w[8]));
-                            rr[i] = fma_(c.w[9], (a1 * a2) * a3, rr[i]);
-                        }
-                    }
-                }
-                const T coef = P[P_COEF + s];
-                Pack<T, VEC> o;
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) {
-                    const T hv = s == 0 ? cu.v[i] : cv.v[i];
-                    const T lp = s == 0 ? lap[0][i] : lap[1][i];
-                    const T res = coef * lp + rr[i];            // two roundings (train_2drd.py:115)
-                    const T inc = res * dt;                     // two roundings (train_2drd.py:117)
-                    o.v[i] = hv + inc;
-                }
-                char* po = const_cast<char*>(plane_base<T, NDIM>(out + s * g.ss + g.off, g, iz));
-                stb<T, VEC>(po, L.eb, o);
-            }
-            PI_STAMP3(4 + (j > 0));
-        }
-    }
-    PI_STAMP3(7);
-}
-
-// Ensemble adjoint step: pi_bwd_batch_kernel with the block of sample blockIdx.y and the partial row
-// blockIdx.y * rows + blockIdx.x -- `rows` per sample, one stride for every launch of a call, so that the finishing
-// reduction (pi_reduce_partials_ens_kernel) sums each sample's rows alone.  A copy, as above.
-template <typename T, int NDIM, int HC, int VEC, bool WGRAD>
-__global__ void __launch_bounds__(256)
-pi_bwd_ens_kernel(const T* __restrict__ h, const T* __restrict__ G, const T* __restrict__ inj, T* __restrict__ Gp,
-                    double* __restrict__ partials, const T* __restrict__ P, Geom g, int hc_rt, long sample, int rows)
-{
-    constexpr int RZ = 1;
-    const long sbase = (long)blockIdx.y * sample;  // sample blockIdx.y; partial row per (sample, workgroup)
-    h += sbase; G += sbase; Gp += sbase;
-    if (inj) inj += sbase;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T* red = reinterpret_cast<T*>(smem_raw);           // [nwaves][np] running sums of this block
-
-    const int hc = HC == POLY ? 0 : (HC > 0 ? HC : hc_rt);
-    const int np = nparams(hc);
-    P += (long)blockIdx.y * np;                         // block of sample blockIdx.y
-    const int nwaves = blockDim.x / WAVE;
-    const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
-    T* myred = red + wave * np;
-    double* redc = reinterpret_cast<double*>(smem_raw + ((size_t)nwaves * np * sizeof(T) + 15) / 16 * 16);   // [nwaves][2]
-    for (int i = threadIdx.x; i < nwaves * np; i += blockDim.x) red[i] = T(0);
-    if (threadIdx.x < 2 * nwaves) redc[threadIdx.x] = 0.0;
-    // running partial of this workgroup's row: requested NOW, needed at the very end (a dependent load -> add -> store
-    // in the tail of every launch otherwise; same fix as in the tile sweep)
-    auto carries_grad = [&](int idx) {
-        if (idx >= np || idx == P_DT || (idx >= P_C0 && idx < P_W)) return false;   // dt, frozen stencil: no gradient
-        return WGRAD || idx < P_W;                                                  // sweep-only flavour: coefficients only
-    };
-    double* const prow = partials + ((long)blockIdx.y * rows + blockIdx.x) * np;
+    long row = blockIdx.x;
+    if constexpr (sizeof...(X) == 1) row = (long)blockIdx.y * gridDim.x + blockIdx.x;
+    if constexpr (sizeof...(X) == 2) row = (long)blockIdx.y * flavour_arg<1>(x...) + blockIdx.x;
+    double* const prow = partials + row * np;
     const double pold = carries_grad((int)threadIdx.x) ? prow[threadIdx.x] : 0.0;
     __syncthreads();
 
@@ -1515,19 +780,30 @@ pi_bwd_ens_kernel(const T* __restrict__ h, const T* __restrict__ G, const T* __r
 // latency, full chip.  NS = 2: one workgroup differentiates both species' branches (small hc, the
 // state is read once); NS = 1: blockIdx.y picks the species.  Hidden channels [j0, j0+JC).
 // ---------------------------------------------------------------------------------------------
-template <typename T, int JC, int NS, int VEC>
+// X... = `long fstride, int rows`: the ENSEMBLE gradient pass over the trajectories [T+1][B][2][*S] of B samples with B
+// parameter blocks [B][np], ONE launch: the sample is the last grid dimension (z here, whose y picks the species; y for the
+// moments below).  Each workgroup moves traj, adj and P once to its sample and writes partial row sample * rows + (its row
+// in the one-trajectory flavour).
+template <typename T, int JC, int NS, int VEC, typename... X>
 __global__ void __launch_bounds__(256)
 pi_wgrad_kernel(const T* __restrict__ traj, const T* __restrict__ adj, double* __restrict__ partials,
-                const T* __restrict__ P, long n, long ss, long off, int t_lo, int t_hi, int hc, int j0)
+                const T* __restrict__ P, long n, long ss, long off, int t_lo, int t_hi, int hc, int j0, X... x)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T* red = reinterpret_cast<T*>(smem_raw);            // [nwaves][NS*(10*JC+1)]
     constexpr int NA = 10 * JC + 1;
     const int np = nparams(hc);
+    if constexpr (sizeof...(X) == 2) {
+        const long sbase = (long)blockIdx.z * 2 * ss;   // sample blockIdx.z: its block, its frames, its rows
+        P += (long)blockIdx.z * np;
+        traj += sbase;
+        adj += sbase;
+    }
     const T dt = P[P_DT];
     // frames are [2][ss] with the n interior points of a species starting at `off` (slab layout: halo planes
-    // skipped; plain layout: ss = n, off = 0)
-    const long frame = 2 * ss;
+    // skipped; plain layout: ss = n, off = 0); ensemble: frame t -> t+1 of one sample is [B][2][ss] apart
+    long frame = 2 * ss;
+    if constexpr (sizeof...(X) == 2) frame = flavour_arg<0>(x...);
     const long cpf = n / VEC;                            // chunks per frame
     const long nsteps = t_hi - t_lo;
     const long stride = (long)gridDim.x * blockDim.x;
@@ -1597,7 +873,8 @@ pi_wgrad_kernel(const T* __restrict__ traj, const T* __restrict__ adj, double* _
         if (lane == REDUCE_LANE) red[(wave * NS + q) * NA + 10 * JC] = r;
     }
     __syncthreads();
-    const long row = (long)blockIdx.y * gridDim.x + blockIdx.x;
+    long row = (long)blockIdx.y * gridDim.x + blockIdx.x;
+    if constexpr (sizeof...(X) == 2) row += (long)blockIdx.z * flavour_arg<1>(x...);
     for (int k = threadIdx.x; k < NS * NA; k += blockDim.x) {
         const int q = k / NA, idx = k - q * NA;
         if (idx == 10 * JC && j0 != 0) continue;         // the Wh4 bias is accumulated by the j0 == 0 pass only
@@ -1617,15 +894,23 @@ pi_wgrad_kernel(const T* __restrict__ traj, const T* __restrict__ adj, double* _
 // ~30 VALU ops): HBM-bound.  The map back to the branch weights (dc/dW, multilinear) is a
 // 20 x (2*(10*hc+1)) chain rule done by the caller.
 // ---------------------------------------------------------------------------------------------
-template <typename T, int VEC>
+template <typename T, int VEC, typename... X>                       // X...: `long fstride, int rows`, as pi_wgrad_kernel
 __global__ void __launch_bounds__(256)
 pi_moments_kernel(const T* __restrict__ traj, const T* __restrict__ adj, double* __restrict__ partials,
-                  const T* __restrict__ P, long n, long ss, long off, int t_lo, int t_hi)
+                  const T* __restrict__ P, long n, long ss, long off, int t_lo, int t_hi, X... x)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T* red = reinterpret_cast<T*>(smem_raw);            // [nwaves][20]
+    long frame = 2 * ss, row = blockIdx.x;
+    if constexpr (sizeof...(X) == 2) {
+        const long sbase = (long)blockIdx.y * 2 * ss;   // sample blockIdx.y: its block, its frames, its rows
+        P += (long)blockIdx.y * NPOLY;
+        traj += sbase;
+        adj += sbase;
+        frame = flavour_arg<0>(x...);
+        row = (long)blockIdx.y * flavour_arg<1>(x...) + blockIdx.x;
+    }
     const T dt = P[P_DT];
-    const long frame = 2 * ss;
     const long cpf = n / VEC;
     const long nsteps = t_hi - t_lo;
     const long stride = (long)gridDim.x * blockDim.x;
@@ -1675,7 +960,7 @@ pi_moments_kernel(const T* __restrict__ traj, const T* __restrict__ adj, double*
     if (threadIdx.x < 20) {
         T sum = T(0);
         for (int w = 0; w < nwaves; ++w) sum += red[w * 20 + threadIdx.x];
-        partials[(long)blockIdx.x * NPOLY + P_W + threadIdx.x] += (double)sum;
+        partials[row * NPOLY + P_W + threadIdx.x] += (double)sum;
     }
 }
 
@@ -1970,198 +1255,20 @@ pi_sqerr_finish_kernel(const double* __restrict__ partials, int n, double scale,
 }
 
 // param_grad[idx] += sum_b partials[b][idx]; one wave per parameter, fixed order -> deterministic
+// ENS (grid (np, B)): per sample, param_grad[y][idx] += sum_b partials[y * nblocks + b][idx]
+template <bool ENS = false>
 __global__ void __launch_bounds__(64)
 pi_reduce_partials_kernel(const double* __restrict__ partials, int nblocks, int np, double* __restrict__ param_grad)
 {
     const int idx = blockIdx.x;
+    if constexpr (ENS) partials += (long)blockIdx.y * nblocks * np;
     double s = 0.0;
     for (int b = threadIdx.x; b < nblocks; b += WAVE) s += partials[(long)b * np + idx];
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, WAVE);
-    if (threadIdx.x == 0) param_grad[idx] += s;
-}
-
-// ---------------------------------------------------------------------------------------------
-// ENSEMBLE gradient pass: pi_wgrad_kernel / pi_moments_kernel over the trajectories [T+1][B][2][*S] of B samples with B
-// parameter blocks [B][np], ONE launch: the sample is the last grid dimension (z for wgrad, whose y picks the species; y for
-// the moments).  Each workgroup moves traj, adj and P once to its sample and writes partial row sample * rows + (its row in
-// the unbatched kernel).  Copies: the unbatched kernels' code stays exactly as it was.
-// ---------------------------------------------------------------------------------------------
-template <typename T, int JC, int NS, int VEC>
-__global__ void __launch_bounds__(256)
-pi_wgrad_ens_kernel(const T* __restrict__ traj, const T* __restrict__ adj, double* __restrict__ partials,
-                const T* __restrict__ P, long n, long ss, long off, int t_lo, int t_hi, int hc, int j0, long fstride,
-                    int rows)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T* red = reinterpret_cast<T*>(smem_raw);            // [nwaves][NS*(10*JC+1)]
-    constexpr int NA = 10 * JC + 1;
-    const int np = nparams(hc);
-    const long sbase = (long)blockIdx.z * 2 * ss;       // sample blockIdx.z: its block, its frames, its rows
-    P += (long)blockIdx.z * np;
-    traj += sbase;
-    adj += sbase;
-    const T dt = P[P_DT];
-    const long frame = fstride;                         // frame t -> t+1 of one sample: [B][2][ss] apart
-    const long cpf = n / VEC;                            // chunks per frame
-    const long nsteps = t_hi - t_lo;
-    const long stride = (long)gridDim.x * blockDim.x;
-    const long stride_t = stride / cpf, stride_x = stride - stride_t * cpf;
-
-    T acc[NS][JC][10];
-    T acc_b4[NS];
-#pragma unroll
-    for (int q = 0; q < NS; ++q) {
-        acc_b4[q] = T(0);
-#pragma unroll
-        for (int jj = 0; jj < JC; ++jj)
-#pragma unroll
-            for (int m = 0; m < 10; ++m) acc[q][jj][m] = T(0);
-    }
-
-    const long c0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    long tt = c0 / cpf, xc = c0 - tt * cpf;
-    while (tt < nsteps) {
-        const long t = t_lo + 1 + tt;                    // step t maps frame t-1 -> frame t
-        const long x = off + xc * VEC;
-        const Pack<T, VEC> u = ld<T, VEC>(traj + (t - 1) * frame + x);
-        const Pack<T, VEC> v = ld<T, VEC>(traj + (t - 1) * frame + ss + x);
-#pragma unroll
-        for (int q = 0; q < NS; ++q) {
-            const int s = NS == 2 ? q : (int)blockIdx.y;
-            const T* W = P + P_W + s * species_block(hc) + 10 * j0;
-            const Pack<T, VEC> a = ld<T, VEC>(adj + t * frame + s * ss + x);
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                const T gr = a.v[i] * dt;
-                acc_b4[q] += gr;
-#pragma unroll
-                for (int jj = 0; jj < JC; ++jj) {
-                    const T* w = W + 10 * jj;
-                    const T a1 = fma_(w[0], u.v[i], fma_(w[1], v.v[i], w[2]));
-                    const T a2 = fma_(w[3], u.v[i], fma_(w[4], v.v[i], w[5]));
-                    const T a3 = fma_(w[6], u.v[i], fma_(w[7], v.v[i], w[8]));
-                    const T p12 = a1 * a2;
-                    const T gw = gr * w[9];
-                    const T q1 = gw * (a2 * a3), q2 = gw * (a1 * a3), q3 = gw * p12;
-                    T* A = acc[q][jj];
-                    A[9] = fma_(gr, p12 * a3, A[9]);
-                    A[0] = fma_(q1, u.v[i], A[0]); A[1] = fma_(q1, v.v[i], A[1]); A[2] += q1;
-                    A[3] = fma_(q2, u.v[i], A[3]); A[4] = fma_(q2, v.v[i], A[4]); A[5] += q2;
-                    A[6] = fma_(q3, u.v[i], A[6]); A[7] = fma_(q3, v.v[i], A[7]); A[8] += q3;
-                }
-            }
-        }
-        xc += stride_x;
-        tt += stride_t;
-        if (xc >= cpf) { xc -= cpf; ++tt; }
-    }
-
-    const int nwaves = blockDim.x / WAVE;
-    const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
-#pragma unroll
-    for (int q = 0; q < NS; ++q) {
-#pragma unroll
-        for (int jj = 0; jj < JC; ++jj)
-#pragma unroll
-            for (int m = 0; m < 10; ++m) {
-                const T r = wave_sum_to_last(acc[q][jj][m]);
-                if (lane == REDUCE_LANE) red[(wave * NS + q) * NA + 10 * jj + m] = r;
-            }
-        const T r = wave_sum_to_last(acc_b4[q]);
-        if (lane == REDUCE_LANE) red[(wave * NS + q) * NA + 10 * JC] = r;
-    }
-    __syncthreads();
-    const long row = (long)blockIdx.z * rows + (long)blockIdx.y * gridDim.x + blockIdx.x;
-    for (int k = threadIdx.x; k < NS * NA; k += blockDim.x) {
-        const int q = k / NA, idx = k - q * NA;
-        if (idx == 10 * JC && j0 != 0) continue;         // the Wh4 bias is accumulated by the j0 == 0 pass only
-        const int s = NS == 2 ? q : (int)blockIdx.y;
-        const int gbase = P_W + s * species_block(hc);
-        T sum = T(0);
-        for (int w = 0; w < nwaves; ++w) sum += red[(w * NS + q) * NA + idx];
-        const int col = idx == 10 * JC ? gbase + 10 * hc : gbase + 10 * j0 + idx;
-        partials[row * np + col] += (double)sum;
-    }
-}
-
-template <typename T, int VEC>
-__global__ void __launch_bounds__(256)
-pi_moments_ens_kernel(const T* __restrict__ traj, const T* __restrict__ adj, double* __restrict__ partials,
-                  const T* __restrict__ P, long n, long ss, long off, int t_lo, int t_hi, long fstride, int rows)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T* red = reinterpret_cast<T*>(smem_raw);            // [nwaves][20]
-    const long sbase = (long)blockIdx.y * 2 * ss;       // sample blockIdx.y: its block, its frames, its rows
-    P += (long)blockIdx.y * NPOLY;
-    traj += sbase;
-    adj += sbase;
-    const T dt = P[P_DT];
-    const long frame = fstride;                         // frame t -> t+1 of one sample: [B][2][ss] apart
-    const long cpf = n / VEC;
-    const long nsteps = t_hi - t_lo;
-    const long stride = (long)gridDim.x * blockDim.x;
-    const long stride_t = stride / cpf, stride_x = stride - stride_t * cpf;
-    T acc[2][10];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int m = 0; m < 10; ++m) acc[s][m] = T(0);
-
-    const long c0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    long tt = c0 / cpf, xc = c0 - tt * cpf;
-    while (tt < nsteps) {
-        const long t = t_lo + 1 + tt;
-        const long x = off + xc * VEC;
-        const Pack<T, VEC> u = ld<T, VEC>(traj + (t - 1) * frame + x);
-        const Pack<T, VEC> v = ld<T, VEC>(traj + (t - 1) * frame + ss + x);
-        const Pack<T, VEC> au = ld<T, VEC>(adj + t * frame + x);
-        const Pack<T, VEC> av = ld<T, VEC>(adj + t * frame + ss + x);
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) {
-            const T uu = u.v[i], vv = v.v[i];
-            const T u2 = uu * uu, uv = uu * vv, v2 = vv * vv;
-            const T phi[10] = {T(1), uu, vv, u2, uv, v2, u2 * uu, u2 * vv, uu * v2, v2 * vv};
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const T gr = (s == 0 ? au.v[i] : av.v[i]) * dt;
-                acc[s][0] += gr;
-#pragma unroll
-                for (int m = 1; m < 10; ++m) acc[s][m] = fma_(gr, phi[m], acc[s][m]);
-            }
-        }
-        xc += stride_x;
-        tt += stride_t;
-        if (xc >= cpf) { xc -= cpf; ++tt; }
-    }
-    const int nwaves = blockDim.x / WAVE;
-    const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int m = 0; m < 10; ++m) {
-            const T r = wave_sum_to_last(acc[s][m]);
-            if (lane == REDUCE_LANE) red[wave * 20 + 10 * s + m] = r;
-        }
-    __syncthreads();
-    if (threadIdx.x < 20) {
-        T sum = T(0);
-        for (int w = 0; w < nwaves; ++w) sum += red[w * 20 + threadIdx.x];
-        partials[((long)blockIdx.y * rows + blockIdx.x) * NPOLY + P_W + threadIdx.x] += (double)sum;
-    }
-}
-
-// param_grad[b][idx] += sum_r partials[b * rows + r][idx]: pi_reduce_partials_kernel per sample (grid (np, B)); fixed order
-__global__ void __launch_bounds__(64)
-pi_reduce_partials_ens_kernel(const double* __restrict__ partials, int rows, int np, double* __restrict__ param_grad)
-{
-    const int idx = blockIdx.x;
-    const double* part = partials + (long)blockIdx.y * rows * np;
-    double s = 0.0;
-    for (int b = threadIdx.x; b < rows; b += WAVE) s += part[(long)b * np + idx];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, WAVE);
-    if (threadIdx.x == 0) param_grad[(long)blockIdx.y * np + idx] += s;
+    long out = idx;
+    if constexpr (ENS) out += (long)blockIdx.y * np;
+    if (threadIdx.x == 0) param_grad[out] += s;
 }
 
 }  // namespace pi

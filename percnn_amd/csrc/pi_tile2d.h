@@ -592,15 +592,21 @@ __device__ __forceinline__ void fwd_substeps(T* b0, T* b1, T* __restrict__ frame
         fwd_substeps<T, HC, K, BX, BY, NT, M + 1, LAST_STORE, GEO, WT, HALFS>(b0, b1, frames, frame_stride, g, ty0, tx0, P, geo);
 }
 
-template <typename T, int HC, int K, int BX, int BY, int NT>
+// Flavours (pi_device.h, flavour_arg), here and in pi_adj2d_tile_kernel: S... = `long sample` runs B independent trajectories
+// [T+1][B][2][*S] (frame-major) on a (tiles, B) grid -- workgroup (x, b) runs tile x on sample b: the sample's base (b * 2N) is a
+// 64-bit offset taken once, `frame_stride` (B * 2N) steps from frame t to frame t+1 of the same sample, the in-sample
+// addressing is unchanged.  R... = `int np` on top of that: one parameter block per sample, P [B][np], moved once by b * np
+// (wave-uniform: the block still arrives through scalar loads).  S sits in the middle of the list, so launch sites name it.
+template <typename T, int HC, int K, int BX, int BY, int NT, typename... S, typename... R>
 __global__ void __launch_bounds__(NT)
-pi_fwd2d_tile_kernel(T* __restrict__ frames /* frame t; t+1..t+K are written */, long frame_stride,
-                     const T* __restrict__ P, TileGeom g)
+pi_fwd2d_tile_kernel(T* __restrict__ frames /* frame t (of sample 0); t+1..t+K are written */, long frame_stride, S... sample,
+                     const T* __restrict__ P, TileGeom g, R... np)
 {
     using TL = Tile<K, BX, BY>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T* b0 = reinterpret_cast<T*>(smem_raw) + lds_pad0<T>::value;
     T* b1 = reinterpret_cast<T*>(smem_raw) + 2 * TL::PLANE + lds_pad1<T>::value;
+    if constexpr (sizeof...(S) == 1) frames += (long)blockIdx.y * flavour_arg<0>(sample...);
     const int tile = tile_of_block(blockIdx.x, g);
     const int ty0 = (tile / g.tiles_x) * BY, tx0 = (tile % g.tiles_x) * BX;
     PI_STAMP_PREV();
@@ -610,6 +616,7 @@ pi_fwd2d_tile_kernel(T* __restrict__ frames /* frame t; t+1..t+K are written */,
     // per launch of four steps -- a short launch waits for the 36 scalar loads before its first sub-step instead of under it; round 6)
     __syncthreads();
     PI_STAMP(1);
+    if constexpr (sizeof...(R) == 1) P += (long)blockIdx.y * flavour_arg<0>(np...);
     fwd_substeps<T, HC, K, BX, BY, NT, 0>(b0, b1, frames, frame_stride, g, ty0, tx0, P);
     PI_STAMP(15);
 }
@@ -1192,12 +1199,20 @@ __device__ __forceinline__ void adj_substeps(T* b0, T* b1, const T* __restrict__
                                                                         store_handover, geo, jp, hoff);
 }
 
-template <typename T, int HC, int K, int BX, int BY, int NT, bool MOM = false>
+// Flavours as pi_fwd2d_tile_kernel: S... = `long sample` (partial row blockIdx.y * gridDim.x + blockIdx.x), R... = `int rows`
+// on top (block of sample b; partial row b * rows + x, `rows` per sample and one stride for every launch of a call).
+template <typename T, int HC, int K, int BX, int BY, int NT, bool MOM = false, typename... S, typename... R>
 __global__ void __launch_bounds__(NT)
 pi_adj2d_tile_kernel(const T* __restrict__ hframe_t, const T* __restrict__ gframe_t, T* __restrict__ aframe_t,
-                     long frame_stride, unsigned inj_mask, T* __restrict__ g_h0, int steps_to_zero,
-                     double* __restrict__ partials, int np, const T* __restrict__ P, TileGeom g)
+                     long frame_stride, S... sample, unsigned inj_mask, T* __restrict__ g_h0, int steps_to_zero,
+                     double* __restrict__ partials, int np, const T* __restrict__ P, TileGeom g, R... rows)
 {
+    if constexpr (sizeof...(R) == 1) P += (long)blockIdx.y * np;
+    if constexpr (sizeof...(S) == 1) {
+        const long sbase = (long)blockIdx.y * flavour_arg<0>(sample...);   // sample blockIdx.y; partial row per (sample, tile)
+        hframe_t += sbase; gframe_t += sbase; aframe_t += sbase;
+        if (g_h0) g_h0 += sbase;
+    }
     using TL = Tile<K, BX, BY>;
     // Operand pipeline: one sub-step ahead (2 x 16 VGPRs).  Requesting ALL sub-steps' operands at kernel start was
     // measured slower (17.6 vs 15.5 us per K=4 launch: 64 extra VGPRs, requests queued ahead of the window load).
@@ -1227,337 +1242,10 @@ pi_adj2d_tile_kernel(const T* __restrict__ hframe_t, const T* __restrict__ gfram
     // 2..21 the 20 moments (row layout of the direct kernels: P_W + 10*s + m)
     const int slot = threadIdx.x < 2 ? P_COEF + (int)threadIdx.x : P_W + (int)threadIdx.x - 2;
     const bool has_slot = threadIdx.x < (MOM ? 22 : 2);
-    double* pslot = partials + (long)blockIdx.x * np + (has_slot ? slot : P_COEF);
-    const double pold = has_slot ? *pslot : 0.0;
-    StripOps<T> ops0;
-    // The strip offsets of ALL sub-steps are computed here, in the shadow of the window load (the VALU is idle for ~1 us),
-    // and pinned: inside the issue-bound sub-steps the wraps, 64-bit multiplies and shifts of the next strip's operand
-    // addresses were ~45 of ~290 VALU instructions per wave and sub-step.
-    StripAddr sa[K];
-    if constexpr (PRE) {
-        strip_addr_table<K, BX, BY, NT, 0>(sa, g, ty0, tx0);
-        adj_load_ops<T, K, BX, BY, NT, 0>(ops0, 0, hframe_t - frame_stride, inj_mask & 1u ? gframe_t - frame_stride : nullptr,
-                                          g, ty0, tx0, &sa[0]);
-    }
-    wl.commit(b0);
-    lds_barrier();                                         // LDS only: the operand loads stay in flight
-    PI_STAMP(1);
-    double acc_c[2] = {0.0, 0.0};                          // heavily cancelling sums (stencil row-sum ~ 0): fp64
-    TileMoments<T, MOM> mom;
-    if constexpr (MOM) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int m = 0; m < 10; ++m) mom.a[s][m] = typename MomAcc<T>::type{};
-    }
-    adj_substeps<T, HC, K, BX, BY, NT, 0, PRE, MOM>(b0, b1, hframe_t, gframe_t, aframe_t, frame_stride, inj_mask, g_h0,
-                                                    steps_to_zero, g, ty0, tx0, P, acc_c, ops0, mom, sa, lacc);
-    // diffusion-coefficient gradients of this tile over the K sub-steps: one reduction per launch
-    // (LDS-only barriers: the last frame's global stores need not drain first)
-    lds_barrier();
-    double* red = reinterpret_cast<double*>(smem_raw);     // state buffers are dead now
-    const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
-    constexpr int NW = NT / WAVE;
-    // red[0 .. 2*NW): per-wave coefficient sums; MOM (float32): red[2*NW .. 2*NW + 20): block totals of the moments;
-    // float scratch [20][NT + 16] behind them
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        const double r = wave_sum_to_last(acc_c[s]);
-        if (lane == REDUCE_LANE) red[wave * 2 + s] = r;
-    }
-    constexpr bool MOM_LDS = MOM && sizeof(T) == 4;        // moments through an LDS transpose (see below)
-    if constexpr (MOM_LDS) {
-        // Block-wide sums of the 20 per-thread moments through an LDS transpose: every thread writes its 20 values, then
-        // 16 lanes per moment add NT/16 values each and fold with four DPP steps.  All 8 waves of all 256 workgroups reach
-        // this tail at the same time, so its instruction count is exposed in full: the earlier 20 six-step DPP wave
-        // reductions per wave cost ~1 us of a 12.6 us launch (same finding as in pi_bwd_kernel, where removing the
-        // reduction in a timing experiment gained 1.6 us at 128^3).
-        constexpr int RS = NT + 16;                        // + 16 floats per row: 4 rows cover all 64 banks
-        T* scr = reinterpret_cast<T*>(red + 2 * NW + 20);
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int m = 0; m < 10; ++m) scr[(10 * s + m) * RS + (int)threadIdx.x] = mom_total(mom.a[s][m]);
-        lds_barrier();
-        if (threadIdx.x < 320) {                           // five whole waves: 20 moments x 16 lanes
-            const int mm = (int)threadIdx.x >> 4, part = (int)threadIdx.x & 15;
-            const T* row = scr + mm * RS + part;
-            T a0 = T(0), a1 = T(0), a2 = T(0), a3 = T(0);
-#pragma unroll
-            for (int k = 0; k < NT; k += 128) {
-                const T v0 = row[k], v1 = row[k + 16], v2 = row[k + 32], v3 = row[k + 48];
-                const T v4 = row[k + 64], v5 = row[k + 80], v6 = row[k + 96], v7 = row[k + 112];
-                a0 += v0; a1 += v1; a2 += v2; a3 += v3;
-                a0 += v4; a1 += v5; a2 += v6; a3 += v7;
-            }
-            T a = (a0 + a1) + (a2 + a3);
-            a += dpp_mov<0x111, 0xF>(a);                   // row_shr:1, :2, :4, :8 -> lane 15 of each row of 16
-            a += dpp_mov<0x112, 0xF>(a);
-            a += dpp_mov<0x114, 0xF>(a);
-            a += dpp_mov<0x118, 0xF>(a);
-            if (part == 15) red[2 * NW + mm] = (double)a;
-        }
-    } else if constexpr (MOM_LACC) {
-        // the per-lane sums already sit transposed in LDS ([moment][thread], complete: the barrier above waited for the
-        // LDS adds): 16 lanes per moment add NT/16 of them each and fold with four DPP steps
-        if (threadIdx.x < 320) {
-            const int mm = (int)threadIdx.x >> 4, part = (int)threadIdx.x & 15;
-            const double* row = lacc + mm * NT + part;
-            double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-#pragma unroll
-            for (int k = 0; k < NT; k += 64) {
-                const double v0 = row[k], v1 = row[k + 16], v2 = row[k + 32], v3 = row[k + 48];
-                a0 += v0; a1 += v1; a2 += v2; a3 += v3;
-            }
-            double a = (a0 + a1) + (a2 + a3);
-            a += dpp_mov<0x111, 0xF>(a);
-            a += dpp_mov<0x112, 0xF>(a);
-            a += dpp_mov<0x114, 0xF>(a);
-            a += dpp_mov<0x118, 0xF>(a);
-            if (part == 15) red[2 * NW + mm] = a;
-        }
-    }
-    lds_barrier();
-    if (has_slot) {
-        double sum = 0.0;
-        if (threadIdx.x < 2) {
-            for (int w = 0; w < NW; ++w) sum += red[w * 2 + threadIdx.x];
-        } else if constexpr (MOM) {
-            sum = red[2 * NW + threadIdx.x - 2];
-        }
-        *pslot = pold + sum;
-    }
-    PI_STAMP(15);
-}
-
-// ------------------------------------------------------------------------------------------------
-// BATCHED tile launches: B independent trajectories [T+1][B][2][*S] (frame-major), one parameter block.  Grid (tiles, B):
-// workgroup (x, b) runs the unbatched kernel's tile x on sample b -- the sample's base (b * 2N) is a 64-bit offset taken once,
-// `frame_stride` (B * 2N) steps from frame t to frame t+1 of the same sample, the in-sample addressing is unchanged.  The
-// forward is a shell around the same device functions as pi_fwd2d_tile_kernel; the sweep is a copy of pi_adj2d_tile_kernel
-// (partial row blockIdx.y * gridDim.x + blockIdx.x), so that the unbatched kernels' code stays exactly as it was.
-// ------------------------------------------------------------------------------------------------
-template <typename T, int HC, int K, int BX, int BY, int NT>
-__global__ void __launch_bounds__(NT)
-pi_fwd2d_tile_batch_kernel(T* __restrict__ frames /* frame t of sample 0 */, long frame_stride, long sample,
-                           const T* __restrict__ P, TileGeom g)
-{
-    using TL = Tile<K, BX, BY>;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T* b0 = reinterpret_cast<T*>(smem_raw) + lds_pad0<T>::value;
-    T* b1 = reinterpret_cast<T*>(smem_raw) + 2 * TL::PLANE + lds_pad1<T>::value;
-    T* f = frames + (long)blockIdx.y * sample;
-    const int tile = tile_of_block(blockIdx.x, g);
-    const int ty0 = (tile / g.tiles_x) * BY, tx0 = (tile % g.tiles_x) * BX;
-    tile_load<T, K, BX, BY, NT>(f, g, ty0, tx0, b0);
-    __syncthreads();
-    fwd_substeps<T, HC, K, BX, BY, NT, 0>(b0, b1, f, frame_stride, g, ty0, tx0, P);
-}
-
-template <typename T, int HC, int K, int BX, int BY, int NT, bool MOM = false>
-__global__ void __launch_bounds__(NT)
-pi_adj2d_tile_batch_kernel(const T* __restrict__ hframe_t, const T* __restrict__ gframe_t, T* __restrict__ aframe_t,
-                           long frame_stride, long sample, unsigned inj_mask, T* __restrict__ g_h0, int steps_to_zero,
-                           double* __restrict__ partials, int np, const T* __restrict__ P, TileGeom g)
-{
-    const long sbase = (long)blockIdx.y * sample;  // sample blockIdx.y; partial row per (sample, tile)
-    hframe_t += sbase; gframe_t += sbase; aframe_t += sbase;
-    if (g_h0) g_h0 += sbase;
-    using TL = Tile<K, BX, BY>;
-    // Operand pipeline: one sub-step ahead (2 x 16 VGPRs).  Requesting ALL sub-steps' operands at kernel start was
-    // measured slower (17.6 vs 15.5 us per K=4 launch: 64 extra VGPRs, requests queued ahead of the window load).
-    // (the float64 fused-moments flavour gives the operand pipeline's 32 registers to its 20 accumulators: with both it
-    // needs ~270 of the 256 registers a 512-thread workgroup can have and spills -- 20 -> 47 us per launch, measured)
-    constexpr bool PRE = PI_TILE_ADJ_PIPE && TL::region_n(0) / 4 <= NT;
-    constexpr bool MOM_LACC = MOM && sizeof(T) == 8;       // float64: per-lane moment accumulators in LDS (adj_substep)
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T* b0 = reinterpret_cast<T*>(smem_raw) + lds_pad0<T>::value;
-    T* b1 = reinterpret_cast<T*>(smem_raw) + 2 * TL::PLANE + lds_pad1<T>::value;
-    const int tile = tile_of_block(blockIdx.x, g);
-    const int ty0 = (tile / g.tiles_x) * BY, tx0 = (tile % g.tiles_x) * BX;
-    // [20][NT] doubles behind the state buffers (not aliased: they live through all sub-steps)
-    double* lacc = MOM_LACC ? reinterpret_cast<double*>(smem_raw + tile_state_bytes<T, K, BX, BY>()) : nullptr;
-    PI_STAMP_PREV();
-    PI_STAMP(0);
-    WindowLoader<T, K, BX, BY, NT> wl;
-    wl.issue(aframe_t, g, ty0, tx0);                       // adjoint window first, then the operands of sub-step 0
-    if constexpr (MOM_LACC) {
-#pragma unroll
-        for (int m = 0; m < 20; ++m) lacc[m * NT + (int)threadIdx.x] = 0.0;
-    }
-    // running diffusion-coefficient partial of this tile: requested now, needed at the very end (was a dependent
-    // load -> add -> store at the end of every launch: 1 us)
-    static_assert(!MOM || HC == POLY, "fused moments: pre-contracted blocks");
-    // slots of the partial row this thread updates at the end: threads 0,1 the two coefficient sums, MOM: threads
-    // 2..21 the 20 moments (row layout of the direct kernels: P_W + 10*s + m)
-    const int slot = threadIdx.x < 2 ? P_COEF + (int)threadIdx.x : P_W + (int)threadIdx.x - 2;
-    const bool has_slot = threadIdx.x < (MOM ? 22 : 2);
-    double* pslot = partials + ((long)blockIdx.y * gridDim.x + blockIdx.x) * np + (has_slot ? slot : P_COEF);
-    const double pold = has_slot ? *pslot : 0.0;
-    StripOps<T> ops0;
-    // The strip offsets of ALL sub-steps are computed here, in the shadow of the window load (the VALU is idle for ~1 us),
-    // and pinned: inside the issue-bound sub-steps the wraps, 64-bit multiplies and shifts of the next strip's operand
-    // addresses were ~45 of ~290 VALU instructions per wave and sub-step.
-    StripAddr sa[K];
-    if constexpr (PRE) {
-        strip_addr_table<K, BX, BY, NT, 0>(sa, g, ty0, tx0);
-        adj_load_ops<T, K, BX, BY, NT, 0>(ops0, 0, hframe_t - frame_stride, inj_mask & 1u ? gframe_t - frame_stride : nullptr,
-                                          g, ty0, tx0, &sa[0]);
-    }
-    wl.commit(b0);
-    lds_barrier();                                         // LDS only: the operand loads stay in flight
-    PI_STAMP(1);
-    double acc_c[2] = {0.0, 0.0};                          // heavily cancelling sums (stencil row-sum ~ 0): fp64
-    TileMoments<T, MOM> mom;
-    if constexpr (MOM) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int m = 0; m < 10; ++m) mom.a[s][m] = typename MomAcc<T>::type{};
-    }
-    adj_substeps<T, HC, K, BX, BY, NT, 0, PRE, MOM>(b0, b1, hframe_t, gframe_t, aframe_t, frame_stride, inj_mask, g_h0,
-                                                    steps_to_zero, g, ty0, tx0, P, acc_c, ops0, mom, sa, lacc);
-    // diffusion-coefficient gradients of this tile over the K sub-steps: one reduction per launch
-    // (LDS-only barriers: the last frame's global stores need not drain first)
-    lds_barrier();
-    double* red = reinterpret_cast<double*>(smem_raw);     // state buffers are dead now
-    const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
-    constexpr int NW = NT / WAVE;
-    // red[0 .. 2*NW): per-wave coefficient sums; MOM (float32): red[2*NW .. 2*NW + 20): block totals of the moments;
-    // float scratch [20][NT + 16] behind them
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        const double r = wave_sum_to_last(acc_c[s]);
-        if (lane == REDUCE_LANE) red[wave * 2 + s] = r;
-    }
-    constexpr bool MOM_LDS = MOM && sizeof(T) == 4;        // moments through an LDS transpose (see below)
-    if constexpr (MOM_LDS) {
-        // Block-wide sums of the 20 per-thread moments through an LDS transpose: every thread writes its 20 values, then
-        // 16 lanes per moment add NT/16 values each and fold with four DPP steps.  All 8 waves of all 256 workgroups reach
-        // this tail at the same time, so its instruction count is exposed in full: the earlier 20 six-step DPP wave
-        // reductions per wave cost ~1 us of a 12.6 us launch (same finding as in pi_bwd_kernel, where removing the
-        // reduction in a timing experiment gained 1.6 us at 128^3).
-        constexpr int RS = NT + 16;                        // + 16 floats per row: 4 rows cover all 64 banks
-        T* scr = reinterpret_cast<T*>(red + 2 * NW + 20);
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int m = 0; m < 10; ++m) scr[(10 * s + m) * RS + (int)threadIdx.x] = mom_total(mom.a[s][m]);
-        lds_barrier();
-        if (threadIdx.x < 320) {                           // five whole waves: 20 moments x 16 lanes
-            const int mm = (int)threadIdx.x >> 4, part = (int)threadIdx.x & 15;
-            const T* row = scr + mm * RS + part;
-            T a0 = T(0), a1 = T(0), a2 = T(0), a3 = T(0);
-#pragma unroll
-            for (int k = 0; k < NT; k += 128) {
-                const T v0 = row[k], v1 = row[k + 16], v2 = row[k + 32], v3 = row[k + 48];
-                const T v4 = row[k + 64], v5 = row[k + 80], v6 = row[k + 96], v7 = row[k + 112];
-                a0 += v0; a1 += v1; a2 += v2; a3 += v3;
-                a0 += v4; a1 += v5; a2 += v6; a3 += v7;
-            }
-            T a = (a0 + a1) + (a2 + a3);
-            a += dpp_mov<0x111, 0xF>(a);                   // row_shr:1, :2, :4, :8 -> lane 15 of each row of 16
-            a += dpp_mov<0x112, 0xF>(a);
-            a += dpp_mov<0x114, 0xF>(a);
-            a += dpp_mov<0x118, 0xF>(a);
-            if (part == 15) red[2 * NW + mm] = (double)a;
-        }
-    } else if constexpr (MOM_LACC) {
-        // the per-lane sums already sit transposed in LDS ([moment][thread], complete: the barrier above waited for the
-        // LDS adds): 16 lanes per moment add NT/16 of them each and fold with four DPP steps
-        if (threadIdx.x < 320) {
-            const int mm = (int)threadIdx.x >> 4, part = (int)threadIdx.x & 15;
-            const double* row = lacc + mm * NT + part;
-            double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-#pragma unroll
-            for (int k = 0; k < NT; k += 64) {
-                const double v0 = row[k], v1 = row[k + 16], v2 = row[k + 32], v3 = row[k + 48];
-                a0 += v0; a1 += v1; a2 += v2; a3 += v3;
-            }
-            double a = (a0 + a1) + (a2 + a3);
-            a += dpp_mov<0x111, 0xF>(a);
-            a += dpp_mov<0x112, 0xF>(a);
-            a += dpp_mov<0x114, 0xF>(a);
-            a += dpp_mov<0x118, 0xF>(a);
-            if (part == 15) red[2 * NW + mm] = a;
-        }
-    }
-    lds_barrier();
-    if (has_slot) {
-        double sum = 0.0;
-        if (threadIdx.x < 2) {
-            for (int w = 0; w < NW; ++w) sum += red[w * 2 + threadIdx.x];
-        } else if constexpr (MOM) {
-            sum = red[2 * NW + threadIdx.x - 2];
-        }
-        *pslot = pold + sum;
-    }
-    PI_STAMP(15);
-}
-
-// ------------------------------------------------------------------------------------------------
-// ENSEMBLE tile launches: the batched launches above with one parameter block per sample, P [B][np].  Workgroup (x, b)
-// moves P once by b * np (wave-uniform: the block still arrives through scalar loads); the sweep's partial row is
-// b * rows + x, `rows` per sample and one stride for every launch of a call.  Copies, so that the batched kernels' code
-// stays exactly as it was.
-// ------------------------------------------------------------------------------------------------
-template <typename T, int HC, int K, int BX, int BY, int NT>
-__global__ void __launch_bounds__(NT)
-pi_fwd2d_tile_ens_kernel(T* __restrict__ frames /* frame t of sample 0 */, long frame_stride, long sample,
-                           const T* __restrict__ P, TileGeom g, int np)
-{
-    using TL = Tile<K, BX, BY>;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T* b0 = reinterpret_cast<T*>(smem_raw) + lds_pad0<T>::value;
-    T* b1 = reinterpret_cast<T*>(smem_raw) + 2 * TL::PLANE + lds_pad1<T>::value;
-    T* f = frames + (long)blockIdx.y * sample;
-    const int tile = tile_of_block(blockIdx.x, g);
-    const int ty0 = (tile / g.tiles_x) * BY, tx0 = (tile % g.tiles_x) * BX;
-    tile_load<T, K, BX, BY, NT>(f, g, ty0, tx0, b0);
-    __syncthreads();
-    fwd_substeps<T, HC, K, BX, BY, NT, 0>(b0, b1, f, frame_stride, g, ty0, tx0, P + (long)blockIdx.y * np);
-}
-
-template <typename T, int HC, int K, int BX, int BY, int NT, bool MOM = false>
-__global__ void __launch_bounds__(NT)
-pi_adj2d_tile_ens_kernel(const T* __restrict__ hframe_t, const T* __restrict__ gframe_t, T* __restrict__ aframe_t,
-                           long frame_stride, long sample, unsigned inj_mask, T* __restrict__ g_h0, int steps_to_zero,
-                           double* __restrict__ partials, int np, const T* __restrict__ P, TileGeom g, int rows)
-{
-    const long sbase = (long)blockIdx.y * sample;  // sample blockIdx.y: its block, partial row blockIdx.y * rows + tile
-    P += (long)blockIdx.y * np;
-    hframe_t += sbase; gframe_t += sbase; aframe_t += sbase;
-    if (g_h0) g_h0 += sbase;
-    using TL = Tile<K, BX, BY>;
-    // Operand pipeline: one sub-step ahead (2 x 16 VGPRs).  Requesting ALL sub-steps' operands at kernel start was
-    // measured slower (17.6 vs 15.5 us per K=4 launch: 64 extra VGPRs, requests queued ahead of the window load).
-    // (the float64 fused-moments flavour gives the operand pipeline's 32 registers to its 20 accumulators: with both it
-    // needs ~270 of the 256 registers a 512-thread workgroup can have and spills -- 20 -> 47 us per launch, measured)
-    constexpr bool PRE = PI_TILE_ADJ_PIPE && TL::region_n(0) / 4 <= NT;
-    constexpr bool MOM_LACC = MOM && sizeof(T) == 8;       // float64: per-lane moment accumulators in LDS (adj_substep)
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T* b0 = reinterpret_cast<T*>(smem_raw) + lds_pad0<T>::value;
-    T* b1 = reinterpret_cast<T*>(smem_raw) + 2 * TL::PLANE + lds_pad1<T>::value;
-    const int tile = tile_of_block(blockIdx.x, g);
-    const int ty0 = (tile / g.tiles_x) * BY, tx0 = (tile % g.tiles_x) * BX;
-    // [20][NT] doubles behind the state buffers (not aliased: they live through all sub-steps)
-    double* lacc = MOM_LACC ? reinterpret_cast<double*>(smem_raw + tile_state_bytes<T, K, BX, BY>()) : nullptr;
-    PI_STAMP_PREV();
-    PI_STAMP(0);
-    WindowLoader<T, K, BX, BY, NT> wl;
-    wl.issue(aframe_t, g, ty0, tx0);                       // adjoint window first, then the operands of sub-step 0
-    if constexpr (MOM_LACC) {
-#pragma unroll
-        for (int m = 0; m < 20; ++m) lacc[m * NT + (int)threadIdx.x] = 0.0;
-    }
-    // running diffusion-coefficient partial of this tile: requested now, needed at the very end (was a dependent
-    // load -> add -> store at the end of every launch: 1 us)
-    static_assert(!MOM || HC == POLY, "fused moments: pre-contracted blocks");
-    // slots of the partial row this thread updates at the end: threads 0,1 the two coefficient sums, MOM: threads
-    // 2..21 the 20 moments (row layout of the direct kernels: P_W + 10*s + m)
-    const int slot = threadIdx.x < 2 ? P_COEF + (int)threadIdx.x : P_W + (int)threadIdx.x - 2;
-    const bool has_slot = threadIdx.x < (MOM ? 22 : 2);
-    double* pslot = partials + ((long)blockIdx.y * rows + blockIdx.x) * np + (has_slot ? slot : P_COEF);
+    long row = blockIdx.x;
+    if constexpr (sizeof...(R) == 1) row = (long)blockIdx.y * flavour_arg<0>(rows...) + blockIdx.x;
+    else if constexpr (sizeof...(S) == 1) row = (long)blockIdx.y * gridDim.x + blockIdx.x;
+    double* pslot = partials + row * np + (has_slot ? slot : P_COEF);
     const double pold = has_slot ? *pslot : 0.0;
     StripOps<T> ops0;
     // The strip offsets of ALL sub-steps are computed here, in the shadow of the window load (the VALU is idle for ~1 us),
