@@ -678,6 +678,46 @@ int percnn_pi_ensemble_rollout_bwd_f64(const double *traj, const double *g_traj,
                                        const double *params, int hc, int ndim, const int64_t *shape, int batch, int T,
                                        const char *options, void *stream);
 
+/* ---- Losses per sample: the squared-error losses above for a batch / an ensemble ----------------------------------------------
+ * Each sample of a batch (or member of an ensemble) has a loss of its own and an upstream gradient of its own:
+ *   L_b = scale' * sum_{t : frame_mask[t]} sum_x (traj_t[b] - target_t[b])^2 ,   dL/dh_t[b] = a_b * (h_t[b] - target_t[b]),
+ *   a_b = scale * dev_scale[b]        (scale = 2 * scale'; dev_scale: B device elements of the compute type, NULL = all 1)
+ * formed inside the batched / ensemble sweep from the states it reads anyway: no dL/dtraj buffer [T+1][B][2][*S].
+ *   traj, target   [T+1][B][2][*S] frame-major (target NULL = 0; frames outside frame_mask are never read)
+ *   g_h0           [B][2][*S]       param_grad: batch: ONE block, the sum over the samples; ensemble: double [B][np], one row each
+ * Workspace, params, options: those of percnn_pi_{batch,ensemble}_rollout_bwd_*.  Every adjoint field of sample b is bit-identical
+ * to percnn_pi_rollout_bwd_sqerr_* on that sample alone with dev_scale = &dev_scale[b], and to the batched / ensemble sweep on
+ * the materialised gradient.  A loss over frame 0 alone (or T = 0) writes g_h0 = a_b * (h0 - target_0).
+ * percnn_pi_batch_traj_sqerr_*: out[b] = scale * sum_{f < nframes : frame_mask[f]} sum_x (traj_f[b] - target_f[b])^2, B elements of
+ * the compute type, float64 accumulation in a fixed order (bit-identical from run to run); workspace >=
+ * percnn_pi_batch_traj_sqerr_workspace_bytes(batch) bytes, 8-byte aligned (0 for an invalid batch).
+ * Validation before any launch: NULL pointers, an output that aliases an input, batch < 1 (or > 65535), hc == -1 or bad options
+ * -> PERCNN_PI_EINVAL; a workspace that is too small -> PERCNN_PI_EWORKSPACE.  batch == 1 is the unbatched entry point
+ * (percnn_pi_rollout_bwd_sqerr_* / percnn_pi_traj_sqerr_*; the ensemble's on params[0]). */
+size_t percnn_pi_batch_traj_sqerr_workspace_bytes(int batch);
+int percnn_pi_batch_traj_sqerr_f32(const float *traj, const float *target, const unsigned char *frame_mask, int nframes,
+                                   int ndim, const int64_t *shape, int batch, double scale, float *out, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+int percnn_pi_batch_traj_sqerr_f64(const double *traj, const double *target, const unsigned char *frame_mask, int nframes,
+                                   int ndim, const int64_t *shape, int batch, double scale, double *out, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+int percnn_pi_batch_rollout_bwd_sqerr_f32(const float *traj, const float *target, const unsigned char *frame_mask,
+                                          double scale, const float *dev_scale, float *g_h0, double *param_grad,
+                                          void *workspace, size_t workspace_bytes, const float *params, int hc, int ndim,
+                                          const int64_t *shape, int batch, int T, const char *options, void *stream);
+int percnn_pi_batch_rollout_bwd_sqerr_f64(const double *traj, const double *target, const unsigned char *frame_mask,
+                                          double scale, const double *dev_scale, double *g_h0, double *param_grad,
+                                          void *workspace, size_t workspace_bytes, const double *params, int hc, int ndim,
+                                          const int64_t *shape, int batch, int T, const char *options, void *stream);
+int percnn_pi_ensemble_rollout_bwd_sqerr_f32(const float *traj, const float *target, const unsigned char *frame_mask,
+                                          double scale, const float *dev_scale, float *g_h0, double *param_grad,
+                                          void *workspace, size_t workspace_bytes, const float *params, int hc, int ndim,
+                                          const int64_t *shape, int batch, int T, const char *options, void *stream);
+int percnn_pi_ensemble_rollout_bwd_sqerr_f64(const double *traj, const double *target, const unsigned char *frame_mask,
+                                          double scale, const double *dev_scale, double *g_h0, double *param_grad,
+                                          void *workspace, size_t workspace_bytes, const double *params, int hc, int ndim,
+                                          const int64_t *shape, int batch, int T, const char *options, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -66,7 +66,9 @@ EXPORTS = [
                 "residual_bwd", "contract_fwd", "contract_bwd", "step_fwd_opt", "step_bwd_opt", "rollout_fwd_opt",
                 "rollout_bwd_opt", "rollout_bwd_sqerr", "traj_sqerr", "step_bwd_rows", "bwd_rows_finish", "rollout_bwd_top",
                 "batch_step_fwd", "batch_step_bwd", "batch_rollout_fwd", "batch_rollout_bwd", "ensemble_step_fwd",
-                "ensemble_step_bwd", "ensemble_rollout_fwd", "ensemble_rollout_bwd")] + [
+                "ensemble_step_bwd", "ensemble_rollout_fwd", "ensemble_rollout_bwd", "batch_traj_sqerr",
+                "batch_rollout_bwd_sqerr", "ensemble_rollout_bwd_sqerr")] + [
+    "percnn_pi_batch_traj_sqerr_workspace_bytes",
     "percnn_pi_batch_bwd_workspace_bytes", "percnn_pi_batch_rollout_bwd_workspace_bytes",
     "percnn_pi_ensemble_bwd_workspace_bytes", "percnn_pi_ensemble_rollout_bwd_workspace_bytes",
     "percnn_pi_s1_param_count", "percnn_pi_s1_step_fwd_f32", "percnn_pi_s1_rollout_fwd_f32",
@@ -264,6 +266,14 @@ def lib() -> ctypes.CDLL:
         f.restype, f.argtypes = ci, [vp, vp, ci, ci, i64p, ci, ci, cs, vp]
         f = getattr(L, f"percnn_pi_ensemble_rollout_bwd_{suf}")
         f.restype, f.argtypes = ci, [vp, vp, cs, vp, vp, vp, sz, vp, ci, ci, i64p, ci, ci, cs, vp]
+        f = getattr(L, f"percnn_pi_batch_traj_sqerr_{suf}")
+        f.restype, f.argtypes = ci, [vp, vp, cs, ci, ci, i64p, ci, cd, vp, vp, sz, vp]
+        f = getattr(L, f"percnn_pi_batch_rollout_bwd_sqerr_{suf}")
+        f.restype, f.argtypes = ci, [vp, vp, cs, cd, vp, vp, vp, vp, sz, vp, ci, ci, i64p, ci, ci, cs, vp]
+        f = getattr(L, f"percnn_pi_ensemble_rollout_bwd_sqerr_{suf}")
+        f.restype, f.argtypes = ci, [vp, vp, cs, cd, vp, vp, vp, vp, sz, vp, ci, ci, i64p, ci, ci, cs, vp]
+    L.percnn_pi_batch_traj_sqerr_workspace_bytes.restype = sz
+    L.percnn_pi_batch_traj_sqerr_workspace_bytes.argtypes = [ci]
     L.percnn_pi_batch_bwd_workspace_bytes.restype = sz
     L.percnn_pi_batch_bwd_workspace_bytes.argtypes = [ci, ci, i64p, ci, ci]
     L.percnn_pi_batch_rollout_bwd_workspace_bytes.restype = sz

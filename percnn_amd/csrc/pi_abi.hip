@@ -2959,16 +2959,54 @@ int batch_rollout_fwd_impl(T* traj, const T* P, int hc, int ndim, const int64_t*
     return 0;
 }
 
+// loss form of the batched / ensemble sweeps (pi::LossInj; `dev` holds one factor per sample): frame [B][2][*S] of the loss
+// gradient, dst[b] = a_b * (h[b] - target[b]) (target == nullptr: a_b * h[b]) -- the top frame of the sweep, which no later
+// step injects, and dL/dh0 of a loss over frame 0 alone
+template <typename T>
+hipError_t loss_grad_frame_b(const T* h, const T* target, T* dst, const Problem& p, int batch, hipStream_t st)
+{
+    const size_t sample = (size_t)2 * p.n;
+    const bool v16 = sample % pi::vec_width<T>::value == 0 && (sample * sizeof(T)) % 16 == 0 &&
+                     reinterpret_cast<uintptr_t>(h) % 16 == 0 && reinterpret_cast<uintptr_t>(dst) % 16 == 0 &&
+                     (!target || reinterpret_cast<uintptr_t>(target) % 16 == 0);
+    const unsigned nb = (unsigned)std::min<size_t>(2048, (sample + 1023) / 1024);
+    if (v16) hipLaunchKernelGGL((pi::pi_loss_grad_kernel<T, pi::vec_width<T>::value, long>), dim3(nb, (unsigned)batch), dim3(256), 0, st,
+                                h, target, dst, (long)sample, p.loss, (long)sample);
+    else     hipLaunchKernelGGL((pi::pi_loss_grad_kernel<T, 1, long>), dim3(nb, (unsigned)batch), dim3(256), 0, st,
+                                h, target, dst, (long)sample, p.loss, (long)sample);
+    return hipGetLastError();
+}
+
+// loss != nullptr (both sweeps below, as rollout_bwd_impl): no dL/dtraj exists; `g_traj` is the TARGET trajectory [T+1][B][2][*S]
+// (mode 2) or ignored (mode 1), `mask` selects the frames inside the loss and loss->dev holds B factors
+int sweep_loss_form(const pi::LossInj* loss, const void* traj, const void*& g_traj, Problem& p)
+{
+    if (!loss) return 0;
+    if ((loss->mode != 1 && loss->mode != 2) || (loss->mode == 2 && !g_traj)) return PERCNN_PI_EINVAL;
+    p.loss = *loss;
+    if (p.loss.mode == 1) g_traj = traj;
+    return 0;
+}
+
 template <typename T>
 int batch_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* mask, T* g_h0, double* param_grad, void* ws,
                            size_t ws_bytes, const T* P, int hc, int ndim, const int64_t* shape, int batch, int T_steps,
-                           const char* options, void* stream)
+                           const char* options, void* stream, const pi::LossInj* loss = nullptr)
 {
     if (batch == 1)
-        return rollout_bwd_impl<T>(traj, g_traj, mask, g_h0, param_grad, ws, ws_bytes, P, hc, ndim, shape, T_steps, stream, options);
+        return rollout_bwd_impl<T>(traj, g_traj, mask, g_h0, param_grad, ws, ws_bytes, P, hc, ndim, shape, T_steps, stream, options,
+                                   loss);
     Problem p;
     if (int rc = batch_problem(hc, ndim, shape, batch, p, options)) return rc;
+    {
+        const void* gt = g_traj;
+        if (int rc = sweep_loss_form(loss, traj, gt, p)) return rc;
+        g_traj = static_cast<const T*>(gt);
+    }
     if (!traj || !g_traj || !g_h0 || !param_grad || !P || T_steps < 0) return PERCNN_PI_EINVAL;
+    // loss form: dL/dh0 is written while the trajectory, the target and the factors are still being read
+    if (loss && (g_h0 == traj || g_h0 == g_traj || g_h0 == P || (const void*)g_h0 == loss->dev || (const void*)param_grad == loss->dev))
+        return PERCNN_PI_EINVAL;
     if (!ws || ws_bytes < batch_rollout_workspace_bytes(p, batch, T_steps, sizeof(T)) || (reinterpret_cast<uintptr_t>(ws) % 16))
         return PERCNN_PI_EWORKSPACE;
     auto st = static_cast<hipStream_t>(stream);
@@ -2982,19 +3020,24 @@ int batch_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* 
     auto has = [&](int t) { return !mask || mask[t]; };
     int t_top = T_steps;
     while (t_top > 0 && !has(t_top)) --t_top;
+    // dL/dh of one frame that no later step injects (the top frame): a copy, or -- loss form -- a_b * (h - target)
+    auto top_frame = [&](int t, T* dst) -> hipError_t {
+        if (!loss) return hipMemcpyAsync(dst, g_traj + (size_t)t * frame, frame_bytes, hipMemcpyDeviceToDevice, st);
+        return loss_grad_frame_b<T>(traj + (size_t)t * frame, p.loss.mode == 2 ? g_traj + (size_t)t * frame : nullptr, dst, p, batch, st);
+    };
     if (t_top == 0) {
-        if (has(0)) return (int)hipMemcpyAsync(g_h0, g_traj, frame_bytes, hipMemcpyDeviceToDevice, st);
+        if (has(0)) return (int)top_frame(0, g_h0);
         return (int)hipMemsetAsync(g_h0, 0, frame_bytes, st);
     }
     if (hipError_t e = hipMemsetAsync(w.partials, 0, w.partials_bytes, st)) return (int)e;
     const bool tile = batch_tile<T>(p, batch, {traj, g_traj, g_h0, adj}, true);
     const bool fuse = tile ? tile_fuse_ok<T>(p)
                            : (!p.opt.skip_wgrad && (p.opt.fuse_wgrad == 1 || (p.opt.fuse_wgrad == 2 && hc == 0)));
-    // (the direct sweep with fused sums reads the top frame's dL/dtraj where it lies, as rollout_bwd_impl does)
-    const T* top_in_place = (!tile && fuse) ? g_traj + (size_t)t_top * frame : nullptr;
+    // (the direct sweep with fused sums reads the top frame's dL/dtraj where it lies, as rollout_bwd_impl does; in loss form
+    // there is no such frame to read)
+    const T* top_in_place = (!tile && fuse && !loss) ? g_traj + (size_t)t_top * frame : nullptr;
     if (!top_in_place)
-        if (hipError_t e = hipMemcpyAsync(adj + (size_t)t_top * frame, g_traj + (size_t)t_top * frame, frame_bytes,
-                                          hipMemcpyDeviceToDevice, st)) return (int)e;
+        if (hipError_t e = top_frame(t_top, adj + (size_t)t_top * frame)) return (int)e;
     unsigned rows = 0;
     int t_cur = t_top;
     if (tile) {
@@ -3172,14 +3215,22 @@ int ens_rollout_fwd_impl(T* traj, const T* P, int hc, int ndim, const int64_t* s
 template <typename T>
 int ens_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* mask, T* g_h0, double* param_grad, void* ws,
                          size_t ws_bytes, const T* P, int hc, int ndim, const int64_t* shape, int batch, int T_steps,
-                         const char* options, void* stream)
+                         const char* options, void* stream, const pi::LossInj* loss = nullptr)
 {
     Problem p;
     if (int rc = ens_problem(hc, ndim, shape, batch, p, options)) return rc;
+    const T* const target = g_traj;                        // (loss form, mode 1: g_traj becomes traj below)
+    {
+        const void* gt = g_traj;
+        if (int rc = sweep_loss_form(loss, traj, gt, p)) return rc;
+        g_traj = static_cast<const T*>(gt);
+    }
     if (!traj || !g_traj || !g_h0 || !param_grad || !P || T_steps < 0 || g_h0 == traj || g_h0 == g_traj || g_h0 == P)
         return PERCNN_PI_EINVAL;
+    if (loss && ((const void*)g_h0 == loss->dev || (const void*)param_grad == loss->dev)) return PERCNN_PI_EINVAL;
     if (batch == 1)
-        return rollout_bwd_impl<T>(traj, g_traj, mask, g_h0, param_grad, ws, ws_bytes, P, hc, ndim, shape, T_steps, stream, options);
+        return rollout_bwd_impl<T>(traj, loss ? target : g_traj, mask, g_h0, param_grad, ws, ws_bytes, P, hc, ndim, shape, T_steps, stream,
+                                   options, loss);
     if (!ws || ws_bytes < batch_rollout_workspace_bytes(p, batch, T_steps, sizeof(T)) || (reinterpret_cast<uintptr_t>(ws) % 16))
         return PERCNN_PI_EWORKSPACE;
     auto st = static_cast<hipStream_t>(stream);
@@ -3190,8 +3241,12 @@ int ens_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* ma
     auto has = [&](int t) { return !mask || mask[t]; };
     int t_top = T_steps;
     while (t_top > 0 && !has(t_top)) --t_top;
+    auto top_frame = [&](int t, T* dst) -> hipError_t {     // as in batch_rollout_bwd_impl
+        if (!loss) return hipMemcpyAsync(dst, g_traj + (size_t)t * frame, frame_bytes, hipMemcpyDeviceToDevice, st);
+        return loss_grad_frame_b<T>(traj + (size_t)t * frame, p.loss.mode == 2 ? g_traj + (size_t)t * frame : nullptr, dst, p, batch, st);
+    };
     if (t_top == 0) {
-        if (has(0)) return (int)hipMemcpyAsync(g_h0, g_traj, frame_bytes, hipMemcpyDeviceToDevice, st);
+        if (has(0)) return (int)top_frame(0, g_h0);
         return (int)hipMemsetAsync(g_h0, 0, frame_bytes, st);
     }
     const bool tile = batch_tile<T>(p, batch, {traj, g_traj, g_h0, adj}, true);
@@ -3200,11 +3255,10 @@ int ens_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* ma
     const bool pass = !p.opt.skip_wgrad && !fuse;          // time-parallel gradient pass after the sweep
     const int rows = ens_rows_for<T>(p, batch, tile, pass ? t_top : 0);
     if (hipError_t e = hipMemsetAsync(partials, 0, (size_t)batch * rows * pi::nparams(hc) * sizeof(double), st)) return (int)e;
-    // (the direct sweep with fused sums reads the top frame's dL/dtraj where it lies, as rollout_bwd_impl does)
-    const T* top_in_place = (!tile && fuse) ? g_traj + (size_t)t_top * frame : nullptr;
+    // (the direct sweep with fused sums reads the top frame's dL/dtraj where it lies, as rollout_bwd_impl does; not in loss form)
+    const T* top_in_place = (!tile && fuse && !loss) ? g_traj + (size_t)t_top * frame : nullptr;
     if (!top_in_place)
-        if (hipError_t e = hipMemcpyAsync(adj + (size_t)t_top * frame, g_traj + (size_t)t_top * frame, frame_bytes,
-                                          hipMemcpyDeviceToDevice, st)) return (int)e;
+        if (hipError_t e = top_frame(t_top, adj + (size_t)t_top * frame)) return (int)e;
     int t_cur = t_top;
     if (tile) {
         const int K = (p.opt.tile_k == 8 && p.hc != 0) ? 4 : p.opt.tile_k;
@@ -3653,6 +3707,55 @@ int sqerr_impl(const T* traj, const T* target, const unsigned char* mask, int nf
         f = g;
     }
     hipLaunchKernelGGL((pi::pi_sqerr_finish_kernel<T>), dim3(1), dim3(64), 0, st, partials, (int)NB, scale, out);
+    return (int)hipGetLastError();
+}
+
+// partial slots per sample of the batched loss value: about 1024 workgroups over the whole batch, as the unbatched pass has
+unsigned batch_sqerr_slots(int batch) { return (unsigned)std::max(8, 1024 / batch); }
+
+// out[b] = scale * sum over the frames with mask[f] != 0 of sum_x (traj[f][b] - target[f][b])^2, traj / target [nframes][B][2][*S]:
+// per run of selected frames one launch of grid (nb, B) that adds to the slots of each sample alone (launches of one stream are
+// ordered and nb is a function of the arguments: bit-identical from run to run), then one wave per sample sums its slots
+template <typename T>
+int batch_sqerr_impl(const T* traj, const T* target, const unsigned char* mask, int nframes, int ndim, const int64_t* shape,
+                     int batch, double scale, T* out, void* ws, size_t ws_bytes, void* stream)
+{
+    if (batch < 1 || batch > MAX_BATCH) return PERCNN_PI_EINVAL;
+    if (batch == 1) return sqerr_impl<T>(traj, target, mask, nframes, ndim, shape, scale, out, ws, ws_bytes, stream);
+    Problem p;
+    if (int rc = batch_problem(0, ndim, shape, batch, p, nullptr, false)) return rc;
+    if (!traj || !out || nframes < 0 || out == traj || out == target) return PERCNN_PI_EINVAL;
+    const unsigned slots = batch_sqerr_slots(batch);
+    if (!ws || ws_bytes < (size_t)batch * slots * sizeof(double) || reinterpret_cast<uintptr_t>(ws) % 8) return PERCNN_PI_EWORKSPACE;
+    auto st = static_cast<hipStream_t>(stream);
+    const long sample = 2 * p.n, frame = (long)batch * sample;
+    double* partials = static_cast<double*>(ws);
+    if (hipError_t e = hipMemsetAsync(partials, 0, (size_t)batch * slots * sizeof(double), st)) return (int)e;
+    const bool v16 = sample % pi::vec_width<T>::value == 0 && (sample * sizeof(T)) % 16 == 0 &&
+                     reinterpret_cast<uintptr_t>(traj) % 16 == 0 && (!target || reinterpret_cast<uintptr_t>(target) % 16 == 0);
+    unsigned used = 1;                                     // slots of a sample that any launch wrote
+    int f = 0;
+    while (f < nframes) {
+        while (f < nframes && mask && !mask[f]) ++f;
+        int g = f;
+        while (g < nframes && (!mask || mask[g])) ++g;
+        if (g > f) {
+            const T* tr = traj + (size_t)f * frame;
+            const T* tg = target ? target + (size_t)f * frame : nullptr;
+            // a workgroup per 1024 chunks of the sample's part of the run (four per lane), at most the sample's slots
+            const long chunks = (long)(g - f) * (sample / (v16 ? pi::vec_width<T>::value : 1));
+            const unsigned nb = (unsigned)std::min<long>(slots, (chunks + 1023) / 1024);
+            if (nb > used) used = nb;
+            if (v16) hipLaunchKernelGGL((pi::pi_sqerr_kernel<T, pi::vec_width<T>::value, long, int, int>), dim3(nb, (unsigned)batch), dim3(256),
+                                        0, st, tr, tg, sample, partials, frame, g - f, (int)slots);
+            else     hipLaunchKernelGGL((pi::pi_sqerr_kernel<T, 1, long, int, int>), dim3(nb, (unsigned)batch), dim3(256), 0, st, tr, tg,
+                                        sample, partials, frame, g - f, (int)slots);
+            if (hipError_t e = hipGetLastError()) return (int)e;
+        }
+        f = g;
+    }
+    hipLaunchKernelGGL((pi::pi_sqerr_finish_kernel<T, int>), dim3((unsigned)batch), dim3(64), 0, st, partials, (int)used, scale, out,
+                       (int)slots);
     return (int)hipGetLastError();
 }
 }  // namespace
@@ -4232,6 +4335,43 @@ PI_EXPORT_ENSEMBLE(f64, double)
 
 PI_EXPORT_LOSS(f32, float)
 PI_EXPORT_LOSS(f64, double)
+
+// the same losses per sample of a batch / an ensemble (include/percnn_pi.h "Losses per sample")
+size_t percnn_pi_batch_traj_sqerr_workspace_bytes(int batch)
+{
+    if (batch < 1 || batch > MAX_BATCH) return 0;
+    return batch == 1 ? 1024 * sizeof(double) : (size_t)batch * batch_sqerr_slots(batch) * sizeof(double);
+}
+
+#define PI_EXPORT_BATCH_LOSS(SUF, T)                                                                                \
+    int percnn_pi_batch_traj_sqerr_##SUF(const T* traj, const T* target, const unsigned char* frame_mask, int nframes, \
+                                         int ndim, const int64_t* shape, int batch, double scale, T* out,           \
+                                         void* workspace, size_t workspace_bytes, void* stream)                     \
+    { return batch_sqerr_impl<T>(traj, target, frame_mask, nframes, ndim, shape, batch, scale, out, workspace,      \
+                                 workspace_bytes, stream); }                                                        \
+    int percnn_pi_batch_rollout_bwd_sqerr_##SUF(const T* traj, const T* target, const unsigned char* frame_mask,    \
+                                                double scale, const T* dev_scale, T* g_h0, double* param_grad,      \
+                                                void* workspace, size_t workspace_bytes, const T* params, int hc,   \
+                                                int ndim, const int64_t* shape, int batch, int T_steps,             \
+                                                const char* options, void* stream)                                  \
+    {                                                                                                               \
+        const pi::LossInj l{scale, dev_scale, target ? 2 : 1};                                                      \
+        return batch_rollout_bwd_impl<T>(traj, target, frame_mask, g_h0, param_grad, workspace, workspace_bytes,    \
+                                         params, hc, ndim, shape, batch, T_steps, options, stream, &l);             \
+    }                                                                                                               \
+    int percnn_pi_ensemble_rollout_bwd_sqerr_##SUF(const T* traj, const T* target, const unsigned char* frame_mask, \
+                                                   double scale, const T* dev_scale, T* g_h0, double* param_grad,   \
+                                                   void* workspace, size_t workspace_bytes, const T* params, int hc, \
+                                                   int ndim, const int64_t* shape, int batch, int T_steps,          \
+                                                   const char* options, void* stream)                               \
+    {                                                                                                               \
+        const pi::LossInj l{scale, dev_scale, target ? 2 : 1};                                                      \
+        return ens_rollout_bwd_impl<T>(traj, target, frame_mask, g_h0, param_grad, workspace, workspace_bytes,      \
+                                       params, hc, ndim, shape, batch, T_steps, options, stream, &l);               \
+    }
+
+PI_EXPORT_BATCH_LOSS(f32, float)
+PI_EXPORT_BATCH_LOSS(f64, double)
 
 #define PI_EXPORT_RES(SUF, T)                                                                                       \
     int percnn_pi_residual_fwd_##SUF(const T* traj, T* resid, const T* params, int ndim, const int64_t* shape,     \

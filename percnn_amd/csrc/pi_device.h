@@ -121,15 +121,22 @@ __device__ __forceinline__ void poly_dr(const T* __restrict__ c, T u, T v, T& ru
 // with a = scale * (dev ? *dev : 1) -- the host factor (2 / N for a mean) times the scalar autograd hands the loss, read from
 // device memory so that no host synchronisation is needed.  One subtraction and one multiplication, separately rounded:
 // the same values ATen's mse_loss / pow backward writes into a materialised dL/dtraj.
+// Sample flavours of the kernels (flavour_arg above): `dev` is a vector of B elements, one factor per sample -- each member of
+// a batch or an ensemble has a loss and an upstream gradient of its own -- and workgroup (x, b) reads dev[b]: wave-uniform,
+// so still a scalar load.
 struct LossInj {
     double scale;
-    const void* dev;        // nullable; one element of the compute type
+    const void* dev;        // nullable; one element of the compute type (sample flavours: B elements)
     int mode;               // 0, 1, 2
 };
-template <typename T>
-__device__ __forceinline__ T loss_factor(const LossInj& l)
+// S... = the sample index of this workgroup, passed by the sample flavours alone
+template <typename T, typename... S>
+__device__ __forceinline__ T loss_factor(const LossInj& l, S... sample)
 {
-    return (T)l.scale * (l.dev ? *static_cast<const T*>(l.dev) : T(1));
+    if constexpr (sizeof...(S) == 1)
+        return (T)l.scale * (l.dev ? static_cast<const T*>(l.dev)[flavour_arg<0>(sample...)] : T(1));
+    else
+        return (T)l.scale * (l.dev ? *static_cast<const T*>(l.dev) : T(1));
 }
 // value to add to the adjoint state: j = the value loaded through the injection pointer, h = the state at that point
 template <typename T>

@@ -702,7 +702,9 @@ pi_bwd_kernel(const T* __restrict__ h, const T* __restrict__ G, const T* __restr
                     ju = ldb<T, VEC>(plane_base<T, NDIM>(inj + g.off, g, iz), L.eb);
                     jv = ldb<T, VEC>(plane_base<T, NDIM>(inj + g.ss + g.off, g, iz), L.eb);
                 }
-                const T la = g.loss.mode ? loss_factor<T>(g.loss) : T(0);
+                T la;
+                if constexpr (sizeof...(X) >= 1) la = g.loss.mode ? loss_factor<T>(g.loss, (long)blockIdx.y) : T(0);   // its sample's factor
+                else la = g.loss.mode ? loss_factor<T>(g.loss) : T(0);
 #pragma unroll
                 for (int i = 0; i < VEC; ++i) {
                     ou.v[i] += loss_inject(g.loss.mode, la, u.v[i], ju.v[i]);
@@ -1175,11 +1177,21 @@ pi_residual_adj_kernel(const T* __restrict__ traj, const T* __restrict__ G, T* _
 // ---------------------------------------------------------------------------------------------
 // one frame of the loss gradient: out = a * (h - target) (target == nullptr: a * h).  The sweep starts from it (frame T has
 // no later step that could inject it) and the fall-back paths materialise whole trajectories of it.  n = elements.
-template <typename T, int VEC>
+// X... = `long sample` (grid (nb, B)): frame [B][n] of B samples, workgroup (x, b) writes sample b with its factor a_b
+// (loss_factor, pi_device.h); n = elements of one sample then.
+template <typename T, int VEC, typename... X>
 __global__ void __launch_bounds__(256)
-pi_loss_grad_kernel(const T* __restrict__ h, const T* __restrict__ target, T* __restrict__ out, long n, LossInj l)
+pi_loss_grad_kernel(const T* __restrict__ h, const T* __restrict__ target, T* __restrict__ out, long n, LossInj l, X... x)
 {
-    const T a = loss_factor<T>(l);
+    T a;
+    if constexpr (sizeof...(X) == 1) {
+        const long sbase = (long)blockIdx.y * flavour_arg<0>(x...);
+        h += sbase; out += sbase;
+        if (target) target += sbase;
+        a = loss_factor<T>(l, (long)blockIdx.y);
+    } else {
+        a = loss_factor<T>(l);
+    }
     for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * VEC; i < n; i += (long)gridDim.x * blockDim.x * VEC) {
         const Pack<T, VEC> x = ld<T, VEC>(h + i);
         Pack<T, VEC> y = x;
@@ -1196,12 +1208,65 @@ pi_loss_grad_kernel(const T* __restrict__ h, const T* __restrict__ target, T* __
 
 // sum_x (h - target)^2 over `n` consecutive elements (a run of whole frames), one partial per workgroup (double).
 // Streaming: 4 (8 with a target) bytes per element, read once; four 16-byte loads in flight per lane and operand.
-template <typename T, int VEC>
+// X... = `long fstride, int nfr, int slots` (grid (nb, B), nb <= slots): a run of nfr frames [B][n] of B samples, fstride = B * n
+// apart; workgroup (x, b) sums sample b's n elements of every frame of the run into slot b * slots + x -- slots of sample b
+// alone, one stride for every launch of a call.  A lane walks
+// the run's chunks of its sample as the unbatched kernel walks a contiguous run; (frame, chunk in frame) advance with the
+// lane's stride by one add and one conditional wrap, no division in the loop.
+template <typename T, int VEC, typename... X>
 __global__ void __launch_bounds__(256)
-pi_sqerr_kernel(const T* __restrict__ traj, const T* __restrict__ target, long n, double* __restrict__ partials)
+pi_sqerr_kernel(const T* __restrict__ traj, const T* __restrict__ target, long n, double* __restrict__ partials, X... x)
 {
     __shared__ double red[256 / WAVE];
     double acc = 0.0;
+    if constexpr (sizeof...(X) == 3) {
+        const long fstride = flavour_arg<0>(x...);
+        const long sbase = (long)blockIdx.y * n;
+        traj += sbase;
+        if (target) target += sbase;
+        const long cpf = n / VEC, nchunks = cpf * flavour_arg<1>(x...), stride = (long)gridDim.x * blockDim.x;
+        const long sq = stride / cpf, sr = stride % cpf;
+        long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+        long fr = c / cpf, off = c % cpf;                // chunk c = chunk `off` of frame `fr`
+        auto next = [&]() {                              // element offset of chunk c; then c += stride
+            const long e = fr * fstride + off * VEC;
+            c += stride; fr += sq; off += sr;
+            if (off >= cpf) { off -= cpf; ++fr; }
+            return e;
+        };
+        for (; c + 3 * stride < nchunks;) {
+            long e[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) e[q] = next();
+            Pack<T, VEC> v[4], t[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = ld<T, VEC>(traj + e[q]);
+            if (target) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) t[q] = ld<T, VEC>(target + e[q]);
+            }
+            T part = T(0);
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    const T d = target ? v[q].v[k] - t[q].v[k] : v[q].v[k];
+                    part = fma_(d, d, part);
+                }
+            acc += (double)part;
+        }
+        for (; c < nchunks;) {
+            const long e = next();
+            const Pack<T, VEC> v = ld<T, VEC>(traj + e);
+            T part = T(0);
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                const T d = target ? v.v[k] - target[e + k] : v.v[k];
+                part = fma_(d, d, part);
+            }
+            acc += (double)part;
+        }
+    } else {
     const long nchunks = n / VEC, stride = (long)gridDim.x * blockDim.x;
     long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
     for (; c + 3 * stride < nchunks; c += 4 * stride) {
@@ -1232,21 +1297,29 @@ pi_sqerr_kernel(const T* __restrict__ traj, const T* __restrict__ target, long n
         }
         acc += (double)part;
     }
+    }
     acc = wave_sum_to_last(acc);
     if (threadIdx.x % WAVE == REDUCE_LANE) red[threadIdx.x / WAVE] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
         double s = 0.0;
         for (int w = 0; w < 256 / WAVE; ++w) s += red[w];
-        partials[blockIdx.x] += s;                       // slots are zeroed by the host; runs beyond the 64th share slots (stream-ordered)
+        long slot = blockIdx.x;
+        if constexpr (sizeof...(X) == 3) slot = (long)blockIdx.y * flavour_arg<2>(x...) + blockIdx.x;
+        partials[slot] += s;                             // slots are zeroed by the host; runs beyond the 64th share slots (stream-ordered)
     }
 }
 
 // loss = scale * sum of the partials, written in the compute type (one wave, fixed order)
-template <typename T>
+// X... = `int slots` (grid (B)): out[b] = scale * sum of the n partials of sample b, which start at b * slots
+template <typename T, typename... X>
 __global__ void __launch_bounds__(64)
-pi_sqerr_finish_kernel(const double* __restrict__ partials, int n, double scale, T* __restrict__ out)
+pi_sqerr_finish_kernel(const double* __restrict__ partials, int n, double scale, T* __restrict__ out, X... x)
 {
+    if constexpr (sizeof...(X) == 1) {
+        partials += (long)blockIdx.x * flavour_arg<0>(x...);
+        out += blockIdx.x;
+    }
     double s = 0.0;
     for (int b = threadIdx.x; b < n; b += WAVE) s += partials[b];
 #pragma unroll

@@ -1212,6 +1212,10 @@ pi_adj2d_tile_kernel(const T* __restrict__ hframe_t, const T* __restrict__ gfram
         const long sbase = (long)blockIdx.y * flavour_arg<0>(sample...);   // sample blockIdx.y; partial row per (sample, tile)
         hframe_t += sbase; gframe_t += sbase; aframe_t += sbase;
         if (g_h0) g_h0 += sbase;
+        // loss form (pi_device.h): the factors are a vector, one per sample.  The sub-steps are device functions shared with the
+        // resident kernels, which know no sample: move the pointer to this sample's element here, once, instead of handing
+        // loss_factor a sample index down there (wave-uniform, still a scalar load)
+        if (g.loss.dev) g.loss.dev = static_cast<const T*>(g.loss.dev) + blockIdx.y;
     }
     using TL = Tile<K, BX, BY>;
     // Operand pipeline: one sub-step ahead (2 x 16 VGPRs).  Requesting ALL sub-steps' operands at kernel start was

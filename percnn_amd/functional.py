@@ -556,21 +556,154 @@ class PiRolloutSqErrFunction(torch.autograd.Function):
         return g_h0[None], pg.to(P.dtype), None, None, None, None, None
 
 
+def sqerr_selection(steps: int, frames: Optional[Sequence[int]], reduction: str, sample_numel: int, what: str = "pi_rollout_sqerr"):
+    """Host arithmetic of the squared-error operators, no device involved: which of the steps + 1 frames the loss covers and
+    the weight of one squared difference.  frames: indices into the frames (negative ones count from the end, duplicates
+    count once; None = all).  -> (mask, weight): mask a list of steps + 1 bools, or None when every frame is selected;
+    weight = 1 / (selected frames * sample_numel) for "mean" -- sample_numel = 2 * prod(S), the elements of ONE sample's
+    frame -- and 1 for "sum".  An empty selection raises."""
+    T1 = int(steps) + 1
+    sel = sorted(set(int(t) % T1 for t in frames)) if frames is not None else list(range(T1))
+    if not sel:
+        raise ValueError(f"{what}: no frame selected")
+    mask = None if len(sel) == T1 else [t in set(sel) for t in range(T1)]
+    weight = {"mean": 1.0 / (len(sel) * int(sample_numel)), "sum": 1.0}[reduction]
+    return mask, weight
+
+
 def pi_rollout_sqerr(h0: torch.Tensor, P: torch.Tensor, steps: int, target: Optional[torch.Tensor] = None,
                      frames: Optional[Sequence[int]] = None, reduction: str = "mean", options=None):
     """-> (loss, traj detached): ``mse_loss(traj[frames], target[frames], reduction)`` of the T-step rollout from h0 (target
     None: ``(traj[frames] ** 2).mean()`` / ``.sum()``) as one autograd node.  frames: indices into the T+1 frames (default
     all); target: [T+1, 2, *S] (frames outside `frames` are never read)."""
-    T1 = int(steps) + 1
-    sel = sorted(set(int(t) % T1 for t in frames)) if frames is not None else list(range(T1))
-    if not sel:
-        raise ValueError("pi_rollout_sqerr: no frame selected")
-    mask = None if len(sel) == T1 else [t in set(sel) for t in range(T1)]
-    n = len(sel) * int(h0[0].numel())
-    weight = {"mean": 1.0 / n, "sum": 1.0}[reduction]
-    if target is not None and tuple(target.shape) != (T1,) + tuple(h0.shape[1:]):
+    mask, weight = sqerr_selection(steps, frames, reduction, int(h0[0].numel()))
+    if target is not None and tuple(target.shape) != (int(steps) + 1,) + tuple(h0.shape[1:]):
         raise ValueError("target must have the trajectory's shape [steps + 1, 2, *S]")
     return PiRolloutSqErrFunction.apply(h0, P, int(steps), target, mask, weight, options)
+
+
+# ---- the same loss per sample of a batch (one block) / an ensemble (one block per sample): [B] losses, one autograd node ----
+def traj_sqerr_batched(traj: torch.Tensor, target: Optional[torch.Tensor] = None, frame_mask: Optional[Sequence[bool]] = None,
+                       scale: float = 1.0) -> torch.Tensor:
+    """traj / target [F,B,2,*S] -> [B] of traj's dtype: scale * sum over the frames with frame_mask[f] of sum_x (traj[f,b] -
+    target[f,b])^2, one streaming pass and one fixed-order sum per sample (``percnn_pi_batch_traj_sqerr_*``; target None = 0)."""
+    _require(traj, "traj")
+    if target is not None:
+        _require(target, "target", traj.dtype)
+        assert target.shape == traj.shape
+    B, shape = int(traj.shape[1]), traj.shape[3:]
+    L = _lib.lib()
+    nbytes = L.percnn_pi_batch_traj_sqerr_workspace_bytes(B)
+    if nbytes == 0:
+        raise RuntimeError(f"percnn_amd: invalid batch size {B}")
+    out = torch.empty(B, dtype=traj.dtype, device=traj.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=traj.device)
+    f = getattr(L, "percnn_pi_batch_traj_sqerr_" + _SUF[traj.dtype])
+    with torch.cuda.device(traj.device):
+        _lib.check(f(traj.data_ptr(), target.data_ptr() if target is not None else None, _mask_bytes(frame_mask, traj.shape[0]),
+                     traj.shape[0], len(shape), _lib.shape_arg(shape), B, float(scale), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                     _stream()), "batch_traj_sqerr")
+    return out
+
+
+def rollout_bwd_sqerr_batched(traj: torch.Tensor, P: torch.Tensor, target: Optional[torch.Tensor] = None,
+                              frame_mask: Optional[Sequence[bool]] = None, scale: float = 1.0,
+                              dev_scale: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None, options=None,
+                              g_h0: Optional[torch.Tensor] = None):
+    """Backward of the B losses  L_b = (scale / 2) * sum_{t in mask} sum_x (traj[t,b] - target[t,b])^2, each times its own
+    factor ``dev_scale[b]`` (a [B] device tensor, None = 1), WITHOUT a dL/dtraj buffer (``percnn_pi_{batch,ensemble}_rollout_
+    bwd_sqerr_*``).  traj / target [T+1,B,2,*S]; P [np]: one block -> (dL/dh0 [B,2,*S], double [np] summed over the samples);
+    P [B,np]: one block per sample -> (dL/dh0, double [B,np])."""
+    _require(traj, "traj"); _require(P, "params", traj.dtype)
+    if target is not None:
+        _require(target, "target", traj.dtype)
+        assert target.shape == traj.shape
+    T, B, shape = traj.shape[0] - 1, int(traj.shape[1]), traj.shape[3:]
+    kind = "ensemble" if P.dim() == 2 else "batch"
+    if kind == "ensemble" and P.shape[0] != B:
+        raise ValueError(f"one parameter block per sample: P [{B},np], got {tuple(P.shape)}")
+    hc = _hc_of(P[0] if kind == "ensemble" else P)
+    if dev_scale is not None:
+        dev_scale = dev_scale.reshape(B).to(traj.dtype).contiguous()
+    L = _lib.lib()
+    if g_h0 is None:
+        g_h0 = torch.empty_like(traj[0])
+    pg = torch.zeros(tuple(P.shape), dtype=torch.float64, device=traj.device)
+    if ws is None:
+        nbytes = getattr(L, f"percnn_pi_{kind}_rollout_bwd_workspace_bytes")(hc, len(shape), _lib.shape_arg(shape), B, T,
+                                                                            traj.dtype.itemsize)
+        if nbytes == 0:
+            raise RuntimeError("percnn_amd: invalid problem shape, batch size or block kind")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=traj.device)
+    f = getattr(L, f"percnn_pi_{kind}_rollout_bwd_sqerr_" + _SUF[traj.dtype])
+    with torch.cuda.device(traj.device):
+        _lib.check(f(traj.data_ptr(), target.data_ptr() if target is not None else None, _mask_bytes(frame_mask, T + 1),
+                     float(scale), dev_scale.data_ptr() if dev_scale is not None else None, g_h0.data_ptr(), pg.data_ptr(),
+                     ws.data_ptr(), ws.numel(), P.data_ptr(), hc, len(shape), _lib.shape_arg(shape), B, T,
+                     _lib.options_arg(options), _stream()), f"{kind}_rollout_bwd_sqerr")
+    return g_h0, pg
+
+
+class PiRolloutSqErrBatchedFunction(torch.autograd.Function):
+    """``PiRolloutSqErrFunction`` for B trajectories: loss[b] = weight * sum_{t in frames} sum_x (h_t[b] - target_t[b])^2, a
+    [B] tensor, as ONE autograd node.  Forward = the batched (P [np]) or ensemble (P [B,np]) rollout + one streaming
+    reduction per sample; backward = the sweep with the incoming [B] gradient as per-sample factors, the loss gradient formed
+    in-kernel -- no dL/dtraj [T+1,B,2,*S], no host synchronisation.  Returns (loss, traj); traj is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, h0, P, steps, target, frame_mask, weight, options):
+        _native()
+        P = P.contiguous()
+        op = torch.ops.percnn.pi_rollout_ensemble if P.dim() == 2 else torch.ops.percnn.pi_rollout_batched
+        traj = op(h0, P, steps, _options_str(options))
+        loss = traj_sqerr_batched(traj, target, frame_mask, weight)
+        ctx.save_for_backward(traj, P) if target is None else ctx.save_for_backward(traj, P, target)
+        ctx.meta = (frame_mask, float(weight), options)
+        ctx.mark_non_differentiable(traj)
+        ctx.set_materialize_grads(False)
+        return loss, traj
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_traj):
+        if g_loss is None:
+            return None, None, None, None, None, None, None
+        saved = ctx.saved_tensors
+        traj, P = saved[0], saved[1]
+        target = saved[2] if len(saved) > 2 else None
+        frame_mask, weight, options = ctx.meta
+        g_h0, pg = rollout_bwd_sqerr_batched(traj, P, target, frame_mask, 2.0 * weight, g_loss.contiguous(), options=options)
+        return g_h0, pg.to(P.dtype), None, None, None, None, None
+
+
+def _pi_rollout_sqerr_samples(what, h0, P, steps, target, frames, reduction, options):
+    if h0.dim() not in (4, 5) or h0.shape[1] != 2:
+        raise ValueError(f"{what}: h0 must be [B,2,*S], got {tuple(h0.shape)}")
+    mask, weight = sqerr_selection(steps, frames, reduction, int(h0[0].numel()), what)
+    if target is not None:
+        if tuple(target.shape) != (int(steps) + 1,) + tuple(h0.shape):
+            raise ValueError("target must have the trajectory's shape [steps + 1, B, 2, *S]")
+        target = target.detach()
+    return PiRolloutSqErrBatchedFunction.apply(h0, P, int(steps), target, mask, weight, options)
+
+
+def pi_rollout_sqerr_batched(h0: torch.Tensor, P: torch.Tensor, steps: int, target: Optional[torch.Tensor] = None,
+                             frames: Optional[Sequence[int]] = None, reduction: str = "mean", options=None):
+    """-> (loss [B], traj [T+1,B,2,*S] detached): ``loss[b] = mse_loss(traj[frames, b], target[frames, b], reduction)`` of the
+    T-step rollouts from h0 [B,2,*S] with ONE block P [np] (target None: 0; the mean is over len(frames) * 2 * prod(S)), as
+    one autograd node.  ``loss.mean().backward()``, ``.sum()`` or any weighting of the samples is the caller's line; the
+    parameter gradient is the sum over the samples.  target gets no gradient."""
+    if P.dim() != 1:
+        raise ValueError(f"pi_rollout_sqerr_batched: one parameter block [np], got {tuple(P.shape)}")
+    return _pi_rollout_sqerr_samples("pi_rollout_sqerr_batched", h0, P, steps, target, frames, reduction, options)
+
+
+def pi_rollout_sqerr_ensemble(h0: torch.Tensor, P: torch.Tensor, steps: int, target: Optional[torch.Tensor] = None,
+                              frames: Optional[Sequence[int]] = None, reduction: str = "mean", options=None):
+    """``pi_rollout_sqerr_batched`` with one block per sample, P [B,np]: loss[b] is member b's loss, and row b of the [B,np]
+    parameter gradient is the gradient of member b alone."""
+    if P.dim() != 2 or P.shape[0] != h0.shape[0]:
+        raise ValueError(f"pi_rollout_sqerr_ensemble: one parameter block per sample [B,np], got {tuple(P.shape)}")
+    return _pi_rollout_sqerr_samples("pi_rollout_sqerr_ensemble", h0, P, steps, target, frames, reduction, options)
 
 
 def step_fwd(h: torch.Tensor, P: torch.Tensor, out: Optional[torch.Tensor] = None, slab: bool = False,

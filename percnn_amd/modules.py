@@ -954,6 +954,27 @@ class RCNN(nn.Module):
         self.last_trajectory = traj
         return loss
 
+    def sample_losses(self, target: Optional[torch.Tensor] = None, t_slice=slice(None), reduction: str = "mean") -> torch.Tensor:
+        """[B]: ``loss_mse`` of every sample on its own -- ``F.mse_loss(traj[t_slice][:, b], target[t_slice][:, b], reduction)``
+        of the batched trajectory [step+1, B, 2, *S] (``target`` None: 0; the full-trajectory tensor otherwise) -- with the B
+        rollouts as ONE autograd node and no dL/dtraj (``pi_rollout_sqerr_batched`` / ``pi_rollout_sqerr_ensemble``).  For a
+        batched initial state with a Pi-block cell, for a ``CellEnsemble`` (the gradient of loss b reaches member b's
+        parameters) and for B = 1 ([1]).  ``sample_losses().mean().backward()``, a sum or any weighting of the samples is the
+        caller's line.  Needs a dense ``effective_step``; the detached trajectory is kept in ``self.last_trajectory``."""
+        if self.effective_step != list(range(self.step)):
+            raise ValueError("sample_losses() indexes the dense output list: effective_step must be list(range(step))")
+        if hasattr(self, "UpconvBlock"):
+            self.init_state = self.UpconvBlock(self.init_state_low)
+        frames = list(range(self.step + 1))[t_slice]
+        if self._ensemble("RCNN.sample_losses()"):
+            op = F_pi.pi_rollout_sqerr_ensemble
+        else:
+            self._check_batchable("RCNN.sample_losses()")
+            op = F_pi.pi_rollout_sqerr_batched
+        loss, traj = op(self.init_state, self._block(), self.step, target, frames, reduction)
+        self.last_trajectory = traj
+        return loss
+
     def ic_loss(self, mode: Optional[str] = None) -> torch.Tensor:
         """``get_ic_loss(model)`` of the reference scripts (train_2drd.py:331-338, train_3drd.py:325-332): MSE between the IC
         generator's output and the low-resolution measurement interpolated to ITS output size (bicubic in 2D, trilinear in
