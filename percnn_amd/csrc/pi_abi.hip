@@ -8,8 +8,10 @@
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <thread>
+#include <tuple>
 
 #include "../../include/percnn_pi.h"
 #include "pi_kernels.h"
@@ -1251,6 +1253,9 @@ bool persist_ok(const Problem& p, const unsigned char* mask, int t_top, int ngro
 // nothing, and say so in a host-mapped status slot (pi_tile2d.h, PersistArgs::host).  With the handshake (default) the entry
 // point waits for that word -- "all resident" normally arrives a few microseconds after the kernel starts -- and enqueues the
 // launch-per-group sweep itself on an abort; the device then keeps the launch-per-group path until persist_reset.
+// The host side of that protocol is the functions below, once for every resident launcher (2D tile sweeps and forwards, the
+// 3D adjoint sweep, and through pi_host.h the Stage-1 unit): persist_enter -> [persist_fits] -> [persist_scratch] ->
+// persist_claim -> the launch -> persist_launched.
 constexpr int PERSIST_SLOTS = 32;
 struct PersistHost {                                      // host-mapped (hipHostMalloc): written by the device, read here
     volatile int slot[PERSIST_SLOTS][4];                  // {roll call complete, group, tile, aborted}: see PersistArgs::host
@@ -1268,8 +1273,9 @@ struct PersistGuard {
     long launches = 0, aborts = 0;
     int last_group = -1, last_tile = -1;
     bool warned = false;
-    void* fwd_scratch[16] = {};                           // per device: sync words + granule outbox of the resident forward
+    void* fwd_scratch[16] = {};                           // per device: sync words + granule outbox (persist_scratch)
     size_t fwd_scratch_bytes[16] = {};
+    std::map<std::tuple<int, const void*, size_t>, int> fits;   // (device, kernel, LDS bytes) -> workgroups per CU (persist_fits)
 };
 PersistGuard g_persist;
 
@@ -1333,6 +1339,126 @@ void persist_leave(hipStream_t st, int dev)
     if (hipEventRecord(g_persist.ev[dev], st) == hipSuccess) { g_persist.st[dev] = st; g_persist.armed[dev] = true; }
 }
 
+// workgroups of kernel `k` (NT lanes, `lds` bytes) that fit a CU of device `dev`, the current one; 0: none, or the runtime
+// would not say.  Asked once per (device, kernel, lds) -- after allow_lds, which the answer depends on.
+template <typename F>
+int persist_fits(F* k, int NT, size_t lds, int dev)
+{
+    std::lock_guard<std::mutex> lk(g_persist.mu);
+    auto [it, fresh] = g_persist.fits.try_emplace({dev, reinterpret_cast<const void*>(k), lds}, 0);
+    if (fresh) {
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, NT, lds) != hipSuccess || nb < 1) { (void)hipGetLastError(); nb = 0; }
+        it->second = nb;
+    }
+    return it->second;
+}
+
+// the per-device scratch of the launchers that bring no workspace: 256 B of sync words | outbox of `outbox_bytes`, allocated
+// once (sized for this launch or larger) and zeroed on the stream
+hipError_t persist_scratch(size_t outbox_bytes, hipStream_t st, pi_host::Resident& r)
+{
+    const size_t need = 256 + outbox_bytes;
+    {
+        std::lock_guard<std::mutex> lk(g_persist.mu);
+        if (g_persist.fwd_scratch_bytes[r.dev] < need) {
+            if (g_persist.fwd_scratch[r.dev]) {             // (a launch that still uses the old one is ordered before this call's
+                (void)hipFree(g_persist.fwd_scratch[r.dev]);// work only on its own stream: hipFree synchronises the device)
+                g_persist.fwd_scratch[r.dev] = nullptr;
+                g_persist.fwd_scratch_bytes[r.dev] = 0;
+            }
+            void* q = nullptr;
+            if (hipMalloc(&q, need) != hipSuccess || !q) { (void)hipGetLastError(); return hipErrorOutOfMemory; }
+            g_persist.fwd_scratch[r.dev] = q;
+            g_persist.fwd_scratch_bytes[r.dev] = need;
+        }
+        r.scratch = static_cast<unsigned char*>(g_persist.fwd_scratch[r.dev]);
+    }
+    return hipMemsetAsync(r.scratch, 0, need, st);
+}
+
+// a status slot for the launch about to be made (r.dev: from persist_enter), reset, and the bounds of its hand-over waits
+void persist_claim(const Options& o, pi_host::Resident& r)
+{
+    {
+        std::lock_guard<std::mutex> lk(g_persist.mu);
+        r.slot = g_persist.next_slot++ % PERSIST_SLOTS;
+        g_persist.watch[r.slot] = false;
+    }
+    r.hs = g_persist.host->slot[r.slot];
+    r.hs[0] = 0; r.hs[1] = -1; r.hs[2] = -1; r.hs[3] = 0;
+    r.timeout_ticks = (unsigned long long)o.persist_timeout_ms * 100000ull;                 // 100 MHz clock
+    r.first_timeout_ticks = (unsigned long long)o.persist_first_timeout_ms * 100000ull;
+}
+
+// the PersistArgs every 2D resident kernel takes; the launcher adds what is its own (t_top, pause, masked, frames)
+pi::PersistArgs persist_args(const pi_host::Resident& r, unsigned long long* outbox, unsigned* sync, int ngroups)
+{
+    pi::PersistArgs pa{};
+    pa.outbox = outbox; pa.sync = sync; pa.ngroups = ngroups;
+    pa.host = const_cast<int*>(r.hs);
+    pa.timeout_ticks = r.timeout_ticks;
+    pa.first_timeout_ticks = r.first_timeout_ticks;
+    return pa;
+}
+
+// wait for the roll call of a resident launch (not for the launch itself): normally a few microseconds after the kernel
+// starts, i.e. this returns when the stream has reached it.  The bound only guards against a device that never runs the
+// launch at all.  An abort is dealt with here -- the caller recomputes launch by launch.
+hipError_t persist_wait_roll_call(volatile int* hs, int slot, int dev, unsigned grid, const char* what)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned spins = 0;
+    while (hs[0] == 0 && hs[3] == 0) {
+        if ((++spins & 0x3ff) == 0) {
+            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(600)) return hipErrorLaunchTimeOut;
+            std::this_thread::yield();
+        }
+    }
+    if (hs[3] != 0) {
+        std::lock_guard<std::mutex> lk(g_persist.mu);
+        g_persist.watch[slot] = false;
+        ++g_persist.aborts;
+        g_persist.last_group = hs[1];
+        g_persist.last_tile = hs[2];
+        g_persist.disabled[dev] = true;
+        if (!g_persist.warned) {
+            g_persist.warned = true;
+            std::fprintf(stderr, "percnn_pi: %s could not keep all %u workgroups resident on device %d (group %d, tile %d: another "
+                                 "process / kernel holds CUs, or a CU mask is set); using one launch per group of steps from now on "
+                                 "(percnn_pi_set_option(\"persist_reset\", 1) re-arms it)\n", what, grid, dev, (int)hs[1], (int)hs[2]);
+        }
+        return hipErrorLaunchFailure;
+    }
+    return hipSuccess;
+}
+
+// after a launch that was enqueued without error.  hipSuccess: resident and running (handshake), or fire and forget (an abort
+// nobody has dealt with surfaces at the next entry point: PERCNN_PI_EASYNC); hipErrorLaunchFailure: it ran and ABORTED;
+// hipErrorLaunchTimeOut: fatal.  In the first two cases the launch is on the stream: persist_leave records it for persist_enter.
+hipError_t persist_launched(hipStream_t st, const pi_host::Resident& r, int handshake, unsigned grid, const char* what)
+{
+    {
+        std::lock_guard<std::mutex> lk(g_persist.mu);
+        g_persist.watch[r.slot] = true;
+        ++g_persist.launches;
+    }
+    const hipError_t e = handshake ? persist_wait_roll_call(r.hs, r.slot, r.dev, grid, what) : hipSuccess;
+    if (e == hipSuccess || e == hipErrorLaunchFailure) persist_leave(st, r.dev);
+    return e;
+}
+
+// what the caller of a resident launcher does with its return value
+enum class ResidentRun { ran, fall_back, fall_back_clear, fatal };
+ResidentRun resident_outcome(hipError_t e)
+{
+    if (e == hipSuccess) return ResidentRun::ran;
+    if (e == hipErrorLaunchTimeOut) return ResidentRun::fatal;       // the device never ran the launch: the stream is stuck behind it
+    (void)hipGetLastError();                                      // not resident / not supported / aborted: launch by launch
+    // it RAN and gave up: workgroups that were already through may have added to their partial rows -- start the rows over
+    return e == hipErrorLaunchFailure ? ResidentRun::fall_back_clear : ResidentRun::fall_back;
+}
+
 // ---- RESIDENT 3D reverse sweep (pi_res3d.h, round 6) ------------------------------------------------------------------
 // The whole sweep of a float32 pre-contracted 3D rollout as one launch: one resident workgroup per 16 x 16 x 32 block keeps the
 // adjoint state in LDS, reads only h_{t-1} and the injected dL/dtraj_{t-1} per step, hands its two-deep faces to the six
@@ -1381,15 +1507,9 @@ hipError_t launch_adj_res3d(const float* traj, const float* g_traj, const unsign
     constexpr int NT = 512;
     auto* k = pi_adj3d_resident_kernel<NT>;
     if (hipError_t e = allow_lds(k, (size_t)LDS_BYTES)) return e;
-    static int blocks_per_cu[16] = {};                      // per device, asked once
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) { (void)hipGetLastError(); return hipErrorNotSupported; }
-    if (!blocks_per_cu[dev]) {
-        int q = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, k, NT, (size_t)LDS_BYTES) != hipSuccess || q < 1) { (void)hipGetLastError(); q = -1; }
-        blocks_per_cu[dev] = q;
-    }
-    if (blocks_per_cu[dev] < 1) return hipErrorCooperativeLaunchTooLarge;
+    if (persist_fits(k, NT, (size_t)LDS_BYTES, dev) < 1) return hipErrorCooperativeLaunchTooLarge;
     pi_host::Resident r;
     const size_t outbox_bytes = (size_t)2 * (size_t)pl.nblk * Shape<NT>::BOX_BYTES;
     if (hipError_t e = pi_host::resident_begin(st, outbox_bytes, r)) return e == hipErrorLaunchFailure ? hipErrorNotSupported : e;
@@ -1414,16 +1534,19 @@ hipError_t launch_adj_res3d(const float* traj, const float* g_traj, const unsign
     return pi_host::resident_launched(st, r, (unsigned)pl.nblk, "the resident 3D adjoint sweep");
 }
 
-// groups of 4 steps from frame t_top down; g_h0 only if the last group ends at frame 0.  Returns hipErrorCooperativeLaunchTooLarge
-// (or whatever the runtime says) WITHOUT having launched anything if the workgroups cannot all be resident, and
-// hipErrorLaunchFailure if the launch ran and ABORTED (handshake mode; nothing it was asked for has been written): the caller
-// then runs the launch-per-group path.  `sync`: three zeroed device words (PersistArgs::sync).
+// groups of 4 steps from frame t_top down; g_h0 only if the last group ends at frame 0.  Returns hipErrorNotSupported (no
+// resident launch may start here now: persist_enter), hipErrorCooperativeLaunchTooLarge (the workgroups cannot all be resident)
+// or whatever the runtime says WITHOUT having launched anything, and hipErrorLaunchFailure if the launch ran and ABORTED
+// (handshake mode; nothing it was asked for has been written): the caller then runs the launch-per-group path
+// (resident_outcome).  `sync`: three zeroed device words (PersistArgs::sync).
 template <typename T>
 hipError_t launch_adj_persist(const T* hframe_t, const T* gframe_t, T* aframe_t, T* g_h0, int t_top, const unsigned char* mask,
                               int ngroups, double* partials, unsigned long long* outbox, unsigned* sync, const T* P,
-                              const Problem& p, int dev, hipStream_t st)
+                              const Problem& p, hipStream_t st)
 {
     constexpr int K = 4, NT = 512;
+    pi_host::Resident r;
+    if (!persist_enter(st, r.dev)) return hipErrorNotSupported;
     using TL = pi::Tile<K, TILE_B, TILE_B>;
     pi::TileGeom g = make_tile_geom(p, TILE_B);
     const unsigned grid = (unsigned)((p.n0 / TILE_B) * g.tiles_x);
@@ -1438,30 +1561,12 @@ hipError_t launch_adj_persist(const T* hframe_t, const T* gframe_t, T* aframe_t,
         if (!p.opt.persist_split) k = pi::pi_adj2d_persist_kernel<T, K, TILE_B, TILE_B, NT>;
     }
     if (hipError_t e = allow_lds(k, lds)) return e;
-    static int resident[16][2] = {};                        // per device and flavour (per value type: a template): one workgroup per CU?
-    int& res = resident[dev][p.opt.persist_split ? 1 : 0];
-    if (!res) {
-        int nb = 0;
-        res = (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, NT, lds) == hipSuccess && nb >= 1) ? 1 : -1;
-    }
-    if (res < 0) return hipErrorCooperativeLaunchTooLarge;
+    if (persist_fits(k, NT, lds, r.dev) < 1) return hipErrorCooperativeLaunchTooLarge;      // one workgroup per CU (persist_ok)
     if (hipError_t e = hipMemsetAsync(outbox, 0, persist_outbox_bytes(p, (int)sizeof(T)), st)) return e;
     long frame_stride = (long)(2 * p.n);
     int np = pi::nparams(p.hc);
-    pi::PersistArgs pa{};
-    int slot;
-    {
-        std::lock_guard<std::mutex> lk(g_persist.mu);
-        slot = g_persist.next_slot++ % PERSIST_SLOTS;
-        g_persist.watch[slot] = false;
-        ++g_persist.launches;
-    }
-    volatile int* hs = g_persist.host->slot[slot];
-    hs[0] = 0; hs[1] = -1; hs[2] = -1; hs[3] = 0;
-    pa.outbox = outbox; pa.sync = sync; pa.ngroups = ngroups;
-    pa.host = const_cast<int*>(hs);
-    pa.timeout_ticks = (unsigned long long)p.opt.persist_timeout_ms * 100000ull;             // 100 MHz clock
-    pa.first_timeout_ticks = (unsigned long long)p.opt.persist_first_timeout_ms * 100000ull;
+    persist_claim(p.opt, r);
+    pi::PersistArgs pa = persist_args(r, outbox, sync, ngroups);
     pa.t_top = t_top;
     pa.masked = mask ? 1 : 0;
     if (mask)
@@ -1477,38 +1582,7 @@ hipError_t launch_adj_persist(const T* hframe_t, const T* gframe_t, T* aframe_t,
         e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(k), dim3(grid), dim3(NT), args, (unsigned)lds, st);
     }
     if (e != hipSuccess) return e;
-    {   // whoever launched it: an abort nobody has dealt with surfaces at the next entry point (PERCNN_PI_EASYNC)
-        std::lock_guard<std::mutex> lk(g_persist.mu);
-        g_persist.watch[slot] = true;
-    }
-    if (!p.opt.persist_handshake) return hipSuccess;        // fire and forget
-    // wait for the roll call (not for the sweep): normally a few microseconds after the kernel starts, i.e. this returns when the
-    // stream has reached the sweep.  The bound only guards against a device that never runs the launch at all.
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    while (hs[0] == 0 && hs[3] == 0) {
-        if ((++spins & 0x3ff) == 0) {
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(600)) return hipErrorLaunchTimeOut;
-            std::this_thread::yield();
-        }
-    }
-    if (hs[3] != 0) {
-        std::lock_guard<std::mutex> lk(g_persist.mu);
-        g_persist.watch[slot] = false;                      // dealt with here: the caller re-runs the sweep launch by launch
-        ++g_persist.aborts;
-        g_persist.last_group = hs[1];
-        g_persist.last_tile = hs[2];
-        g_persist.disabled[dev] = true;
-        if (!g_persist.warned) {
-            g_persist.warned = true;
-            std::fprintf(stderr, "percnn_pi: the persistent tile sweep could not keep all %u workgroups resident on device %d "
-                                 "(group %d, tile %d: another process / kernel holds CUs, or a CU mask is set); using one launch "
-                                 "per group of steps from now on (percnn_pi_set_option(\"persist_reset\", 1) re-arms it)\n",
-                         grid, dev, (int)hs[1], (int)hs[2]);
-        }
-        return hipErrorLaunchFailure;
-    }
-    return hipSuccess;
+    return persist_launched(st, r, p.opt.persist_handshake, grid, "the persistent tile sweep");
 }
 
 // ---- resident FORWARD (pi_fwd2d_persist_kernel): the same grids, the same residency protocol ----------------------------------
@@ -1535,9 +1609,11 @@ bool fwd_persist_ok(const Problem& p, int ngroups, hipStream_t st)
 // frames t0 + 1 .. t0 + 4 * ngroups from frame t0.  Return values as launch_adj_persist: hipErrorLaunchFailure = it ran and
 // ABORTED (frames may be partly written: the caller recomputes them launch by launch, which is deterministic).
 template <typename T>
-hipError_t launch_fwd_persist(T* frame_t0, int ngroups, const T* P, const Problem& p, int dev, hipStream_t st)
+hipError_t launch_fwd_persist(T* frame_t0, int ngroups, const T* P, const Problem& p, hipStream_t st)
 {
     constexpr int K = 4, NT = 512;
+    pi_host::Resident r;
+    if (!persist_enter(st, r.dev)) return hipErrorNotSupported;
     pi::TileGeom g = make_tile_geom(p, TILE_B);
     const unsigned grid = (unsigned)((p.n0 / TILE_B) * g.tiles_x);
     // state buffers | publish / gather tables and 6 rows of strip geometry | abort word
@@ -1547,48 +1623,12 @@ hipError_t launch_fwd_persist(T* frame_t0, int ngroups, const T* P, const Proble
     const int two = (int64_t)grid > (int64_t)device_cu_count() ? 1 : 0;
     auto* k = two ? pi::pi_fwd2d_persist_kernel<T, K, TILE_B, TILE_B, NT, 2> : pi::pi_fwd2d_persist_kernel<T, K, TILE_B, TILE_B, NT, 1>;
     if (hipError_t e = allow_lds(k, lds)) return e;
-    static int resident[16][2] = {};                        // per device and flavour: workgroups that fit a CU (asked once; -1: none)
-    if (!resident[dev][two]) {
-        int nb = 0;
-        resident[dev][two] = (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, NT, lds) == hipSuccess && nb >= 1) ? nb : -1;
-    }
-    if (resident[dev][two] < 0 || (int64_t)grid > (int64_t)device_cu_count() * resident[dev][two]) return hipErrorCooperativeLaunchTooLarge;
-    // per-device scratch: 256 B of sync words | granule outbox (allocated once, sized for this grid or larger)
-    const size_t need = 256 + persist_outbox_bytes(p, (int)sizeof(T));
-    unsigned char* scratch;
-    {
-        std::lock_guard<std::mutex> lk(g_persist.mu);
-        if (g_persist.fwd_scratch_bytes[dev] < need) {
-            if (g_persist.fwd_scratch[dev]) {               // (a launch that still uses the old one is ordered before this call's
-                (void)hipFree(g_persist.fwd_scratch[dev]);  // work only on its own stream: hipFree synchronises the device)
-                g_persist.fwd_scratch[dev] = nullptr;
-                g_persist.fwd_scratch_bytes[dev] = 0;
-            }
-            void* q = nullptr;
-            if (hipMalloc(&q, need) != hipSuccess || !q) { (void)hipGetLastError(); return hipErrorOutOfMemory; }
-            g_persist.fwd_scratch[dev] = q;
-            g_persist.fwd_scratch_bytes[dev] = need;
-        }
-        scratch = static_cast<unsigned char*>(g_persist.fwd_scratch[dev]);
-    }
-    if (hipError_t e = hipMemsetAsync(scratch, 0, need, st)) return e;
+    const int nb = persist_fits(k, NT, lds, r.dev);
+    if (nb < 1 || (int64_t)grid > (int64_t)device_cu_count() * nb) return hipErrorCooperativeLaunchTooLarge;
+    if (hipError_t e = persist_scratch(persist_outbox_bytes(p, (int)sizeof(T)), st, r)) return e;
     long frame_stride = (long)(2 * p.n);
-    pi::PersistArgs pa{};
-    int slot;
-    {
-        std::lock_guard<std::mutex> lk(g_persist.mu);
-        slot = g_persist.next_slot++ % PERSIST_SLOTS;
-        g_persist.watch[slot] = false;
-        ++g_persist.launches;
-    }
-    volatile int* hs = g_persist.host->slot[slot];
-    hs[0] = 0; hs[1] = -1; hs[2] = -1; hs[3] = 0;
-    pa.outbox = reinterpret_cast<unsigned long long*>(scratch + 256);
-    pa.sync = reinterpret_cast<unsigned*>(scratch);
-    pa.ngroups = ngroups;
-    pa.host = const_cast<int*>(hs);
-    pa.timeout_ticks = (unsigned long long)p.opt.persist_timeout_ms * 100000ull;             // 100 MHz clock
-    pa.first_timeout_ticks = (unsigned long long)p.opt.persist_first_timeout_ms * 100000ull;
+    persist_claim(p.opt, r);
+    pi::PersistArgs pa = persist_args(r, reinterpret_cast<unsigned long long*>(r.scratch + 256), reinterpret_cast<unsigned*>(r.scratch), ngroups);
     void* args[] = {(void*)&frame_t0, (void*)&frame_stride, (void*)&P, (void*)&g, (void*)&pa};
     hipError_t e;
     if (p.opt.tile_persist == 2) {
@@ -1598,36 +1638,7 @@ hipError_t launch_fwd_persist(T* frame_t0, int ngroups, const T* P, const Proble
         e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(k), dim3(grid), dim3(NT), args, (unsigned)lds, st);
     }
     if (e != hipSuccess) return e;
-    {
-        std::lock_guard<std::mutex> lk(g_persist.mu);
-        g_persist.watch[slot] = true;
-    }
-    if (!p.opt.persist_handshake) return hipSuccess;        // fire and forget (an abort: PERCNN_PI_EASYNC at the next entry point)
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    while (hs[0] == 0 && hs[3] == 0) {
-        if ((++spins & 0x3ff) == 0) {
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(600)) return hipErrorLaunchTimeOut;
-            std::this_thread::yield();
-        }
-    }
-    if (hs[3] != 0) {
-        std::lock_guard<std::mutex> lk(g_persist.mu);
-        g_persist.watch[slot] = false;
-        ++g_persist.aborts;
-        g_persist.last_group = hs[1];
-        g_persist.last_tile = hs[2];
-        g_persist.disabled[dev] = true;
-        if (!g_persist.warned) {
-            g_persist.warned = true;
-            std::fprintf(stderr, "percnn_pi: the resident forward rollout could not keep all %u workgroups resident on device %d "
-                                 "(group %d, tile %d: another process / kernel holds CUs, or a CU mask is set); using one launch "
-                                 "per group of steps from now on (percnn_pi_set_option(\"persist_reset\", 1) re-arms it)\n",
-                         grid, dev, (int)hs[1], (int)hs[2]);
-        }
-        return hipErrorLaunchFailure;
-    }
-    return hipSuccess;
+    return persist_launched(st, r, p.opt.persist_handshake, grid, "the resident forward rollout");
 }
 
 // ---- small-tile persistent sweep (pi_adj2d_persist_small_kernel): the 32 x 8 / 256-lane regime with the split schedule --------
@@ -1663,9 +1674,11 @@ bool persist_small_ok(const Problem& p, const unsigned char* mask, int t_top, in
 template <typename T, int BY, int NT, bool HALFS = false>
 hipError_t launch_adj_persist_small_t(const T* hframe_t, const T* gframe_t, T* aframe_t, T* g_h0, int t_top, const unsigned char* mask,
                                     int ngroups, double* partials, unsigned long long* outbox, unsigned* sync, const T* P,
-                                    const Problem& p, int dev, hipStream_t st)
+                                    const Problem& p, hipStream_t st)
 {
     constexpr int K = 4;
+    pi_host::Resident r;
+    if (!persist_enter(st, r.dev)) return hipErrorNotSupported;
     using TL = pi::Tile<K, TILE_B, BY>;
     pi::TileGeom g = make_tile_geom(p, BY);
     const unsigned grid = (unsigned)(((p.n0 + BY - 1) / BY) * g.tiles_x);
@@ -1677,20 +1690,8 @@ hipError_t launch_adj_persist_small_t(const T* hframe_t, const T* gframe_t, T* a
     if (hipError_t e = hipMemsetAsync(outbox, 0, persist_small_outbox_bytes(p, (int)sizeof(T)), st)) return e;
     long frame_stride = (long)(2 * p.n);
     int np = pi::nparams(p.hc);
-    pi::PersistArgs pa{};
-    int slot;
-    {
-        std::lock_guard<std::mutex> lk(g_persist.mu);
-        slot = g_persist.next_slot++ % PERSIST_SLOTS;
-        g_persist.watch[slot] = false;
-        ++g_persist.launches;
-    }
-    volatile int* hs = g_persist.host->slot[slot];
-    hs[0] = 0; hs[1] = -1; hs[2] = -1; hs[3] = 0;
-    pa.outbox = outbox; pa.sync = sync; pa.ngroups = ngroups;
-    pa.host = const_cast<int*>(hs);
-    pa.timeout_ticks = (unsigned long long)p.opt.persist_timeout_ms * 100000ull;
-    pa.first_timeout_ticks = (unsigned long long)p.opt.persist_first_timeout_ms * 100000ull;
+    persist_claim(p.opt, r);
+    pi::PersistArgs pa = persist_args(r, outbox, sync, ngroups);
     pa.t_top = t_top;
     pa.pause = p.opt.adj_small_pause >= 0 ? p.opt.adj_small_pause : (grid <= 64 ? 20 : 28);
     pa.masked = mask ? 1 : 0;
@@ -1699,36 +1700,7 @@ hipError_t launch_adj_persist_small_t(const T* hframe_t, const T* gframe_t, T* a
             if (mask[t]) pa.frames[t >> 5] |= 1u << (t & 31);
     hipLaunchKernelGGL(k, dim3(grid), dim3(NT), lds, st, hframe_t, gframe_t, aframe_t, frame_stride, g_h0, partials, np, P, g, pa);
     if (hipError_t e = hipGetLastError()) return e;
-    {
-        std::lock_guard<std::mutex> lk(g_persist.mu);
-        g_persist.watch[slot] = true;
-    }
-    if (!p.opt.persist_handshake) return hipSuccess;
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    while (hs[0] == 0 && hs[3] == 0) {
-        if ((++spins & 0x3ff) == 0) {
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(600)) return hipErrorLaunchTimeOut;
-            std::this_thread::yield();
-        }
-    }
-    if (hs[3] != 0) {
-        std::lock_guard<std::mutex> lk(g_persist.mu);
-        g_persist.watch[slot] = false;
-        ++g_persist.aborts;
-        g_persist.last_group = hs[1];
-        g_persist.last_tile = hs[2];
-        g_persist.disabled[dev] = true;
-        if (!g_persist.warned) {
-            g_persist.warned = true;
-            std::fprintf(stderr, "percnn_pi: the persistent tile sweep could not keep all %u workgroups resident on device %d "
-                                 "(group %d, tile %d: another process / kernel holds CUs, or a CU mask is set); using one launch "
-                                 "per group of steps from now on (percnn_pi_set_option(\"persist_reset\", 1) re-arms it)\n",
-                         grid, dev, (int)hs[1], (int)hs[2]);
-        }
-        return hipErrorLaunchFailure;
-    }
-    return hipSuccess;
+    return persist_launched(st, r, p.opt.persist_handshake, grid, "the persistent tile sweep");
 }
 
 // ---- small-tile / ragged resident FORWARD (pi_fwd2d_persist_small_kernel) ------------------------------------------------------
@@ -1778,40 +1750,13 @@ int fwd_persist_small_by(const Problem& p, int ngroups, hipStream_t st)
     return by;
 }
 
-// wait for the roll call of a resident launch (or its abort); what launch_fwd_persist / launch_adj_persist do inline
-hipError_t persist_wait_roll_call(volatile int* hs, int slot, int dev, unsigned grid, const char* what)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    while (hs[0] == 0 && hs[3] == 0) {
-        if ((++spins & 0x3ff) == 0) {
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(600)) return hipErrorLaunchTimeOut;
-            std::this_thread::yield();
-        }
-    }
-    if (hs[3] != 0) {
-        std::lock_guard<std::mutex> lk(g_persist.mu);
-        g_persist.watch[slot] = false;
-        ++g_persist.aborts;
-        g_persist.last_group = hs[1];
-        g_persist.last_tile = hs[2];
-        g_persist.disabled[dev] = true;
-        if (!g_persist.warned) {
-            g_persist.warned = true;
-            std::fprintf(stderr, "percnn_pi: %s could not keep all %u workgroups resident on device %d (group %d, tile %d: another "
-                                 "process / kernel holds CUs, or a CU mask is set); using one launch per group of steps from now on "
-                                 "(percnn_pi_set_option(\"persist_reset\", 1) re-arms it)\n", what, grid, dev, (int)hs[1], (int)hs[2]);
-        }
-        return hipErrorLaunchFailure;
-    }
-    return hipSuccess;
-}
-
 // frames t0 + 1 .. t0 + 4 * ngroups from frame t0; return values as launch_fwd_persist
 template <typename T, int BY, int NT, bool HALFS = false>
-hipError_t launch_fwd_persist_small_t(T* frame_t0, int ngroups, const T* P, const Problem& p, int dev, hipStream_t st)
+hipError_t launch_fwd_persist_small_t(T* frame_t0, int ngroups, const T* P, const Problem& p, hipStream_t st)
 {
     constexpr int K = 4;
+    pi_host::Resident r;
+    if (!persist_enter(st, r.dev)) return hipErrorNotSupported;
     using TL = pi::Tile<K, TILE_B, BY>;
     pi::TileGeom g = make_tile_geom(p, BY);
     const unsigned grid = (unsigned)(((p.n0 + BY - 1) / BY) * g.tiles_x);
@@ -1820,92 +1765,45 @@ hipError_t launch_fwd_persist_small_t(T* frame_t0, int ngroups, const T* P, cons
     const size_t lds = pi::tile_state_bytes<T, K, TILE_B, BY>() + (size_t)(2 * NGAT + K) * NT * sizeof(int) + 16;
     auto* k = pi::pi_fwd2d_persist_small_kernel<T, K, TILE_B, BY, NT, HALFS>;
     if (hipError_t e = allow_lds(k, lds)) return e;
-    {
-        static int blocks_per_cu[16] = {};                  // per device (per tile height / value type: a template), asked once
-        int dv = 0;
-        if (hipGetDevice(&dv) != hipSuccess || dv < 0 || dv >= 16) { (void)hipGetLastError(); return hipErrorCooperativeLaunchTooLarge; }
-        if (!blocks_per_cu[dv]) {
-            int q = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, k, NT, lds) != hipSuccess || q < 1) { (void)hipGetLastError(); q = -1; }
-            blocks_per_cu[dv] = q;
-        }
-        const int nb = blocks_per_cu[dv];
-        if (nb < 1 || (int64_t)grid > (int64_t)device_cu_count() * nb) return hipErrorCooperativeLaunchTooLarge;
-    }
-    // per-device scratch (shared with the 32 x 32 resident forward): 256 B of sync words | granule outbox: 2 parities x tiles x 2 x 32 x BY
-    const size_t outbox_bytes = (size_t)2 * grid * (2 * TILE_B * BY) * sizeof(unsigned long long);
-    const size_t need = 256 + outbox_bytes;
-    unsigned char* scratch;
-    {
-        std::lock_guard<std::mutex> lk(g_persist.mu);
-        if (g_persist.fwd_scratch_bytes[dev] < need) {
-            if (g_persist.fwd_scratch[dev]) {
-                (void)hipFree(g_persist.fwd_scratch[dev]);
-                g_persist.fwd_scratch[dev] = nullptr;
-                g_persist.fwd_scratch_bytes[dev] = 0;
-            }
-            void* q = nullptr;
-            if (hipMalloc(&q, need) != hipSuccess || !q) { (void)hipGetLastError(); return hipErrorOutOfMemory; }
-            g_persist.fwd_scratch[dev] = q;
-            g_persist.fwd_scratch_bytes[dev] = need;
-        }
-        scratch = static_cast<unsigned char*>(g_persist.fwd_scratch[dev]);
-    }
-    if (hipError_t e = hipMemsetAsync(scratch, 0, need, st)) return e;
+    const int nb = persist_fits(k, NT, lds, r.dev);
+    if (nb < 1 || (int64_t)grid > (int64_t)device_cu_count() * nb) return hipErrorCooperativeLaunchTooLarge;
+    // per-device scratch (shared with the 32 x 32 resident forward): granule outbox of 2 parities x tiles x 2 x 32 x BY
+    if (hipError_t e = persist_scratch((size_t)2 * grid * (2 * TILE_B * BY) * sizeof(unsigned long long), st, r)) return e;
     long frame_stride = (long)(2 * p.n);
-    pi::PersistArgs pa{};
-    int slot;
-    {
-        std::lock_guard<std::mutex> lk(g_persist.mu);
-        slot = g_persist.next_slot++ % PERSIST_SLOTS;
-        g_persist.watch[slot] = false;
-        ++g_persist.launches;
-    }
-    volatile int* hs = g_persist.host->slot[slot];
-    hs[0] = 0; hs[1] = -1; hs[2] = -1; hs[3] = 0;
-    pa.outbox = reinterpret_cast<unsigned long long*>(scratch + 256);
-    pa.sync = reinterpret_cast<unsigned*>(scratch);
-    pa.ngroups = ngroups;
-    pa.host = const_cast<int*>(hs);
-    pa.timeout_ticks = (unsigned long long)p.opt.persist_timeout_ms * 100000ull;             // 100 MHz clock
-    pa.first_timeout_ticks = (unsigned long long)p.opt.persist_first_timeout_ms * 100000ull;
+    persist_claim(p.opt, r);
+    pi::PersistArgs pa = persist_args(r, reinterpret_cast<unsigned long long*>(r.scratch + 256), reinterpret_cast<unsigned*>(r.scratch), ngroups);
     // (32-row tiles -- ragged grids -- at pause 28 | 40 | 48 | 56 | 64 | 80: 500^2 1.77 1.66 1.60 1.57 1.61 1.73, 400^2 1.54 1.51 1.49 1.49 1.56 1.71)
     pa.pause = p.opt.fwd_small_pause >= 0 ? p.opt.fwd_small_pause : (BY == TILE_B ? 52 : (grid <= 64 ? 24 : 28));
     hipLaunchKernelGGL(k, dim3(grid), dim3(NT), lds, st, frame_t0, frame_stride, P, g, pa);
     if (hipError_t e = hipGetLastError()) return e;
-    {
-        std::lock_guard<std::mutex> lk(g_persist.mu);
-        g_persist.watch[slot] = true;
-    }
-    if (!p.opt.persist_handshake) return hipSuccess;        // fire and forget (an abort: PERCNN_PI_EASYNC at the next entry point)
-    return persist_wait_roll_call(hs, slot, dev, grid, "the resident forward rollout (small tiles)");
+    return persist_launched(st, r, p.opt.persist_handshake, grid, "the resident forward rollout (small tiles)");
 }
 
 template <typename T>
-hipError_t launch_fwd_persist_small(int by, T* frame_t0, int ngroups, const T* P, const Problem& p, int dev, hipStream_t st)
+hipError_t launch_fwd_persist_small(int by, T* frame_t0, int ngroups, const T* P, const Problem& p, hipStream_t st)
 {
     // (round 6: 32 x 8 tiles on half-strips, 512 lanes; fwd_small_half=0: whole strips on 256 lanes)
-    if (by == 8 && p.opt.fwd_small_half) return launch_fwd_persist_small_t<T, 8, 512, true>(frame_t0, ngroups, P, p, dev, st);
-    if (by == 8) return launch_fwd_persist_small_t<T, 8, 256>(frame_t0, ngroups, P, p, dev, st);
-    if (by == 16 && p.opt.fwd_small_half) return launch_fwd_persist_small_t<T, 16, 640, true>(frame_t0, ngroups, P, p, dev, st);
-    if (by == 16) return launch_fwd_persist_small_t<T, 16, 320>(frame_t0, ngroups, P, p, dev, st);
-    if (p.opt.fwd_small_half) return launch_fwd_persist_small_t<T, TILE_B, 1024, true>(frame_t0, ngroups, P, p, dev, st);
-    return launch_fwd_persist_small_t<T, TILE_B, 512>(frame_t0, ngroups, P, p, dev, st);
+    if (by == 8 && p.opt.fwd_small_half) return launch_fwd_persist_small_t<T, 8, 512, true>(frame_t0, ngroups, P, p, st);
+    if (by == 8) return launch_fwd_persist_small_t<T, 8, 256>(frame_t0, ngroups, P, p, st);
+    if (by == 16 && p.opt.fwd_small_half) return launch_fwd_persist_small_t<T, 16, 640, true>(frame_t0, ngroups, P, p, st);
+    if (by == 16) return launch_fwd_persist_small_t<T, 16, 320>(frame_t0, ngroups, P, p, st);
+    if (p.opt.fwd_small_half) return launch_fwd_persist_small_t<T, TILE_B, 1024, true>(frame_t0, ngroups, P, p, st);
+    return launch_fwd_persist_small_t<T, TILE_B, 512>(frame_t0, ngroups, P, p, st);
 }
 
 template <typename T>
 hipError_t launch_adj_persist_small(const T* hframe_t, const T* gframe_t, T* aframe_t, T* g_h0, int t_top, const unsigned char* mask,
                                     int ngroups, double* partials, unsigned long long* outbox, unsigned* sync, const T* P,
-                                    const Problem& p, int dev, hipStream_t st)
+                                    const Problem& p, hipStream_t st)
 {
     if (tile_by_for(p) == 16 && p.opt.adj_small_half)
-        return launch_adj_persist_small_t<T, 16, 640, true>(hframe_t, gframe_t, aframe_t, g_h0, t_top, mask, ngroups, partials, outbox, sync, P, p, dev, st);
+        return launch_adj_persist_small_t<T, 16, 640, true>(hframe_t, gframe_t, aframe_t, g_h0, t_top, mask, ngroups, partials, outbox, sync, P, p, st);
     if (tile_by_for(p) == 16)
-        return launch_adj_persist_small_t<T, 16, 320>(hframe_t, gframe_t, aframe_t, g_h0, t_top, mask, ngroups, partials, outbox, sync, P, p, dev, st);
+        return launch_adj_persist_small_t<T, 16, 320>(hframe_t, gframe_t, aframe_t, g_h0, t_top, mask, ngroups, partials, outbox, sync, P, p, st);
     // (round 6: half-strips on 512 lanes -- two waves per SIMD; adj_small_half=0: whole strips on 256 lanes)
     if (p.opt.adj_small_half)
-        return launch_adj_persist_small_t<T, 8, 512, true>(hframe_t, gframe_t, aframe_t, g_h0, t_top, mask, ngroups, partials, outbox, sync, P, p, dev, st);
-    return launch_adj_persist_small_t<T, 8, 256>(hframe_t, gframe_t, aframe_t, g_h0, t_top, mask, ngroups, partials, outbox, sync, P, p, dev, st);
+        return launch_adj_persist_small_t<T, 8, 512, true>(hframe_t, gframe_t, aframe_t, g_h0, t_top, mask, ngroups, partials, outbox, sync, P, p, st);
+    return launch_adj_persist_small_t<T, 8, 256>(hframe_t, gframe_t, aframe_t, g_h0, t_top, mask, ngroups, partials, outbox, sync, P, p, st);
 }
 
 // ---- workspace carving -------------------------------------------------------------------------
@@ -2461,24 +2359,22 @@ int rollout_fwd_impl(T* traj, const T* P, int hc, int ndim, const int64_t* shape
         // launch-per-group kernel's trajectory bit for bit); an aborted launch is recomputed below, launch by launch
         {
             const int ngroups = K == 4 ? T_steps / K : 0;
-            int pdev = 0;
             const bool big = fwd_persist_ok<T>(p, ngroups, st);
             // ... and the grids the 32 x 32 flavour does not take -- small-tile regime, ragged grids, fewer than 16 tiles -- on
             // pi_fwd2d_persist_small_kernel (round 5; float32)
             int small_by = 0;
             if constexpr (sizeof(T) == 4) small_by = big ? (fwd_prefers_16_rows<T>(p) ? 16 : 0) : fwd_persist_small_by<T>(p, ngroups, st);
-            if ((big || small_by) && persist_enter(st, pdev)) {
+            if (big || small_by) {
                 hipError_t e;
                 if constexpr (sizeof(T) == 4)
-                    e = (big && !small_by) ? launch_fwd_persist<T>(traj, ngroups, P, p, pdev, st)
-                            : launch_fwd_persist_small<T>(small_by, traj, ngroups, P, p, pdev, st);
+                    e = (big && !small_by) ? launch_fwd_persist<T>(traj, ngroups, P, p, st)
+                            : launch_fwd_persist_small<T>(small_by, traj, ngroups, P, p, st);
                 else
-                    e = launch_fwd_persist<T>(traj, ngroups, P, p, pdev, st);
-                if (e == hipSuccess) { t = K * ngroups; persist_leave(st, pdev); }
-                else if (e == hipErrorLaunchTimeOut) return (int)e;
-                else {
-                    (void)hipGetLastError();                // not resident / not supported / aborted
-                    if (e == hipErrorLaunchFailure) persist_leave(st, pdev);
+                    e = launch_fwd_persist<T>(traj, ngroups, P, p, st);
+                switch (resident_outcome(e)) {
+                case ResidentRun::ran: t = K * ngroups; break;
+                case ResidentRun::fatal: return (int)e;
+                default: break;                             // frames it may have written are recomputed below
                 }
             }
         }
@@ -2602,6 +2498,16 @@ int rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* mask, 
         if (hipError_t e = hipStreamWaitEvent(ss->stream, ev, 0)) return (int)e;
     }
     int t_cur = t_top;
+    // a resident launch of the sweep down to frame t_end has returned `e`: it runs (t_cur = t_end), or the launch-per-group /
+    // -per-step path below takes over from t_cur -- on partial rows started over if the launch got as far as adding to them
+    auto resident_sweep = [&](hipError_t e, int t_end) -> int {
+        switch (resident_outcome(e)) {
+        case ResidentRun::ran: t_cur = t_end; return 0;
+        case ResidentRun::fatal: return (int)e;
+        case ResidentRun::fall_back_clear: return (int)hipMemsetAsync(w.partials, 0, w.partials_bytes, st);
+        default: return 0;
+        }
+    };
     if (tile_eligible<T>(p, {traj, g_traj, g_h0, adj}, true)) {
         const int K = (p.opt.tile_k == 8 && p.hc != 0) ? 4 : p.opt.tile_k;
         rows = (unsigned)tile_count<T>(p, true);
@@ -2615,21 +2521,10 @@ int rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* mask, 
                 auto* outbox = reinterpret_cast<unsigned long long*>(adj + (size_t)(t_end + 1) * frame);
                 // roll-call / abort words: the last partial row (zeroed above; tiles <= #CUs << MAX_BWD_BLOCKS rows are in use)
                 unsigned* sync = reinterpret_cast<unsigned*>(w.partials + (size_t)(MAX_BWD_BLOCKS - 1) * pi::nparams(p.hc));
-                int pdev = 0;
-                if (persist_enter(st, pdev)) {
-                    const hipError_t e = launch_adj_persist<T>(traj + (size_t)t_cur * frame, g_traj + (size_t)t_cur * frame,
-                                                               adj + (size_t)t_cur * frame, t_end == 0 ? g_h0 : nullptr, t_cur,
-                                                               mask, ngroups, w.partials, outbox, sync, P, p, pdev, st);
-                    if (e == hipSuccess) { t_cur = t_end; persist_leave(st, pdev); }
-                    else if (e == hipErrorLaunchTimeOut) return (int)e;
-                    else {
-                        (void)hipGetLastError();            // not resident / not supported / aborted: the launch-per-group path
-                        if (e == hipErrorLaunchFailure) {   // it RAN and gave up: workgroups that were already through may have
-                            persist_leave(st, pdev);        // added to their partial rows -- start the rows over
-                            if (hipError_t e2 = hipMemsetAsync(w.partials, 0, w.partials_bytes, st)) return (int)e2;
-                        }
-                    }
-                }
+                if (int rc = resident_sweep(launch_adj_persist<T>(traj + (size_t)t_cur * frame, g_traj + (size_t)t_cur * frame,
+                                                                  adj + (size_t)t_cur * frame, t_end == 0 ? g_h0 : nullptr, t_cur,
+                                                                  mask, ngroups, w.partials, outbox, sync, P, p, st), t_end))
+                    return rc;
             }
         }
         // the small-tile regime (32 x 8 tiles, split schedule): the same, with every adjoint frame written and the granule
@@ -2641,21 +2536,10 @@ int rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* mask, 
                 const int t_end = t_cur - K * ngroups;
                 auto* outbox = reinterpret_cast<unsigned long long*>(reinterpret_cast<unsigned char*>(w.partials) + w.partials_bytes);
                 unsigned* sync = reinterpret_cast<unsigned*>(w.partials + (size_t)(MAX_BWD_BLOCKS - 1) * pi::nparams(p.hc));
-                int pdev = 0;
-                if (persist_enter(st, pdev)) {
-                    const hipError_t e = launch_adj_persist_small<T>(traj + (size_t)t_cur * frame, g_traj + (size_t)t_cur * frame,
-                                                                     adj + (size_t)t_cur * frame, t_end == 0 ? g_h0 : nullptr, t_cur,
-                                                                     mask, ngroups, w.partials, outbox, sync, P, p, pdev, st);
-                    if (e == hipSuccess) { t_cur = t_end; persist_leave(st, pdev); }
-                    else if (e == hipErrorLaunchTimeOut) return (int)e;
-                    else {
-                        (void)hipGetLastError();
-                        if (e == hipErrorLaunchFailure) {
-                            persist_leave(st, pdev);
-                            if (hipError_t e2 = hipMemsetAsync(w.partials, 0, w.partials_bytes, st)) return (int)e2;
-                        }
-                    }
-                }
+                if (int rc = resident_sweep(launch_adj_persist_small<T>(traj + (size_t)t_cur * frame, g_traj + (size_t)t_cur * frame,
+                                                                        adj + (size_t)t_cur * frame, t_end == 0 ? g_h0 : nullptr, t_cur,
+                                                                        mask, ngroups, w.partials, outbox, sync, P, p, st), t_end))
+                    return rc;
             }
         }
         for (; t_cur - K >= 0; t_cur -= K) {
@@ -2674,14 +2558,8 @@ int rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* mask, 
         Res3dPlan rp;
         if (t_cur == t_top && direct_sweep && fuse && !loss && res3d_plan(p, t_top, sizeof(T), rp)) {
             const T* gin = top_in_place ? top_in_place : adj + (size_t)t_top * frame;
-            const hipError_t e = launch_adj_res3d(traj, g_traj, mask, gin, g_h0, t_top, w.partials, P, p, rp, st);
-            if (e == hipSuccess) { t_cur = 0; rows = (unsigned)rp.nblk; }
-            else if (e == hipErrorLaunchTimeOut) return (int)e;
-            else {
-                (void)hipGetLastError();
-                if (e == hipErrorLaunchFailure)             // it ran and gave up: blocks that were through may have added to their rows
-                    if (hipError_t e2 = hipMemsetAsync(w.partials, 0, w.partials_bytes, st)) return (int)e2;
-            }
+            if (int rc = resident_sweep(launch_adj_res3d(traj, g_traj, mask, gin, g_h0, t_top, w.partials, P, p, rp, st), 0)) return rc;
+            if (t_cur == 0) rows = (unsigned)rp.nblk;       // it ran (t_top >= 16 here): one partial row per block
         }
     }
     for (int t = t_cur; t >= 1; --t) {
@@ -3829,6 +3707,8 @@ int debug_plan_impl(int hc, int ndim, const int64_t* shape, const char* options,
 // They share the residency guard of the 2D resident kernels: one resident grid per device at a time (calls on other streams
 // are detected and refused), host-mapped status slots, a per-device scratch (sync words + granule outbox), the handshake on the
 // roll call and the "disabled after an abort" state (percnn_pi_persist_status / persist_reset report and re-arm both).
+// No step of the protocol is written here: these are the functions at PersistGuard, under the process-wide options (the 2D
+// launchers take a call's own).
 namespace pi_host {
 int resident_async_error() { return persist_async_error(); }
 int resident_cu_count() { return device_cu_count(); }
@@ -3842,46 +3722,16 @@ hipError_t resident_begin(void* stream, size_t outbox_bytes, Resident& r)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return hipErrorNotSupported; }
     if (!persist_enter(st, r.dev)) return hipErrorNotSupported;
-    const size_t need = 256 + outbox_bytes;
-    {
-        std::lock_guard<std::mutex> lk(g_persist.mu);
-        if (g_persist.fwd_scratch_bytes[r.dev] < need) {
-            if (g_persist.fwd_scratch[r.dev]) {
-                (void)hipFree(g_persist.fwd_scratch[r.dev]);
-                g_persist.fwd_scratch[r.dev] = nullptr;
-                g_persist.fwd_scratch_bytes[r.dev] = 0;
-            }
-            void* q = nullptr;
-            if (hipMalloc(&q, need) != hipSuccess || !q) { (void)hipGetLastError(); return hipErrorOutOfMemory; }
-            g_persist.fwd_scratch[r.dev] = q;
-            g_persist.fwd_scratch_bytes[r.dev] = need;
-        }
-        r.scratch = static_cast<unsigned char*>(g_persist.fwd_scratch[r.dev]);
-        r.slot = g_persist.next_slot++ % PERSIST_SLOTS;
-        g_persist.watch[r.slot] = false;
-    }
-    if (hipError_t e = hipMemsetAsync(r.scratch, 0, need, st)) return e;
-    r.hs = g_persist.host->slot[r.slot];
-    r.hs[0] = 0; r.hs[1] = -1; r.hs[2] = -1; r.hs[3] = 0;
-    r.timeout_ticks = (unsigned long long)o.persist_timeout_ms * 100000ull;                 // 100 MHz clock
-    r.first_timeout_ticks = (unsigned long long)o.persist_first_timeout_ms * 100000ull;
+    if (hipError_t e = persist_scratch(outbox_bytes, st, r)) return e;
+    persist_claim(o, r);
     return hipSuccess;
 }
 // after the launch: hipSuccess = resident and running; hipErrorLaunchFailure = it aborted (the caller recomputes launch by launch)
 hipError_t resident_launched(void* stream, Resident& r, unsigned grid, const char* what)
 {
-    auto st = static_cast<hipStream_t>(stream);
     int handshake;
     { std::lock_guard<std::mutex> lk(g_defaults_mu); handshake = g_defaults.persist_handshake; }
-    {
-        std::lock_guard<std::mutex> lk(g_persist.mu);
-        g_persist.watch[r.slot] = true;
-        ++g_persist.launches;                               // (counted here: the caller's launch has been enqueued without error)
-    }
-    hipError_t e = hipSuccess;
-    if (handshake) e = persist_wait_roll_call(r.hs, r.slot, r.dev, grid, what);
-    if (e == hipSuccess || e == hipErrorLaunchFailure) persist_leave(st, r.dev);
-    return e;
+    return persist_launched(static_cast<hipStream_t>(stream), r, handshake, grid, what);
 }
 }  // namespace pi_host
 

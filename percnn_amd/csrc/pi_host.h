@@ -1,5 +1,7 @@
 // pi_host.h -- what the library's translation units share on the HOST side (pi_abi.hip defines it, pi_s1_abi.hip uses it):
 // the residency guard of the resident ("persistent") launches.  Not part of the C-ABI.
+// The protocol itself -- slot claim, per-device scratch, "launched" step with the roll-call wait and the abort bookkeeping --
+// is written once, at PersistGuard in pi_abi.hip; resident_begin / resident_launched are those steps for another translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
