@@ -718,6 +718,54 @@ int percnn_pi_ensemble_rollout_bwd_sqerr_f64(const double *traj, const double *t
                                           void *workspace, size_t workspace_bytes, const double *params, int hc, int ndim,
                                           const int64_t *shape, int batch, int T, const char *options, void *stream);
 
+/* ---- Sparse observations: the losses per sample on a sub-lattice of the selected frames, against a compact target -----------------
+ * The reference trains on coarse measurements, mse_loss(output[:-1:15, :, ::2, ::2, ::2], truth[::15, :, ::2, ::2, ::2]).  With
+ * strides (s_0, .., s_{ndim-1}), each >= 1, Sc_d = ceil(S_d / s_d), and the n frames selected by frame_mask numbered k = 0 .. n-1
+ * in time order:
+ *   L_b = scale' * sum_k sum_{c, x on the lattice} (traj_{t_k}[b][c][x] - target_c[k][b][c][x / s])^2 ,   lattice: x_d % s_d == 0
+ *   dL/dh_t[b] = a_b * (h_t[b] - target_c[k][b][x / s]) at the lattice points of frame t = t_k, 0 at every other point and in every
+ *   other frame;   a_b = scale * dev_scale[b]   (scale = 2 * scale'; dev_scale as above), rounded as above: one subtraction, one
+ *   multiplication.  Formed inside the batched / ensemble sweep: no dL/dtraj buffer, and the observed frames are not scattered.
+ *   strides    const int *, ndim entries (host memory)
+ *   frame_mask host array of T + 1 (nframes) bytes, NULL = every frame
+ *   target_c   [n][B][2][*Sc] of the compute type, compact in time as well as in space, NULL = 0.  It is read element by element:
+ *              no alignment beyond that of its type is asked of it.
+ *   traj, g_h0, param_grad, params, options, workspace: as in "Losses per sample" -- the workspace sizes are those of
+ *   percnn_pi_{batch,ensemble}_rollout_bwd_workspace_bytes and percnn_pi_batch_traj_sqerr_workspace_bytes.
+ * batch == 1 runs the same launches with one sample (it is NOT the unbatched sweep, which may dispatch a resident kernel that has
+ * no such form); the workspace queries above return the unbatched sizes for batch == 1, which are at least what these launches
+ * need.  All strides 1 is the dense loss with a time-compact target: the sweep's results and the loss value are those of
+ * percnn_pi_{batch,ensemble}_rollout_bwd_sqerr_* / percnn_pi_batch_traj_sqerr_* bit for bit (batch > 1).
+ * Every adjoint field is bit-identical to the batched / ensemble sweep on the materialised gradient; a zero may differ in sign.
+ * Validation before any launch: as in "Losses per sample"; in addition strides == NULL, a stride < 1 or hc == -1 (also with
+ * batch == 1) -> PERCNN_PI_EINVAL.  The loss value is accumulated in float64 in a fixed order: bit-identical from run to run. */
+int percnn_pi_batch_traj_obs_sqerr_f32(const float *traj, const float *target_c, const unsigned char *frame_mask, int nframes,
+                                       int ndim, const int64_t *shape, const int *strides, int batch, double scale, float *out,
+                                       void *workspace, size_t workspace_bytes, void *stream);
+int percnn_pi_batch_traj_obs_sqerr_f64(const double *traj, const double *target_c, const unsigned char *frame_mask, int nframes,
+                                       int ndim, const int64_t *shape, const int *strides, int batch, double scale, double *out,
+                                       void *workspace, size_t workspace_bytes, void *stream);
+int percnn_pi_batch_rollout_bwd_obs_sqerr_f32(const float *traj, const float *target_c, const unsigned char *frame_mask,
+                                              const int *strides, double scale, const float *dev_scale, float *g_h0,
+                                              double *param_grad, void *workspace, size_t workspace_bytes, const float *params,
+                                              int hc, int ndim, const int64_t *shape, int batch, int T, const char *options,
+                                              void *stream);
+int percnn_pi_batch_rollout_bwd_obs_sqerr_f64(const double *traj, const double *target_c, const unsigned char *frame_mask,
+                                              const int *strides, double scale, const double *dev_scale, double *g_h0,
+                                              double *param_grad, void *workspace, size_t workspace_bytes, const double *params,
+                                              int hc, int ndim, const int64_t *shape, int batch, int T, const char *options,
+                                              void *stream);
+int percnn_pi_ensemble_rollout_bwd_obs_sqerr_f32(const float *traj, const float *target_c, const unsigned char *frame_mask,
+                                                 const int *strides, double scale, const float *dev_scale, float *g_h0,
+                                                 double *param_grad, void *workspace, size_t workspace_bytes, const float *params,
+                                                 int hc, int ndim, const int64_t *shape, int batch, int T, const char *options,
+                                                 void *stream);
+int percnn_pi_ensemble_rollout_bwd_obs_sqerr_f64(const double *traj, const double *target_c, const unsigned char *frame_mask,
+                                                 const int *strides, double scale, const double *dev_scale, double *g_h0,
+                                                 double *param_grad, void *workspace, size_t workspace_bytes, const double *params,
+                                                 int hc, int ndim, const int64_t *shape, int batch, int T, const char *options,
+                                                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,8 @@ loss;  ``synthetic`` initial states for benchmarks / tests.
 from ._lib import build, lib, set_option, LIB_PATH  # noqa: F401
 from .functional import (pi_step, pi_rollout, pack_params, contract_block, param_count, rollout_fwd_, rollout_bwd,  # noqa: F401
                          step_fwd, step_bwd, PiStepFunction, PiRolloutFunction, pi_step_batched, pi_rollout_batched,
-                         pi_step_ensemble, pi_rollout_ensemble, pi_rollout_sqerr_batched, pi_rollout_sqerr_ensemble)
+                         pi_step_ensemble, pi_rollout_ensemble, pi_rollout_sqerr_batched, pi_rollout_sqerr_ensemble,
+                         pi_rollout_obs_sqerr_batched, pi_rollout_obs_sqerr_ensemble)
 from .modules import RCNNCell, RCNN, Upscaler, Stage3LambdaOmegaCell, Stage3BurgersCell, gs2d_cell, gs3d_cell, lo2d_cell, laplace_stencil, CellEnsemble  # noqa: F401
 
 from . import ops  # noqa: F401  (registers torch.ops.percnn.*)

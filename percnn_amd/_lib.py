@@ -67,7 +67,8 @@ EXPORTS = [
                 "rollout_bwd_opt", "rollout_bwd_sqerr", "traj_sqerr", "step_bwd_rows", "bwd_rows_finish", "rollout_bwd_top",
                 "batch_step_fwd", "batch_step_bwd", "batch_rollout_fwd", "batch_rollout_bwd", "ensemble_step_fwd",
                 "ensemble_step_bwd", "ensemble_rollout_fwd", "ensemble_rollout_bwd", "batch_traj_sqerr",
-                "batch_rollout_bwd_sqerr", "ensemble_rollout_bwd_sqerr")] + [
+                "batch_rollout_bwd_sqerr", "ensemble_rollout_bwd_sqerr", "batch_traj_obs_sqerr",
+                "batch_rollout_bwd_obs_sqerr", "ensemble_rollout_bwd_obs_sqerr")] + [
     "percnn_pi_batch_traj_sqerr_workspace_bytes",
     "percnn_pi_batch_bwd_workspace_bytes", "percnn_pi_batch_rollout_bwd_workspace_bytes",
     "percnn_pi_ensemble_bwd_workspace_bytes", "percnn_pi_ensemble_rollout_bwd_workspace_bytes",
@@ -272,6 +273,13 @@ def lib() -> ctypes.CDLL:
         f.restype, f.argtypes = ci, [vp, vp, cs, cd, vp, vp, vp, vp, sz, vp, ci, ci, i64p, ci, ci, cs, vp]
         f = getattr(L, f"percnn_pi_ensemble_rollout_bwd_sqerr_{suf}")
         f.restype, f.argtypes = ci, [vp, vp, cs, cd, vp, vp, vp, vp, sz, vp, ci, ci, i64p, ci, ci, cs, vp]
+        ip = ctypes.POINTER(ctypes.c_int)
+        f = getattr(L, f"percnn_pi_batch_traj_obs_sqerr_{suf}")
+        f.restype, f.argtypes = ci, [vp, vp, cs, ci, ci, i64p, ip, ci, cd, vp, vp, sz, vp]
+        f = getattr(L, f"percnn_pi_batch_rollout_bwd_obs_sqerr_{suf}")
+        f.restype, f.argtypes = ci, [vp, vp, cs, ip, cd, vp, vp, vp, vp, sz, vp, ci, ci, i64p, ci, ci, cs, vp]
+        f = getattr(L, f"percnn_pi_ensemble_rollout_bwd_obs_sqerr_{suf}")
+        f.restype, f.argtypes = ci, [vp, vp, cs, ip, cd, vp, vp, vp, vp, sz, vp, ci, ci, i64p, ci, ci, cs, vp]
     L.percnn_pi_batch_traj_sqerr_workspace_bytes.restype = sz
     L.percnn_pi_batch_traj_sqerr_workspace_bytes.argtypes = [ci]
     L.percnn_pi_batch_bwd_workspace_bytes.restype = sz

@@ -12,6 +12,7 @@
 #include <mutex>
 #include <thread>
 #include <tuple>
+#include <vector>
 
 #include "../../include/percnn_pi.h"
 #include "pi_kernels.h"
@@ -2640,7 +2641,8 @@ hipError_t launch_fwd_tile_b(T* frame_t, const T* P, const Problem& p, int batch
 
 template <typename T, int HC, int K, int NT, int BY = TILE_B, bool MOM = false, int BX = TILE_B>
 hipError_t launch_adj_tile_b(const T* hframe_t, const T* gframe_t, T* aframe_t, unsigned inj_mask, T* g_h0, int steps_to_zero,
-                             double* partials, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows = -1)
+                             double* partials, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows = -1,
+                             const pi::ObsTile* ob = nullptr)
 {
     using TL = pi::Tile<K, BX, BY>;
     const pi::TileGeom g = make_tile_geom(p, BY, BX);
@@ -2663,6 +2665,14 @@ hipError_t launch_adj_tile_b(const T* hframe_t, const T* gframe_t, T* aframe_t, 
     // as launch_fwd_tile_b: the target type picks the trailing pack (`int rows`)
     void (*ens)(const T*, const T*, T*, long, long, unsigned, T*, int, double*, int, const T*, pi::TileGeom, int) =
         pi::pi_adj2d_tile_kernel<T, HC, K, BX, BY, NT, MOM, long>;
+    if (ob) {                                   // sparse-observation flavours: the lattice behind the other trailing arguments
+        static_assert(K <= 8, "ObsTile::coff");
+        void (*bo)(const T*, const T*, T*, long, long, unsigned, T*, int, double*, int, const T*, pi::TileGeom, pi::ObsTile) =
+            pi::pi_adj2d_tile_kernel<T, HC, K, BX, BY, NT, MOM, long>;
+        void (*eo)(const T*, const T*, T*, long, long, unsigned, T*, int, double*, int, const T*, pi::TileGeom, int, pi::ObsTile) =
+            pi::pi_adj2d_tile_kernel<T, HC, K, BX, BY, NT, MOM, long>;
+        return ens_rows >= 0 ? go(eo, ens_rows, *ob) : go(bo, *ob);
+    }
     return ens_rows >= 0 ? go(ens, ens_rows) : go(pi::pi_adj2d_tile_kernel<T, HC, K, BX, BY, NT, MOM, long>);
 }
 
@@ -2684,13 +2694,14 @@ hipError_t fwd_tile_b(T* frame_t, const T* P, const Problem& p, int batch, hipSt
 
 template <typename T>
 hipError_t adj_tile_b(const T* hframe_t, const T* gframe_t, T* aframe_t, unsigned inj_mask, T* g_h0, int steps_to_zero,
-                      double* partials, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows = -1)
+                      double* partials, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows = -1,
+                      const pi::ObsTile* ob = nullptr)
 {
     if constexpr (sizeof(T) == 4) {
         const bool fused = tile_fuse_ok<T>(p);
 #define CALL_WIDE_B(NT, BY, BX, MOM) launch_adj_tile_b<T, pi::POLY, 4, NT, BY, MOM, BX>(hframe_t, gframe_t, aframe_t, inj_mask, \
                                                                                       g_h0, steps_to_zero, partials, P, p, batch, st, \
-                                                                                      ens_rows)
+                                                                                      ens_rows, ob)
         switch (tile_wide_for<T>(p, true)) {
             case 1: return fused ? CALL_WIDE_B(640, 40, 32, true) : CALL_WIDE_B(640, 40, 32, false);
             case 2: return fused ? CALL_WIDE_B(768, 40, 40, true) : CALL_WIDE_B(768, 40, 40, false);
@@ -2700,9 +2711,9 @@ hipError_t adj_tile_b(const T* hframe_t, const T* gframe_t, T* aframe_t, unsigne
     }
     if (tile_fuse_ok<T>(p))
         return launch_adj_tile_b<T, pi::POLY, 4, 512, TILE_B, true>(hframe_t, gframe_t, aframe_t, inj_mask, g_h0, steps_to_zero,
-                                                                    partials, P, p, batch, st, ens_rows);
+                                                                    partials, P, p, batch, st, ens_rows, ob);
 #define CALL_ATB(HC, K, NT, ...) launch_adj_tile_b<T, HC, K, NT, ##__VA_ARGS__>(hframe_t, gframe_t, aframe_t, inj_mask, g_h0, \
-                                                                               steps_to_zero, partials, P, p, batch, st, ens_rows)
+                                                                               steps_to_zero, partials, P, p, batch, st, ens_rows, ob)
     PI_TILE_DISPATCH(CALL_ATB);
 #undef CALL_ATB
 }
@@ -2726,7 +2737,7 @@ hipError_t launch_fwd_b(const T* h, T* out, const T* P, const Problem& p, int ba
 
 template <typename T, int NDIM, int HC, int VEC, bool WGRAD>
 hipError_t launch_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* partials, const T* P, const Problem& p, int batch,
-                        hipStream_t st, unsigned* rows_out, int ens_rows = -1)
+                        hipStream_t st, unsigned* rows_out, int ens_rows = -1, const pi::ObsLat* ol = nullptr)
 {
     Geom g = make_geom(p);
     const int block = direct_block(p, g, VEC);
@@ -2745,9 +2756,12 @@ hipError_t launch_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* par
     };
     if (ens_rows >= 0) {
         if (grid > (unsigned)ens_rows) return (hipError_t)PERCNN_PI_ETOOLARGE;   // ens_rows bounds every launch (ens_rows_for)
+        if (ol) return go(pi::pi_bwd_kernel<T, NDIM, HC, VEC, WGRAD, 1, long, int, pi::ObsLat>, ens_rows, *ol);
         return go(pi::pi_bwd_kernel<T, NDIM, HC, VEC, WGRAD, 1, long, int>, ens_rows);
     }
-    const hipError_t e = go(pi::pi_bwd_kernel<T, NDIM, HC, VEC, WGRAD, 1, long>);
+    // (ol: the sparse-observation flavours, `inj` = the compact target frame)
+    const hipError_t e = ol ? go(pi::pi_bwd_kernel<T, NDIM, HC, VEC, WGRAD, 1, long, pi::ObsLat>, *ol)
+                            : go(pi::pi_bwd_kernel<T, NDIM, HC, VEC, WGRAD, 1, long>);
     if (e == hipSuccess && rows_out) *rows_out = grid * (unsigned)batch;
     return e;
 }
@@ -2763,10 +2777,11 @@ hipError_t step_fwd_b(const T* h, T* out, const T* P, const Problem& p, int batc
 
 template <typename T, bool WGRAD>
 hipError_t step_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* partials, const T* P, const Problem& p, int batch,
-                      hipStream_t st, unsigned* rows_out, int ens_rows = -1)
+                      hipStream_t st, unsigned* rows_out, int ens_rows = -1, const pi::ObsLat* ol = nullptr)
 {
-    const int vec = pick_vec<T>(p, {h, G, inj, Gp});
-#define CALL_BWDB(NDIM, HC, VEC) launch_bwd_b<T, NDIM, HC, VEC, WGRAD>(h, G, inj, Gp, partials, P, p, batch, st, rows_out, ens_rows)
+    // (the compact target of the sparse-observation flavours is read element-wise: its alignment does not pick the lanes)
+    const int vec = pick_vec<T>(p, {h, G, ol ? nullptr : inj, Gp});
+#define CALL_BWDB(NDIM, HC, VEC) launch_bwd_b<T, NDIM, HC, VEC, WGRAD>(h, G, inj, Gp, partials, P, p, batch, st, rows_out, ens_rows, ol)
     PI_DISPATCH(CALL_BWDB);
 #undef CALL_BWDB
 }
@@ -2855,6 +2870,61 @@ hipError_t loss_grad_frame_b(const T* h, const T* target, T* dst, const Problem&
     return hipGetLastError();
 }
 
+// ---- sparse-observation loss form (pi_device.h, ObsLat): the loss lives on the lattice x_d % s_d == 0 of the selected frames and
+// the target is compact in space and time, [n][B][2][*Sc] with one frame per selected frame
+struct ObsHost {
+    pi::ObsLat lat;
+    const void* target;              // compact target, nullptr = 0
+    std::vector<long> cframe;        // trajectory frame t -> element offset of its compact frame (selected frames only)
+    int nsel;                        // selected frames
+};
+
+// strides: ndim entries >= 1; mask: nframes bytes or nullptr = every frame
+int make_obs(const Problem& p, int batch, const int* strides, const void* target, const unsigned char* mask, int nframes, ObsHost& o)
+{
+    if (!strides) return PERCNN_PI_EINVAL;
+    for (int a = 0; a < p.ndim; ++a)
+        if (strides[a] < 1) return PERCNN_PI_EINVAL;
+    const int64_t ext[3] = {p.ndim == 3 ? p.n0 : 1, p.ndim == 3 ? p.n1 : p.n0, p.W};
+    o.lat.cs = 1;
+    for (int a = 0; a < 3; ++a) {
+        const int st = (p.ndim == 2 && a == 0) ? 1 : strides[a - (3 - p.ndim)];
+        o.lat.s[a] = st;
+        o.lat.d[a] = make_fastdiv((unsigned)st);
+        o.lat.sc[a] = (int)((ext[a] + st - 1) / st);
+        o.lat.cs *= o.lat.sc[a];
+    }
+    o.lat.has_target = target ? 1 : 0;
+    o.target = target;
+    o.cframe.assign((size_t)std::max(nframes, 0), 0);
+    o.nsel = 0;
+    for (int t = 0; t < nframes; ++t)
+        if (!mask || mask[t]) o.cframe[t] = (long)(o.nsel++) * batch * 2 * o.lat.cs;
+    return 0;
+}
+
+// the top frame of a sparse-observation sweep (and dL/dh0 of a loss over frame 0 alone): the sparse form of loss_grad_frame_b --
+// a dense frame [B][2][*S], zero off the lattice and a_b * (h - target_c) on it; target_c = this frame's compact target or nullptr
+template <typename T>
+hipError_t obs_grad_frame_b(const T* h, const T* target_c, T* dst, const Problem& p, int batch, const pi::ObsLat& lat, hipStream_t st)
+{
+    const long sample = 2 * p.n, rows = 2 * p.n0 * p.n1;
+    const unsigned nb = (unsigned)std::min<long>(2048, rows);
+    hipLaunchKernelGGL((pi::pi_loss_grad_kernel<T, 1, long, int, int, pi::ObsLat>), dim3(nb, (unsigned)batch), dim3(256), 0, st, h,
+                       target_c, dst, sample, p.loss, sample, (int)(p.ndim == 3 ? p.n1 : p.n0), (int)p.W, lat);   // (axes as ObsLat's)
+    return hipGetLastError();
+}
+
+// the lattice description of one tile launch from frame t: sub-step q injects frame t - 1 - q (if bit q of `mask`)
+pi::ObsTile obs_tile(const ObsHost& oh, unsigned mask, int t, int K)
+{
+    pi::ObsTile ob{};
+    ob.lat = oh.lat;
+    ob.target = oh.target;
+    for (int q = 0; q < K && q < 8; ++q) ob.coff[q] = (mask >> q) & 1u ? oh.cframe[(size_t)(t - 1 - q)] : 0;
+    return ob;
+}
+
 // loss != nullptr (both sweeps below, as rollout_bwd_impl): no dL/dtraj exists; `g_traj` is the TARGET trajectory [T+1][B][2][*S]
 // (mode 2) or ignored (mode 1), `mask` selects the frames inside the loss and loss->dev holds B factors
 int sweep_loss_form(const pi::LossInj* loss, const void* traj, const void*& g_traj, Problem& p)
@@ -2869,12 +2939,17 @@ int sweep_loss_form(const pi::LossInj* loss, const void* traj, const void*& g_tr
 template <typename T>
 int batch_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* mask, T* g_h0, double* param_grad, void* ws,
                            size_t ws_bytes, const T* P, int hc, int ndim, const int64_t* shape, int batch, int T_steps,
-                           const char* options, void* stream, const pi::LossInj* loss = nullptr)
+                           const char* options, void* stream, const pi::LossInj* loss = nullptr, const int* obs_strides = nullptr,
+                           const T* target_c = nullptr)
 {
-    if (batch == 1)
+    // obs_strides (with loss, mode 2, and g_traj = traj): the sparse-observation loss form, target_c its compact target or nullptr.
+    // It runs the launches below for one sample too: the unbatched sweep may dispatch a resident kernel, which has no such form
+    const bool obs = loss && obs_strides;
+    if (batch == 1 && !obs)
         return rollout_bwd_impl<T>(traj, g_traj, mask, g_h0, param_grad, ws, ws_bytes, P, hc, ndim, shape, T_steps, stream, options,
                                    loss);
     Problem p;
+    if (obs && hc == -1) return PERCNN_PI_EINVAL;
     if (int rc = batch_problem(hc, ndim, shape, batch, p, options)) return rc;
     {
         const void* gt = g_traj;
@@ -2885,6 +2960,11 @@ int batch_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* 
     // loss form: dL/dh0 is written while the trajectory, the target and the factors are still being read
     if (loss && (g_h0 == traj || g_h0 == g_traj || g_h0 == P || (const void*)g_h0 == loss->dev || (const void*)param_grad == loss->dev))
         return PERCNN_PI_EINVAL;
+    ObsHost oh;
+    if (obs) {
+        if (g_h0 == target_c) return PERCNN_PI_EINVAL;
+        if (int rc = make_obs(p, batch, obs_strides, target_c, mask, T_steps + 1, oh)) return rc;
+    }
     if (!ws || ws_bytes < batch_rollout_workspace_bytes(p, batch, T_steps, sizeof(T)) || (reinterpret_cast<uintptr_t>(ws) % 16))
         return PERCNN_PI_EWORKSPACE;
     auto st = static_cast<hipStream_t>(stream);
@@ -2899,8 +2979,11 @@ int batch_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* 
     int t_top = T_steps;
     while (t_top > 0 && !has(t_top)) --t_top;
     // dL/dh of one frame that no later step injects (the top frame): a copy, or -- loss form -- a_b * (h - target)
+    // (sparse observations: target_c + cframe(t) is frame t's compact target)
+    auto ctarget = [&](int t) -> const T* { return target_c ? target_c + oh.cframe[(size_t)t] : nullptr; };
     auto top_frame = [&](int t, T* dst) -> hipError_t {
         if (!loss) return hipMemcpyAsync(dst, g_traj + (size_t)t * frame, frame_bytes, hipMemcpyDeviceToDevice, st);
+        if (obs) return obs_grad_frame_b<T>(traj + (size_t)t * frame, ctarget(t), dst, p, batch, oh.lat, st);
         return loss_grad_frame_b<T>(traj + (size_t)t * frame, p.loss.mode == 2 ? g_traj + (size_t)t * frame : nullptr, dst, p, batch, st);
     };
     if (t_top == 0) {
@@ -2924,18 +3007,22 @@ int batch_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* 
         for (; t_cur - K >= 0; t_cur -= K) {
             unsigned m = 0;
             for (int q = 0; q < K; ++q) if (has(t_cur - 1 - q)) m |= 1u << q;
+            pi::ObsTile ob{};
+            if (obs) ob = obs_tile(oh, m, t_cur, K);
             if (hipError_t e = adj_tile_b<T>(traj + (size_t)t_cur * frame, g_traj + (size_t)t_cur * frame, adj + (size_t)t_cur * frame,
-                                             m, g_h0, t_cur == K ? K : 0, w.partials, P, p, batch, st))
+                                             m, g_h0, t_cur == K ? K : 0, w.partials, P, p, batch, st, -1, obs ? &ob : nullptr))
                 return (int)e;
         }
     }
     for (int t = t_cur; t >= 1; --t) {
         T* dst = (t == 1) ? g_h0 : adj + (size_t)(t - 1) * frame;
         const T* inj = has(t - 1) ? g_traj + (size_t)(t - 1) * frame : nullptr;
+        if (obs && inj && target_c) inj = ctarget(t - 1);   // (without a target the pointer only says "inside the loss")
         const T* gin = (top_in_place && t == t_top) ? top_in_place : adj + (size_t)t * frame;
+        const pi::ObsLat* ol = obs ? &oh.lat : nullptr;
         unsigned r2 = 0;
-        hipError_t e = fuse ? step_bwd_b<T, true>(traj + (size_t)(t - 1) * frame, gin, inj, dst, w.partials, P, p, batch, st, &r2)
-                            : step_bwd_b<T, false>(traj + (size_t)(t - 1) * frame, gin, inj, dst, w.partials, P, p, batch, st, &r2);
+        hipError_t e = fuse ? step_bwd_b<T, true>(traj + (size_t)(t - 1) * frame, gin, inj, dst, w.partials, P, p, batch, st, &r2, -1, ol)
+                            : step_bwd_b<T, false>(traj + (size_t)(t - 1) * frame, gin, inj, dst, w.partials, P, p, batch, st, &r2, -1, ol);
         if (e) return (int)e;
         if (r2 > rows) rows = r2;
     }
@@ -3093,8 +3180,10 @@ int ens_rollout_fwd_impl(T* traj, const T* P, int hc, int ndim, const int64_t* s
 template <typename T>
 int ens_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* mask, T* g_h0, double* param_grad, void* ws,
                          size_t ws_bytes, const T* P, int hc, int ndim, const int64_t* shape, int batch, int T_steps,
-                         const char* options, void* stream, const pi::LossInj* loss = nullptr)
+                         const char* options, void* stream, const pi::LossInj* loss = nullptr, const int* obs_strides = nullptr,
+                         const T* target_c = nullptr)
 {
+    const bool obs = loss && obs_strides;                  // sparse-observation loss form, as in batch_rollout_bwd_impl
     Problem p;
     if (int rc = ens_problem(hc, ndim, shape, batch, p, options)) return rc;
     const T* const target = g_traj;                        // (loss form, mode 1: g_traj becomes traj below)
@@ -3106,7 +3195,12 @@ int ens_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* ma
     if (!traj || !g_traj || !g_h0 || !param_grad || !P || T_steps < 0 || g_h0 == traj || g_h0 == g_traj || g_h0 == P)
         return PERCNN_PI_EINVAL;
     if (loss && ((const void*)g_h0 == loss->dev || (const void*)param_grad == loss->dev)) return PERCNN_PI_EINVAL;
-    if (batch == 1)
+    ObsHost oh;
+    if (obs) {
+        if (g_h0 == target_c) return PERCNN_PI_EINVAL;
+        if (int rc = make_obs(p, batch, obs_strides, target_c, mask, T_steps + 1, oh)) return rc;
+    }
+    if (batch == 1 && !obs)
         return rollout_bwd_impl<T>(traj, loss ? target : g_traj, mask, g_h0, param_grad, ws, ws_bytes, P, hc, ndim, shape, T_steps, stream,
                                    options, loss);
     if (!ws || ws_bytes < batch_rollout_workspace_bytes(p, batch, T_steps, sizeof(T)) || (reinterpret_cast<uintptr_t>(ws) % 16))
@@ -3119,8 +3213,10 @@ int ens_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* ma
     auto has = [&](int t) { return !mask || mask[t]; };
     int t_top = T_steps;
     while (t_top > 0 && !has(t_top)) --t_top;
+    auto ctarget = [&](int t) -> const T* { return target_c ? target_c + oh.cframe[(size_t)t] : nullptr; };
     auto top_frame = [&](int t, T* dst) -> hipError_t {     // as in batch_rollout_bwd_impl
         if (!loss) return hipMemcpyAsync(dst, g_traj + (size_t)t * frame, frame_bytes, hipMemcpyDeviceToDevice, st);
+        if (obs) return obs_grad_frame_b<T>(traj + (size_t)t * frame, ctarget(t), dst, p, batch, oh.lat, st);
         return loss_grad_frame_b<T>(traj + (size_t)t * frame, p.loss.mode == 2 ? g_traj + (size_t)t * frame : nullptr, dst, p, batch, st);
     };
     if (t_top == 0) {
@@ -3143,17 +3239,21 @@ int ens_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* ma
         for (; t_cur - K >= 0; t_cur -= K) {
             unsigned m = 0;
             for (int q = 0; q < K; ++q) if (has(t_cur - 1 - q)) m |= 1u << q;
+            pi::ObsTile ob{};
+            if (obs) ob = obs_tile(oh, m, t_cur, K);
             if (hipError_t e = adj_tile_b<T>(traj + (size_t)t_cur * frame, g_traj + (size_t)t_cur * frame, adj + (size_t)t_cur * frame,
-                                             m, g_h0, t_cur == K ? K : 0, partials, P, p, batch, st, rows))
+                                             m, g_h0, t_cur == K ? K : 0, partials, P, p, batch, st, rows, obs ? &ob : nullptr))
                 return (int)e;
         }
     }
     for (int t = t_cur; t >= 1; --t) {
         T* dst = (t == 1) ? g_h0 : adj + (size_t)(t - 1) * frame;
         const T* inj = has(t - 1) ? g_traj + (size_t)(t - 1) * frame : nullptr;
+        if (obs && inj && target_c) inj = ctarget(t - 1);
         const T* gin = (top_in_place && t == t_top) ? top_in_place : adj + (size_t)t * frame;
-        hipError_t e = fuse ? step_bwd_b<T, true>(traj + (size_t)(t - 1) * frame, gin, inj, dst, partials, P, p, batch, st, nullptr, rows)
-                            : step_bwd_b<T, false>(traj + (size_t)(t - 1) * frame, gin, inj, dst, partials, P, p, batch, st, nullptr, rows);
+        const pi::ObsLat* ol = obs ? &oh.lat : nullptr;
+        hipError_t e = fuse ? step_bwd_b<T, true>(traj + (size_t)(t - 1) * frame, gin, inj, dst, partials, P, p, batch, st, nullptr, rows, ol)
+                            : step_bwd_b<T, false>(traj + (size_t)(t - 1) * frame, gin, inj, dst, partials, P, p, batch, st, nullptr, rows, ol);
         if (e) return (int)e;
     }
     if (pass) {
@@ -3628,6 +3728,60 @@ int batch_sqerr_impl(const T* traj, const T* target, const unsigned char* mask, 
                                         0, st, tr, tg, sample, partials, frame, g - f, (int)slots);
             else     hipLaunchKernelGGL((pi::pi_sqerr_kernel<T, 1, long, int, int>), dim3(nb, (unsigned)batch), dim3(256), 0, st, tr, tg,
                                         sample, partials, frame, g - f, (int)slots);
+            if (hipError_t e = hipGetLastError()) return (int)e;
+        }
+        f = g;
+    }
+    hipLaunchKernelGGL((pi::pi_sqerr_finish_kernel<T, int>), dim3((unsigned)batch), dim3(64), 0, st, partials, (int)used, scale, out,
+                       (int)slots);
+    return (int)hipGetLastError();
+}
+
+// the sparse-observation form of batch_sqerr_impl: out[b] = scale * sum over the selected frames and the lattice points of
+// (traj - target_c)^2, target_c [n][B][2][*Sc] compact in space and time.  Same slots, launch order and finishing pass, for one
+// sample too.  All strides 1: the lattice is the grid and the run goes through the dense kernel with its 16-byte lanes, so the
+// result is batch_sqerr_impl's bit for bit.
+template <typename T>
+int batch_obs_sqerr_impl(const T* traj, const T* target_c, const unsigned char* mask, int nframes, int ndim, const int64_t* shape,
+                         const int* strides, int batch, double scale, T* out, void* ws, size_t ws_bytes, void* stream)
+{
+    if (batch < 1 || batch > MAX_BATCH) return PERCNN_PI_EINVAL;
+    Problem p;
+    if (int rc = batch_problem(0, ndim, shape, batch, p, nullptr, false)) return rc;
+    if (!traj || !out || nframes < 0 || out == traj || out == target_c) return PERCNN_PI_EINVAL;
+    ObsHost oh;
+    if (int rc = make_obs(p, batch, strides, target_c, mask, nframes, oh)) return rc;
+    const unsigned slots = batch_sqerr_slots(batch);
+    if (!ws || ws_bytes < (size_t)batch * slots * sizeof(double) || reinterpret_cast<uintptr_t>(ws) % 8) return PERCNN_PI_EWORKSPACE;
+    auto st = static_cast<hipStream_t>(stream);
+    const long sample = 2 * p.n, frame = (long)batch * sample, cframe = (long)batch * 2 * oh.lat.cs;
+    double* partials = static_cast<double*>(ws);
+    if (hipError_t e = hipMemsetAsync(partials, 0, (size_t)batch * slots * sizeof(double), st)) return (int)e;
+    const bool dense = oh.lat.cs == p.n;
+    const bool v16 = dense && sample % pi::vec_width<T>::value == 0 && (sample * sizeof(T)) % 16 == 0 &&
+                     reinterpret_cast<uintptr_t>(traj) % 16 == 0 && (!target_c || reinterpret_cast<uintptr_t>(target_c) % 16 == 0);
+    unsigned used = 1;
+    int f = 0;
+    while (f < nframes) {
+        while (f < nframes && mask && !mask[f]) ++f;
+        int g = f;
+        while (g < nframes && (!mask || mask[g])) ++g;
+        if (g > f) {
+            const T* tr = traj + (size_t)f * frame;
+            const T* tg = target_c ? target_c + oh.cframe[(size_t)f] : nullptr;
+            const long chunks = (long)(g - f) * (dense ? sample / (v16 ? pi::vec_width<T>::value : 1) : 2 * oh.lat.cs);
+            const unsigned nb = (unsigned)std::min<long>(slots, (chunks + 1023) / 1024);
+            if (nb > used) used = nb;
+            const dim3 grid(nb, (unsigned)batch);
+            if (!dense)
+                hipLaunchKernelGGL((pi::pi_sqerr_kernel<T, 1, long, int, int, long, int, int, pi::ObsLat>), grid, dim3(256), 0, st, tr, tg,
+                                   sample, partials, frame, g - f, (int)slots, cframe, (int)(p.ndim == 3 ? p.n1 : p.n0), (int)p.W, oh.lat);
+            else if (v16)
+                hipLaunchKernelGGL((pi::pi_sqerr_kernel<T, pi::vec_width<T>::value, long, int, int>), grid, dim3(256), 0, st, tr, tg,
+                                   sample, partials, frame, g - f, (int)slots);
+            else
+                hipLaunchKernelGGL((pi::pi_sqerr_kernel<T, 1, long, int, int>), grid, dim3(256), 0, st, tr, tg, sample, partials, frame,
+                                   g - f, (int)slots);
             if (hipError_t e = hipGetLastError()) return (int)e;
         }
         f = g;
@@ -4222,6 +4376,45 @@ size_t percnn_pi_batch_traj_sqerr_workspace_bytes(int batch)
 
 PI_EXPORT_BATCH_LOSS(f32, float)
 PI_EXPORT_BATCH_LOSS(f64, double)
+
+// the sparse-observation losses per sample (include/percnn_pi.h "Sparse observations"): the sweeps in loss form, mode 2, with the
+// lattice; the trajectory stands in for the dL/dtraj pointer, which these flavours never read
+#define PI_EXPORT_OBS_LOSS(SUF, T)                                                                                  \
+    int percnn_pi_batch_traj_obs_sqerr_##SUF(const T* traj, const T* target_c, const unsigned char* frame_mask,     \
+                                             int nframes, int ndim, const int64_t* shape, const int* strides,       \
+                                             int batch, double scale, T* out, void* workspace,                      \
+                                             size_t workspace_bytes, void* stream)                                  \
+    { return batch_obs_sqerr_impl<T>(traj, target_c, frame_mask, nframes, ndim, shape, strides, batch, scale, out,  \
+                                     workspace, workspace_bytes, stream); }                                         \
+    int percnn_pi_batch_rollout_bwd_obs_sqerr_##SUF(const T* traj, const T* target_c,                               \
+                                                    const unsigned char* frame_mask, const int* strides,            \
+                                                    double scale, const T* dev_scale, T* g_h0, double* param_grad,  \
+                                                    void* workspace, size_t workspace_bytes, const T* params,       \
+                                                    int hc, int ndim, const int64_t* shape, int batch, int T_steps, \
+                                                    const char* options, void* stream)                              \
+    {                                                                                                               \
+        if (!strides || hc == -1) return PERCNN_PI_EINVAL;                                                          \
+        const pi::LossInj l{scale, dev_scale, 2};                                                                   \
+        return batch_rollout_bwd_impl<T>(traj, traj, frame_mask, g_h0, param_grad, workspace, workspace_bytes,      \
+                                         params, hc, ndim, shape, batch, T_steps, options, stream, &l, strides,     \
+                                         target_c);                                                                 \
+    }                                                                                                               \
+    int percnn_pi_ensemble_rollout_bwd_obs_sqerr_##SUF(const T* traj, const T* target_c,                            \
+                                                       const unsigned char* frame_mask, const int* strides,         \
+                                                       double scale, const T* dev_scale, T* g_h0,                   \
+                                                       double* param_grad, void* workspace, size_t workspace_bytes, \
+                                                       const T* params, int hc, int ndim, const int64_t* shape,     \
+                                                       int batch, int T_steps, const char* options, void* stream)   \
+    {                                                                                                               \
+        if (!strides || hc == -1) return PERCNN_PI_EINVAL;                                                          \
+        const pi::LossInj l{scale, dev_scale, 2};                                                                   \
+        return ens_rollout_bwd_impl<T>(traj, traj, frame_mask, g_h0, param_grad, workspace, workspace_bytes,        \
+                                       params, hc, ndim, shape, batch, T_steps, options, stream, &l, strides,       \
+                                       target_c);                                                                   \
+    }
+
+PI_EXPORT_OBS_LOSS(f32, float)
+PI_EXPORT_OBS_LOSS(f64, double)
 
 #define PI_EXPORT_RES(SUF, T)                                                                                       \
     int percnn_pi_residual_fwd_##SUF(const T* traj, T* resid, const T* params, int ndim, const int64_t* shape,     \

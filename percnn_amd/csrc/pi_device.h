@@ -167,6 +167,44 @@ struct FastDiv {
     __device__ __forceinline__ unsigned div_nz(unsigned x) const { return __umulhi(x, m) >> s; }
 };
 
+// ---- sparse-observation loss form (the reference's own data loss: mse_loss(output[::15, :, ::2, ::2, ::2], truth[...])) --------
+// The loss lives on the sub-lattice x_d % s_d == 0 of the observed frames and the target is COMPACT: frame [B][2][*Sc],
+// Sc_d = ceil(S_d / s_d), one frame per observed frame.  Axes are numbered slowest first and always three: a 2D grid is
+// (1, H, W) with stride 1 on the leading axis.  floor(x / s) is a valid compact coordinate for EVERY x, so a target load at the
+// floor index is always in bounds and can stay unconditional; the point is on the lattice iff q * s == x.
+// The sweeps keep the mode-2 arithmetic a * (h - j) of loss_inject: their loaders hand it j = the target value (0 without a
+// target) on the lattice and j = h off it, where it gives a * (h - h) = 0 -- what a materialised gradient holds there.
+// Sample flavours only; the description travels as the LAST trailing kernel argument (ObsLat: direct kernel, top frame, loss
+// value; ObsTile: 2D tile sweep).  No resident, brick or plane-streaming kernel is instantiated with it.
+struct ObsLat {
+    FastDiv d[3];           // x / s per axis
+    int s[3];               // strides
+    int sc[3];              // compact extents
+    long cs;                // compact species stride = sc[0] * sc[1] * sc[2]; a compact sample is 2 * cs elements
+    int has_target;         // 0: the target is zero and no target pointer is read
+};
+// the tile sweep injects up to K frames per launch, and the observed ones are not a uniform stride apart in the time-compact
+// target: one element offset per sub-step (sub-step m injects frame t - 1 - m), relative to `target` = sample 0 of compact frame 0
+struct ObsTile {
+    ObsLat lat;
+    const void* target;     // compact target [n][B][2][*Sc] of the compute type; nullptr <=> !lat.has_target
+    long coff[8];
+};
+template <typename A, typename B> struct same_type { static constexpr bool value = false; };
+template <typename A> struct same_type<A, A> { static constexpr bool value = true; };
+// number of lattice descriptions in a flavour pack (0 or 1, the last argument)
+template <typename... X> struct obs_args { static constexpr int value = 0; };
+template <typename A, typename... X> struct obs_args<A, X...> {
+    static constexpr int value = ((same_type<A, ObsLat>::value || same_type<A, ObsTile>::value) ? 1 : 0) + obs_args<X...>::value;
+};
+// compact coordinate of x on axis `a` and whether x is a lattice coordinate
+__device__ __forceinline__ unsigned obs_q(const ObsLat& l, int a, unsigned x, bool& on)
+{
+    const unsigned q = l.d[a].div(x);
+    on = q * (unsigned)l.s[a] == x;
+    return q;
+}
+
 // XCD-aware block remap: hand each XCD (private 4 MiB L2) a contiguous range of the grid so the
 // axis-0 neighbours of a block's rows are served by the same L2.  Pure speed; any mapping is correct.
 // Any block count: XCD x (the blocks with bid % 8 == x) gets the contiguous range starting at x*q + min(x, r), q = n / 8,

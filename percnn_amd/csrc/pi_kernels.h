@@ -497,17 +497,21 @@ __global__ void __launch_bounds__(256)
 pi_bwd_kernel(const T* __restrict__ h, const T* __restrict__ G, const T* __restrict__ inj, T* __restrict__ Gp,
               double* __restrict__ partials, const T* __restrict__ P, Geom g, int hc_rt, X... x)
 {
-    if constexpr (sizeof...(X) >= 1) {
+    // sparse-observation flavour (pi_device.h): one more trailing argument, the lattice; `inj` is then the COMPACT target
+    // frame [B][2][*Sc] (without a target: any non-null pointer, never read) and g.loss.mode is 2
+    constexpr int OBS = obs_args<X...>::value, NX = (int)sizeof...(X) - OBS;
+    if constexpr (NX >= 1) {
         const long sbase = (long)blockIdx.y * flavour_arg<0>(x...);  // sample blockIdx.y; partial row per (sample, workgroup)
         h += sbase; G += sbase; Gp += sbase;
-        if (inj) inj += sbase;
+        if constexpr (OBS) { if (inj) inj += (long)blockIdx.y * 2 * flavour_arg<NX>(x...).cs; }
+        else if (inj) inj += sbase;
     }
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T* red = reinterpret_cast<T*>(smem_raw);           // [nwaves][np] running sums of this block
 
     const int hc = HC == POLY ? 0 : (HC > 0 ? HC : hc_rt);
     const int np = nparams(hc);
-    if constexpr (sizeof...(X) == 2) P += (long)blockIdx.y * np;       // block of sample blockIdx.y
+    if constexpr (NX == 2) P += (long)blockIdx.y * np;                 // block of sample blockIdx.y
     const int nwaves = blockDim.x / WAVE;
     const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
     T* myred = red + wave * np;
@@ -521,8 +525,8 @@ pi_bwd_kernel(const T* __restrict__ h, const T* __restrict__ G, const T* __restr
         return WGRAD || idx < P_W;                                                  // sweep-only flavour: coefficients only
     };
     long row = blockIdx.x;
-    if constexpr (sizeof...(X) == 1) row = (long)blockIdx.y * gridDim.x + blockIdx.x;
-    if constexpr (sizeof...(X) == 2) row = (long)blockIdx.y * flavour_arg<1>(x...) + blockIdx.x;
+    if constexpr (NX == 1) row = (long)blockIdx.y * gridDim.x + blockIdx.x;
+    if constexpr (NX == 2) row = (long)blockIdx.y * flavour_arg<1>(x...) + blockIdx.x;
     double* const prow = partials + row * np;
     const double pold = carries_grad((int)threadIdx.x) ? prow[threadIdx.x] : 0.0;
     __syncthreads();
@@ -698,12 +702,29 @@ pi_bwd_kernel(const T* __restrict__ h, const T* __restrict__ G, const T* __restr
             }
             if (inj) {
                 Pack<T, VEC> ju = u, jv = v;
+                if constexpr (OBS) {
+                    // lattice points take the target value at their compact index (element-wise loads at the floor index:
+                    // in bounds for every point, no alignment asked of the target), the others keep j = h: a * (h - h) = 0
+                    const ObsLat ol = flavour_arg<NX>(x...);
+                    bool on0 = true, on1;
+                    const unsigned q0 = NDIM == 3 ? obs_q(ol, 0, (unsigned)iz, on0) : 0u;
+                    const unsigned q1 = obs_q(ol, 1, (unsigned)L.row, on1);
+                    const long rbase = ((long)q0 * ol.sc[1] + q1) * ol.sc[2];
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i) {
+                        bool on2;
+                        const long ci = rbase + obs_q(ol, 2, (unsigned)(L.x0 + i), on2);
+                        T tu = T(0), tv = T(0);
+                        if (ol.has_target) { tu = inj[ci]; tv = inj[ol.cs + ci]; }
+                        if (on0 && on1 && on2) { ju.v[i] = tu; jv.v[i] = tv; }
+                    }
+                } else
                 if (g.loss.mode != 1) {                                  // mode 1 injects a function of the state alone
                     ju = ldb<T, VEC>(plane_base<T, NDIM>(inj + g.off, g, iz), L.eb);
                     jv = ldb<T, VEC>(plane_base<T, NDIM>(inj + g.ss + g.off, g, iz), L.eb);
                 }
                 T la;
-                if constexpr (sizeof...(X) >= 1) la = g.loss.mode ? loss_factor<T>(g.loss, (long)blockIdx.y) : T(0);   // its sample's factor
+                if constexpr (NX >= 1) la = g.loss.mode ? loss_factor<T>(g.loss, (long)blockIdx.y) : T(0);   // its sample's factor
                 else la = g.loss.mode ? loss_factor<T>(g.loss) : T(0);
 #pragma unroll
                 for (int i = 0; i < VEC; ++i) {
@@ -1179,11 +1200,42 @@ pi_residual_adj_kernel(const T* __restrict__ traj, const T* __restrict__ G, T* _
 // no later step that could inject it) and the fall-back paths materialise whole trajectories of it.  n = elements.
 // X... = `long sample` (grid (nb, B)): frame [B][n] of B samples, workgroup (x, b) writes sample b with its factor a_b
 // (loss_factor, pi_device.h); n = elements of one sample then.
+// X... = `long sample, int n1, int W, ObsLat` (grid (nb, B), VEC = 1): the sparse-observation form (pi_device.h).  `out` is the
+// same dense frame [B][n], zero off the lattice and a_b * (h - target) on it; `target` is the COMPACT frame [B][2][*Sc].  A
+// workgroup walks rows of W points (their species / plane / row are scalar), its lanes the points of a row.
 template <typename T, int VEC, typename... X>
 __global__ void __launch_bounds__(256)
 pi_loss_grad_kernel(const T* __restrict__ h, const T* __restrict__ target, T* __restrict__ out, long n, LossInj l, X... x)
 {
     T a;
+    if constexpr (sizeof...(X) == 4) {
+        static_assert(VEC == 1, "element-wise");
+        const ObsLat ol = flavour_arg<3>(x...);
+        const long sbase = (long)blockIdx.y * flavour_arg<0>(x...);
+        const int n1 = flavour_arg<1>(x...), W = flavour_arg<2>(x...);
+        h += sbase; out += sbase;
+        if (target) target += (long)blockIdx.y * 2 * ol.cs;
+        a = loss_factor<T>(l, (long)blockIdx.y);
+        const long ss = n / 2, rows_s = ss / W;           // rows per species
+        for (long r = blockIdx.x; r < 2 * rows_s; r += gridDim.x) {
+            const long sp = r / rows_s, rr = r - sp * rows_s;
+            const unsigned x0 = (unsigned)(rr / n1), x1 = (unsigned)(rr - (long)x0 * n1);
+            bool on0, on1;
+            const unsigned q0 = obs_q(ol, 0, x0, on0), q1 = obs_q(ol, 1, x1, on1);
+            const long cbase = sp * ol.cs + ((long)q0 * ol.sc[1] + q1) * ol.sc[2];
+            for (int xx = (int)threadIdx.x; xx < W; xx += (int)blockDim.x) {
+                bool on2;
+                const unsigned q2 = obs_q(ol, 2, (unsigned)xx, on2);
+                T y = T(0);
+                if (on0 && on1 && on2) {
+                    const T hv = h[r * W + xx];
+                    y = a * (target ? hv - target[cbase + q2] : hv);
+                }
+                out[r * W + xx] = y;
+            }
+        }
+        return;
+    } else
     if constexpr (sizeof...(X) == 1) {
         const long sbase = (long)blockIdx.y * flavour_arg<0>(x...);
         h += sbase; out += sbase;
@@ -1213,13 +1265,35 @@ pi_loss_grad_kernel(const T* __restrict__ h, const T* __restrict__ target, T* __
 // alone, one stride for every launch of a call.  A lane walks
 // the run's chunks of its sample as the unbatched kernel walks a contiguous run; (frame, chunk in frame) advance with the
 // lane's stride by one add and one conditional wrap, no division in the loop.
+// X... = `long fstride, int nfr, int slots, long cfstride, int n1, int W, ObsLat` (VEC = 1): the sparse-observation form
+// (pi_device.h) of the same run -- the sum runs over the lattice points only, `target` is the run's first COMPACT frame
+// [B][2][*Sc], cfstride = B * 2 * cs apart.  A lane walks the compact elements of its sample; every square is added in float64.
 template <typename T, int VEC, typename... X>
 __global__ void __launch_bounds__(256)
 pi_sqerr_kernel(const T* __restrict__ traj, const T* __restrict__ target, long n, double* __restrict__ partials, X... x)
 {
     __shared__ double red[256 / WAVE];
     double acc = 0.0;
-    if constexpr (sizeof...(X) == 3) {
+    constexpr int NS = (int)sizeof...(X) - 4 * obs_args<X...>::value;    // 0, or the 3 arguments of the sample flavours
+    if constexpr (obs_args<X...>::value == 1) {
+        static_assert(VEC == 1 && NS == 3, "element-wise, sample flavour");
+        const ObsLat ol = flavour_arg<6>(x...);
+        const long fstride = flavour_arg<0>(x...), cfstride = flavour_arg<3>(x...);
+        const long n1 = flavour_arg<4>(x...), W = flavour_arg<5>(x...);
+        const long ss = n / 2, csample = 2 * ol.cs, total = csample * flavour_arg<1>(x...);
+        traj += (long)blockIdx.y * n;
+        if (target) target += (long)blockIdx.y * csample;
+        for (long c = (long)blockIdx.x * blockDim.x + threadIdx.x; c < total; c += (long)gridDim.x * blockDim.x) {
+            const long fr = c / csample, r = c - fr * csample;
+            const long sp = r / ol.cs, ci = r - sp * ol.cs;
+            const long t = ci / ol.sc[2], q2 = ci - t * ol.sc[2];
+            const long q0 = t / ol.sc[1], q1 = t - q0 * ol.sc[1];
+            const long e = fr * fstride + sp * ss + ((q0 * ol.s[0]) * n1 + q1 * ol.s[1]) * W + q2 * ol.s[2];
+            const T d = target ? traj[e] - target[fr * cfstride + r] : traj[e];
+            acc += (double)d * (double)d;
+        }
+    } else
+    if constexpr (NS == 3) {
         const long fstride = flavour_arg<0>(x...);
         const long sbase = (long)blockIdx.y * n;
         traj += sbase;
@@ -1305,7 +1379,7 @@ pi_sqerr_kernel(const T* __restrict__ traj, const T* __restrict__ target, long n
         double s = 0.0;
         for (int w = 0; w < 256 / WAVE; ++w) s += red[w];
         long slot = blockIdx.x;
-        if constexpr (sizeof...(X) == 3) slot = (long)blockIdx.y * flavour_arg<2>(x...) + blockIdx.x;
+        if constexpr (NS == 3) slot = (long)blockIdx.y * flavour_arg<2>(x...) + blockIdx.x;
         partials[slot] += s;                             // slots are zeroed by the host; runs beyond the 64th share slots (stream-ordered)
     }
 }

@@ -810,10 +810,56 @@ __device__ __forceinline__ void strip_addr_table(StripAddr (&sa)[K], const TileG
     if constexpr (M + 1 < K) strip_addr_table<K, BX, BY, NT, M + 1>(sa, g, ty0, tx0);
 }
 
-// sa: the strip's offsets if they were computed ahead (kernel prologue), else nullptr
+// sparse-observation flavour of the operand loader (pi_device.h, ObsTile): the injection operands of the strip's four points.
+// The lattice test and the compact index use the WRAPPED global coordinates, so a halo point injects exactly what its owner
+// injects, also where the stride does not divide the extent.  Lattice points get the target value at their compact index (0
+// without a target), the others the state itself: the mode-2 arithmetic of the sub-steps then forms a * (u - u) = 0 there and
+// needs no flavour of its own.  The loads stay unconditional (see adj_load_ops) and element-wise: the floor index is in
+// bounds for every point, and a frame outside the loss, or a loss without a target, reads the state frame at that index.
 template <typename T, int K, int BX, int BY, int NT, int M>
+__device__ __forceinline__ void adj_load_obs(StripOps<T>& o, int q, const T* __restrict__ hfr, const T* __restrict__ gfr,
+                                             const TileGeom& g, int ty0, int tx0, const ObsTile& ob)
+{
+    using SM = StripMap<K, BX, BY, M, PART_FULL>;
+    constexpr int RN4 = SM::N, O = 2 * (M + 1);
+    int idx = (int)threadIdx.x + q * NT;                   // the strip of strip_addr
+    if (idx >= RN4) idx = RN4 - 1;
+    int ry, rc;
+    SM::locate(idx, ry, rc);
+    const int ly = ry + O, lx = 4 * rc + O;
+    const int gy = wrap1(ty0 - 2 * K + ly, g.H);
+    const int gx[2] = {wrap1(tx0 - 2 * K + lx, g.W), wrap1(tx0 - 2 * K + lx + 2, g.W)};
+    const bool use = gfr && ob.target;                      // wave-uniform
+    const T* src = use ? static_cast<const T*>(ob.target) + ob.coff[M] : hfr;
+    const long sp = use ? ob.lat.cs : g.ss;
+    bool ony;
+    const long rbase = (long)obs_q(ob.lat, 1, (unsigned)gy, ony) * ob.lat.sc[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            bool onx;
+            const long ci = rbase + obs_q(ob.lat, 2, (unsigned)(gx[h] + e), onx);
+            const T tu = src[ci], tv = src[sp + ci];
+            const bool on = ony && onx;
+            o.ju[2 * h + e] = on ? (use ? tu : T(0)) : o.u[2 * h + e];
+            o.jv[2 * h + e] = on ? (use ? tv : T(0)) : o.v[2 * h + e];
+        }
+}
+
+// the lattice description of the workgroup's own sample (blockIdx.y): its part of the compact target
+template <typename T>
+__device__ __forceinline__ ObsTile obs_of_sample(ObsTile ob)
+{
+    if (ob.target) ob.target = static_cast<const T*>(ob.target) + (long)blockIdx.y * 2 * ob.lat.cs;
+    return ob;
+}
+
+// sa: the strip's offsets if they were computed ahead (kernel prologue), else nullptr
+// OB... = `ObsTile`: the sparse-observation flavour (adj_load_obs above; `gfr` then only says whether the frame is inside the loss)
+template <typename T, int K, int BX, int BY, int NT, int M, typename... OB>
 __device__ __forceinline__ void adj_load_ops(StripOps<T>& o, int q, const T* __restrict__ hfr, const T* __restrict__ gfr,
-                                             const TileGeom& g, int ty0, int tx0, const StripAddr* sa = nullptr)
+                                             const TileGeom& g, int ty0, int tx0, const StripAddr* sa = nullptr, OB... ob)
 {
     const StripAddr A = sa ? *sa : strip_addr<K, BX, BY, NT, M>(q, g, ty0, tx0);
     // The sub-steps are VALU-issue-bound (two waves per SIMD: the per-wave timeline shows waves 4-7 finishing 0.45 us after
@@ -846,6 +892,7 @@ __device__ __forceinline__ void adj_load_ops(StripOps<T>& o, int q, const T* __r
     o.v[0] = c.v[0]; o.v[1] = c.v[1]; o.v[2] = d.v[0]; o.v[3] = d.v[1];
     o.ju[0] = a2.v[0]; o.ju[1] = a2.v[1]; o.ju[2] = b2.v[0]; o.ju[3] = b2.v[1];
     o.jv[0] = c2.v[0]; o.jv[1] = c2.v[1]; o.jv[2] = d2.v[0]; o.jv[3] = d2.v[1];
+    if constexpr (sizeof...(OB) == 1) adj_load_obs<T, K, BX, BY, NT, M>(o, q, hfr, gfr, g, ty0, tx0, ob...);
 }
 
 // PRE = true: the strip operands of this sub-step were requested at kernel start (`pre`), so the cold
@@ -918,12 +965,12 @@ __device__ __forceinline__ unsigned persist_half_geo_word(const TileGeom& g, int
 // HALFS (round 6, geometry words only): the lane works on a HALF-strip -- the two points at the word's offset; `pre` holds their
 // operands in elements 0, 1 and bits 17, 18 of the word their ownership.  Same operations per point.
 template <typename T, int HC, int K, int BX, int BY, int NT, int M, bool PRE, bool MOM, int PART = PART_FULL, int TID0 = 0,
-          bool GEO = false, int LACC = NT, bool HALFS = false>
+          bool GEO = false, int LACC = NT, bool HALFS = false, typename... OB>
 __device__ __forceinline__ void adj_substep(T* cur, T* nxt, const T* __restrict__ hfr, const T* __restrict__ gfr,
                                             const TileGeom& g, int ty0, int tx0, const T* __restrict__ P,
                                             double (&acc_c)[2], const StripOps<T>& pre, TileMoments<T, MOM>& mom,
                                             double* lacc = nullptr, const unsigned* geo = nullptr,
-                                            const JacPairs<T>* jp = nullptr)
+                                            const JacPairs<T>* jp = nullptr, OB... ob)
 {
     static_assert(P_DT == 0 && P_COEF == 1 && P_C0 == 3 && P_TAPS == 4, "JacPairs::st follows P's order");
     auto cf = [P, jp](int i) -> V2<T> {
@@ -971,7 +1018,7 @@ __device__ __forceinline__ void adj_substep(T* cur, T* nxt, const T* __restrict_
             for (int i = 0; i < 4; ++i) ownbits |= (rowin && (unsigned)(lx + i - 2 * K) < own_nx) ? (1u << i) : 0u;
         }
         StripOps<T> lo;
-        if constexpr (!PRE) adj_load_ops<T, K, BX, BY, NT, M>(lo, q, hfr, gfr, g, ty0, tx0);
+        if constexpr (!PRE) adj_load_ops<T, K, BX, BY, NT, M>(lo, q, hfr, gfr, g, ty0, tx0, nullptr, ob...);
         // whole waves beyond the region skip the strip (see fwd_substep); their operand loads above stay unconditional --
         // loads inside a branch would cost the compiler its count of outstanding requests
         if constexpr (GEO) {
@@ -1143,14 +1190,15 @@ __device__ __forceinline__ void persist_load_ops_half(StripOps<T>& o, const T* _
 // its LDS barrier (one strip per lane only); `ops` holds the operands of sub-step M, requested one sub-step earlier.
 // HALFS (round 6, resident small-tile sweep): the lanes work on half-strips -- `geo` rows from persist_half_geo_word, operand byte
 // offsets per sub-step in `hoff`[K] (persist_half_off) instead of `sa`.
-template <typename T, int HC, int K, int BX, int BY, int NT, int M, bool PRE, bool MOM, bool GEO = false, bool HALFS = false>
+template <typename T, int HC, int K, int BX, int BY, int NT, int M, bool PRE, bool MOM, bool GEO = false, bool HALFS = false,
+          typename... OB>
 __device__ __forceinline__ void adj_substeps(T* b0, T* b1, const T* __restrict__ hbase, const T* __restrict__ gbase,
                                              T* __restrict__ abase, long frame_stride, unsigned inj_mask,
                                              T* __restrict__ g_h0, int steps_to_zero, const TileGeom& g, int ty0,
                                              int tx0, const T* __restrict__ P, double (&acc_c)[2],
                                              const StripOps<T>& ops, TileMoments<T, MOM>& mom, const StripAddr (&sa)[K],
                                              double* lacc = nullptr, bool store_handover = true, const unsigned* geo = nullptr,
-                                             const JacPairs<T>* jp = nullptr, const unsigned* hoff = nullptr)
+                                             const JacPairs<T>* jp = nullptr, const unsigned* hoff = nullptr, OB... ob)
 {
     T* cur = (M & 1) ? b1 : b0;
     T* nxt = (M & 1) ? b0 : b1;
@@ -1162,11 +1210,12 @@ __device__ __forceinline__ void adj_substeps(T* b0, T* b1, const T* __restrict__
             persist_load_ops_half<T>(ahead, hbase + fn, (inj_mask >> (M + 1)) & 1u ? gbase + fn : nullptr, g, hoff[M + 1]);
         else
             adj_load_ops<T, K, BX, BY, NT, M + 1>(ahead, 0, hbase + fn, (inj_mask >> (M + 1)) & 1u ? gbase + fn : nullptr, g,
-                                                  ty0, tx0, &sa[M + 1]);
+                                                  ty0, tx0, &sa[M + 1], ob...);
     }
     // (GEO: row M of the caller's [K][NT] table of geometry words + its held coefficient pairs -- resident sweeps only)
     adj_substep<T, HC, K, BX, BY, NT, M, PRE, MOM, PART_FULL, 0, GEO, NT, HALFS>(cur, nxt, hbase + fo, (inj_mask >> M) & 1u ? gbase + fo : nullptr, g,
-                                                                                 ty0, tx0, P, acc_c, ops, mom, lacc, GEO ? geo + M * NT : nullptr, jp);
+                                                                                 ty0, tx0, P, acc_c, ops, mom, lacc, GEO ? geo + M * NT : nullptr, jp,
+                                                                                 ob...);
 #if PI_PIN_MOMENTS
     // Pin this sub-step's moment accumulation HERE.  Left alone, the scheduler sinks the moment FMAs of all four sub-steps
     // (they depend on no LDS traffic) behind the last barrier -- 350 VALU instructions in the tail of the launch, where all
@@ -1196,18 +1245,22 @@ __device__ __forceinline__ void adj_substeps(T* b0, T* b1, const T* __restrict__
     if constexpr (M + 1 < K)
         adj_substeps<T, HC, K, BX, BY, NT, M + 1, PRE, MOM, GEO, HALFS>(b0, b1, hbase, gbase, abase, frame_stride, inj_mask, g_h0,
                                                                         steps_to_zero, g, ty0, tx0, P, acc_c, ahead, mom, sa, lacc,
-                                                                        store_handover, geo, jp, hoff);
+                                                                        store_handover, geo, jp, hoff, ob...);
 }
 
 // Flavours as pi_fwd2d_tile_kernel: S... = `long sample` (partial row blockIdx.y * gridDim.x + blockIdx.x), R... = `int rows`
 // on top (block of sample b; partial row b * rows + x, `rows` per sample and one stride for every launch of a call).
+// Sparse-observation flavours (sample flavours only; pi_device.h): an `ObsTile` as the last argument of R...; `gframe_t` is
+// then the trajectory (never read as a gradient: g.loss.mode is 2 and adj_load_obs supplies the injection operands).
 template <typename T, int HC, int K, int BX, int BY, int NT, bool MOM = false, typename... S, typename... R>
 __global__ void __launch_bounds__(NT)
 pi_adj2d_tile_kernel(const T* __restrict__ hframe_t, const T* __restrict__ gframe_t, T* __restrict__ aframe_t,
                      long frame_stride, S... sample, unsigned inj_mask, T* __restrict__ g_h0, int steps_to_zero,
                      double* __restrict__ partials, int np, const T* __restrict__ P, TileGeom g, R... rows)
 {
-    if constexpr (sizeof...(R) == 1) P += (long)blockIdx.y * np;
+    constexpr int OBS = obs_args<R...>::value, NR = (int)sizeof...(R) - OBS;
+    static_assert(!OBS || sizeof...(S) == 1, "sparse observations: sample flavours only");
+    if constexpr (NR == 1) P += (long)blockIdx.y * np;
     if constexpr (sizeof...(S) == 1) {
         const long sbase = (long)blockIdx.y * flavour_arg<0>(sample...);   // sample blockIdx.y; partial row per (sample, tile)
         hframe_t += sbase; gframe_t += sbase; aframe_t += sbase;
@@ -1247,7 +1300,7 @@ pi_adj2d_tile_kernel(const T* __restrict__ hframe_t, const T* __restrict__ gfram
     const int slot = threadIdx.x < 2 ? P_COEF + (int)threadIdx.x : P_W + (int)threadIdx.x - 2;
     const bool has_slot = threadIdx.x < (MOM ? 22 : 2);
     long row = blockIdx.x;
-    if constexpr (sizeof...(R) == 1) row = (long)blockIdx.y * flavour_arg<0>(rows...) + blockIdx.x;
+    if constexpr (NR == 1) row = (long)blockIdx.y * flavour_arg<0>(rows...) + blockIdx.x;
     else if constexpr (sizeof...(S) == 1) row = (long)blockIdx.y * gridDim.x + blockIdx.x;
     double* pslot = partials + row * np + (has_slot ? slot : P_COEF);
     const double pold = has_slot ? *pslot : 0.0;
@@ -1258,6 +1311,10 @@ pi_adj2d_tile_kernel(const T* __restrict__ hframe_t, const T* __restrict__ gfram
     StripAddr sa[K];
     if constexpr (PRE) {
         strip_addr_table<K, BX, BY, NT, 0>(sa, g, ty0, tx0);
+        if constexpr (OBS)
+            adj_load_ops<T, K, BX, BY, NT, 0>(ops0, 0, hframe_t - frame_stride, inj_mask & 1u ? gframe_t - frame_stride : nullptr,
+                                              g, ty0, tx0, &sa[0], obs_of_sample<T>(flavour_arg<NR>(rows...)));
+        else
         adj_load_ops<T, K, BX, BY, NT, 0>(ops0, 0, hframe_t - frame_stride, inj_mask & 1u ? gframe_t - frame_stride : nullptr,
                                           g, ty0, tx0, &sa[0]);
     }
@@ -1272,6 +1329,11 @@ pi_adj2d_tile_kernel(const T* __restrict__ hframe_t, const T* __restrict__ gfram
 #pragma unroll
             for (int m = 0; m < 10; ++m) mom.a[s][m] = typename MomAcc<T>::type{};
     }
+    if constexpr (OBS)
+        adj_substeps<T, HC, K, BX, BY, NT, 0, PRE, MOM>(b0, b1, hframe_t, gframe_t, aframe_t, frame_stride, inj_mask, g_h0,
+                                                        steps_to_zero, g, ty0, tx0, P, acc_c, ops0, mom, sa, lacc, true, nullptr,
+                                                        nullptr, nullptr, obs_of_sample<T>(flavour_arg<NR>(rows...)));
+    else
     adj_substeps<T, HC, K, BX, BY, NT, 0, PRE, MOM>(b0, b1, hframe_t, gframe_t, aframe_t, frame_stride, inj_mask, g_h0,
                                                     steps_to_zero, g, ty0, tx0, P, acc_c, ops0, mom, sa, lacc);
     // diffusion-coefficient gradients of this tile over the K sub-steps: one reduction per launch

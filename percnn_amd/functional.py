@@ -706,6 +706,180 @@ def pi_rollout_sqerr_ensemble(h0: torch.Tensor, P: torch.Tensor, steps: int, tar
     return _pi_rollout_sqerr_samples("pi_rollout_sqerr_ensemble", h0, P, steps, target, frames, reduction, options)
 
 
+# ---- the per-sample loss on sparse observations: a sub-lattice of the selected frames against a compact target ----
+def obs_selection(steps: int, t_idx: Sequence[int], strides, shape: Sequence[int], reduction: str = "mean",
+                  what: str = "pi_rollout_obs_sqerr"):
+    """Host arithmetic of the sparse-observation operators, no device involved.  t_idx: frame indices into the steps + 1
+    frames, strictly increasing after negative ones are wrapped; strides: an int or one int >= 1 per axis of `shape`.
+    -> (t_idx wrapped, mask, strides, Sc, weight): mask a list of steps + 1 bools (None when every frame is selected),
+    Sc = ceil(S / s) per axis, weight = 1 / (len(t_idx) * 2 * prod(Sc)) for "mean" -- what ``F.mse_loss`` of one sample's
+    slice divides by -- and 1 for "sum"."""
+    T1 = int(steps) + 1
+    sel = [int(t) % T1 for t in t_idx]
+    if not sel:
+        raise ValueError(f"{what}: no frame selected")
+    if any(b <= a for a, b in zip(sel, sel[1:])):
+        raise ValueError(f"{what}: t_idx must be strictly increasing, got {list(t_idx)}")
+    if isinstance(strides, int):
+        strides = (strides,) * len(shape)
+    strides = tuple(int(x) for x in strides)
+    if len(strides) != len(shape):
+        raise ValueError(f"{what}: one stride per axis of {tuple(shape)}, got {strides}")
+    if any(x < 1 for x in strides):
+        raise ValueError(f"{what}: strides must be >= 1, got {strides}")
+    Sc = tuple(-(-int(n) // x) for n, x in zip(shape, strides))
+    mask = None if len(sel) == T1 else [t in set(sel) for t in range(T1)]
+    numel = 2
+    for n in Sc:
+        numel *= n
+    weight = {"mean": 1.0 / (len(sel) * numel), "sum": 1.0}[reduction]
+    return sel, mask, strides, Sc, weight
+
+
+def _strides_arg(strides):
+    return (ctypes.c_int * len(strides))(*[int(x) for x in strides])
+
+
+def _check_compact(target, traj, frame_mask, strides):
+    F, B, shape = traj.shape[0], int(traj.shape[1]), traj.shape[3:]
+    n = F if frame_mask is None else sum(1 for m in frame_mask if m)
+    if len(strides) != len(shape):
+        raise ValueError(f"one stride per axis of {tuple(shape)}, got {tuple(strides)}")
+    if target is not None:
+        _require(target, "target", traj.dtype)
+    if target is not None and all(int(x) >= 1 for x in strides):   # (a stride < 1 is the library's to refuse)
+        want = (n, B, 2) + tuple(-(-int(s) // int(x)) for s, x in zip(shape, strides))
+        if tuple(target.shape) != want:
+            raise ValueError(f"compact target must be {want}, got {tuple(target.shape)}")
+
+
+def traj_obs_sqerr_batched(traj: torch.Tensor, target: Optional[torch.Tensor] = None,
+                           frame_mask: Optional[Sequence[bool]] = None, strides: Sequence[int] = (), scale: float = 1.0) -> torch.Tensor:
+    """traj [F,B,2,*S], target [n,B,2,*Sc] compact in time and space (None = 0) -> [B] of traj's dtype: scale * sum over the
+    frames with frame_mask[f] and the lattice points x_d % s_d == 0 of (traj - target)^2 (``percnn_pi_batch_traj_obs_sqerr_*``)."""
+    _require(traj, "traj")
+    _check_compact(target, traj, frame_mask, strides)
+    B, shape = int(traj.shape[1]), traj.shape[3:]
+    L = _lib.lib()
+    nbytes = L.percnn_pi_batch_traj_sqerr_workspace_bytes(B)
+    if nbytes == 0:
+        raise RuntimeError(f"percnn_amd: invalid batch size {B}")
+    out = torch.empty(B, dtype=traj.dtype, device=traj.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=traj.device)
+    f = getattr(L, "percnn_pi_batch_traj_obs_sqerr_" + _SUF[traj.dtype])
+    with torch.cuda.device(traj.device):
+        _lib.check(f(traj.data_ptr(), target.data_ptr() if target is not None else None, _mask_bytes(frame_mask, traj.shape[0]),
+                     traj.shape[0], len(shape), _lib.shape_arg(shape), _strides_arg(strides), B, float(scale), out.data_ptr(),
+                     ws.data_ptr(), ws.numel(), _stream()), "batch_traj_obs_sqerr")
+    return out
+
+
+def rollout_bwd_obs_sqerr_batched(traj: torch.Tensor, P: torch.Tensor, target: Optional[torch.Tensor] = None,
+                                  frame_mask: Optional[Sequence[bool]] = None, strides: Sequence[int] = (), scale: float = 1.0,
+                                  dev_scale: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None, options=None,
+                                  g_h0: Optional[torch.Tensor] = None, ensemble: Optional[bool] = None):
+    """``rollout_bwd_sqerr_batched`` for the loss on the lattice of the selected frames against the compact target
+    [n,B,2,*Sc] (``percnn_pi_{batch,ensemble}_rollout_bwd_obs_sqerr_*``): no dL/dtraj, no scatter of the observed frames.
+    ensemble: None = by the rank of P ([np] / [B,np]).  B = 1 runs the same launches with one sample."""
+    _require(traj, "traj"); _require(P, "params", traj.dtype)
+    _check_compact(target, traj, frame_mask, strides)
+    T, B, shape = traj.shape[0] - 1, int(traj.shape[1]), traj.shape[3:]
+    if ensemble is None:
+        ensemble = P.dim() == 2
+    if P.dim() != (2 if ensemble else 1):
+        raise ValueError(f"{'one parameter block per sample [B,np]' if ensemble else 'one parameter block [np]'}, got {tuple(P.shape)}")
+    kind = "ensemble" if ensemble else "batch"
+    if ensemble and P.shape[0] != B:
+        raise ValueError(f"one parameter block per sample: P [{B},np], got {tuple(P.shape)}")
+    hc = _hc_of(P[0] if ensemble else P)
+    if dev_scale is not None:
+        dev_scale = dev_scale.reshape(B).to(traj.dtype).contiguous()
+    L = _lib.lib()
+    if g_h0 is None:
+        g_h0 = torch.empty_like(traj[0])
+    pg = torch.zeros(tuple(P.shape), dtype=torch.float64, device=traj.device)
+    if ws is None:
+        nbytes = getattr(L, f"percnn_pi_{kind}_rollout_bwd_workspace_bytes")(hc, len(shape), _lib.shape_arg(shape), B, T,
+                                                                            traj.dtype.itemsize)
+        if nbytes == 0:
+            raise RuntimeError("percnn_amd: invalid problem shape, batch size or block kind")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=traj.device)
+    f = getattr(L, f"percnn_pi_{kind}_rollout_bwd_obs_sqerr_" + _SUF[traj.dtype])
+    with torch.cuda.device(traj.device):
+        _lib.check(f(traj.data_ptr(), target.data_ptr() if target is not None else None, _mask_bytes(frame_mask, T + 1),
+                     _strides_arg(strides), float(scale), dev_scale.data_ptr() if dev_scale is not None else None,
+                     g_h0.data_ptr(), pg.data_ptr(), ws.data_ptr(), ws.numel(), P.data_ptr(), hc, len(shape),
+                     _lib.shape_arg(shape), B, T, _lib.options_arg(options), _stream()), f"{kind}_rollout_bwd_obs_sqerr")
+    return g_h0, pg
+
+
+class PiRolloutObsSqErrBatchedFunction(torch.autograd.Function):
+    """``PiRolloutSqErrBatchedFunction`` on sparse observations: loss[b] = weight * sum_k sum over the lattice of
+    (h_{t_k}[b] - target[k, b])^2, a [B] tensor, as ONE autograd node.  Forward = the batched (P [np]) or ensemble (P [B,np])
+    rollout + one reduction per sample over the lattice; backward = the sweep with the incoming [B] gradient as per-sample
+    factors, the loss gradient formed in-kernel at the lattice points -- no dL/dtraj [T+1,B,2,*S], no scatter, no host
+    synchronisation.  Returns (loss, traj); traj is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, h0, P, steps, target, frame_mask, strides, weight, options):
+        _native()
+        P = P.contiguous()
+        op = torch.ops.percnn.pi_rollout_ensemble if P.dim() == 2 else torch.ops.percnn.pi_rollout_batched
+        traj = op(h0, P, steps, _options_str(options))
+        loss = traj_obs_sqerr_batched(traj, target, frame_mask, strides, weight)
+        ctx.save_for_backward(traj, P) if target is None else ctx.save_for_backward(traj, P, target)
+        ctx.meta = (frame_mask, strides, float(weight), options)
+        ctx.mark_non_differentiable(traj)
+        ctx.set_materialize_grads(False)
+        return loss, traj
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_traj):
+        if g_loss is None:
+            return None, None, None, None, None, None, None, None
+        saved = ctx.saved_tensors
+        traj, P = saved[0], saved[1]
+        target = saved[2] if len(saved) > 2 else None
+        frame_mask, strides, weight, options = ctx.meta
+        g_h0, pg = rollout_bwd_obs_sqerr_batched(traj, P, target, frame_mask, strides, 2.0 * weight, g_loss.contiguous(),
+                                                 options=options)
+        return g_h0, pg.to(P.dtype), None, None, None, None, None, None
+
+
+def _pi_rollout_obs_sqerr_samples(what, h0, P, steps, target, t_idx, strides, reduction, options):
+    if h0.dim() not in (4, 5) or h0.shape[1] != 2:
+        raise ValueError(f"{what}: h0 must be [B,2,*S], got {tuple(h0.shape)}")
+    sel, mask, strides, Sc, weight = obs_selection(steps, t_idx, strides, tuple(h0.shape[2:]), reduction, what)
+    if target is not None:
+        if tuple(target.shape) != (len(sel), int(h0.shape[0]), 2) + Sc:
+            raise ValueError(f"{what}: target must be [n, B, 2, *ceil(S / s)] = {(len(sel), int(h0.shape[0]), 2) + Sc}, "
+                             f"got {tuple(target.shape)}")
+        target = target.detach().contiguous()
+    return PiRolloutObsSqErrBatchedFunction.apply(h0, P, int(steps), target, mask, strides, weight, options)
+
+
+def pi_rollout_obs_sqerr_batched(h0: torch.Tensor, P: torch.Tensor, steps: int, target: Optional[torch.Tensor],
+                                 t_idx: Sequence[int], strides, reduction: str = "mean", options=None):
+    """-> (loss [B], traj [T+1,B,2,*S] detached): ``loss[b] = mse_loss(traj[t_idx][:, b, :, ::s_0, ::s_1(, ::s_2)],
+    target[:, b], reduction)`` of the T-step rollouts from h0 [B,2,*S] with ONE block P [np], as one autograd node --
+    the reference's data loss (``output[0:-1:20, :, ::4, ::4]`` against the coarse truth) for B trajectories at once.
+    target: [len(t_idx), B, 2, *ceil(S / s)], compact in time and space (None: 0); t_idx strictly increasing (negative
+    indices count from the end); strides an int or one per axis.  The parameter gradient is the sum over the samples;
+    target gets no gradient."""
+    if P.dim() != 1:
+        raise ValueError(f"pi_rollout_obs_sqerr_batched: one parameter block [np], got {tuple(P.shape)}")
+    return _pi_rollout_obs_sqerr_samples("pi_rollout_obs_sqerr_batched", h0, P, steps, target, t_idx, strides, reduction, options)
+
+
+def pi_rollout_obs_sqerr_ensemble(h0: torch.Tensor, P: torch.Tensor, steps: int, target: Optional[torch.Tensor],
+                                  t_idx: Sequence[int], strides, reduction: str = "mean", options=None):
+    """``pi_rollout_obs_sqerr_batched`` with one block per sample, P [B,np]: loss[b] is member b's loss, and row b of the
+    [B,np] parameter gradient is the gradient of member b alone."""
+    if P.dim() != 2 or P.shape[0] != h0.shape[0]:
+        raise ValueError(f"pi_rollout_obs_sqerr_ensemble: one parameter block per sample [B,np], got {tuple(P.shape)}")
+    return _pi_rollout_obs_sqerr_samples("pi_rollout_obs_sqerr_ensemble", h0, P, steps, target, t_idx, strides, reduction, options)
+
+
 def step_fwd(h: torch.Tensor, P: torch.Tensor, out: Optional[torch.Tensor] = None, slab: bool = False,
              halo: int = 2, skip: int = 0, planes: Optional[Sequence[int]] = None, options=None):
     """h: [2,*S] -> next state.  slab=True: h is a local slab [2, n0+2*halo, ...] (see include/percnn_pi.h);

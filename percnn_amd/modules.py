@@ -954,18 +954,32 @@ class RCNN(nn.Module):
         self.last_trajectory = traj
         return loss
 
-    def sample_losses(self, target: Optional[torch.Tensor] = None, t_slice=slice(None), reduction: str = "mean") -> torch.Tensor:
+    def sample_losses(self, target: Optional[torch.Tensor] = None, t_slice=slice(None), reduction: str = "mean",
+                      space_stride: int = 1) -> torch.Tensor:
         """[B]: ``loss_mse`` of every sample on its own -- ``F.mse_loss(traj[t_slice][:, b], target[t_slice][:, b], reduction)``
         of the batched trajectory [step+1, B, 2, *S] (``target`` None: 0; the full-trajectory tensor otherwise) -- with the B
         rollouts as ONE autograd node and no dL/dtraj (``pi_rollout_sqerr_batched`` / ``pi_rollout_sqerr_ensemble``).  For a
         batched initial state with a Pi-block cell, for a ``CellEnsemble`` (the gradient of loss b reaches member b's
         parameters) and for B = 1 ([1]).  ``sample_losses().mean().backward()``, a sum or any weighting of the samples is the
-        caller's line.  Needs a dense ``effective_step``; the detached trajectory is kept in ``self.last_trajectory``."""
+        caller's line.  Needs a dense ``effective_step``; the detached trajectory is kept in ``self.last_trajectory``.
+        ``space_stride > 1``: the reference's data loss on coarse measurements, per sample -- ``target`` is compact, shaped
+        like ``traj[t_slice][:, :, :, ::s, ::s(, ::s)]`` (None: 0), and the loss lives on that sub-lattice of the selected
+        frames (``pi_rollout_obs_sqerr_batched`` / ``pi_rollout_obs_sqerr_ensemble``); what ``loss_mse(space_stride > 1)``
+        is for one trajectory, still one autograd node without a dL/dtraj."""
         if self.effective_step != list(range(self.step)):
             raise ValueError("sample_losses() indexes the dense output list: effective_step must be list(range(step))")
         if hasattr(self, "UpconvBlock"):
             self.init_state = self.UpconvBlock(self.init_state_low)
         frames = list(range(self.step + 1))[t_slice]
+        if space_stride != 1:
+            if self._ensemble("RCNN.sample_losses()"):
+                op = F_pi.pi_rollout_obs_sqerr_ensemble
+            else:
+                self._check_batchable("RCNN.sample_losses()")
+                op = F_pi.pi_rollout_obs_sqerr_batched
+            loss, traj = op(self.init_state, self._block(), self.step, target, frames, int(space_stride), reduction)
+            self.last_trajectory = traj
+            return loss
         if self._ensemble("RCNN.sample_losses()"):
             op = F_pi.pi_rollout_sqerr_ensemble
         else:
