@@ -766,6 +766,61 @@ int percnn_pi_ensemble_rollout_bwd_obs_sqerr_f64(const double *traj, const doubl
                                                  int hc, int ndim, const int64_t *shape, int batch, int T, const char *options,
                                                  void *stream);
 
+/* ---- Batched residual loss: the physics-residual loss per sample -----------------------------------------------------------
+ * percnn_pi_residual_sqloss_* (above) for every sample of a frame-major trajectory traj [nframes+1 ..][B][2][*S], in the launches
+ * of one sample:  loss_out[b] = L of sample b, as defined there (the reference's loss_gen of that member alone).
+ *   _batch_    : params [36], one equation for every sample.
+ *   _ensemble_ : params [B][36], sample b scored against block b -- dt, D_u, D_v, the taps and the reaction may differ per row.
+ * The signatures are those of the unbatched entries with `batch` after `shape`.
+ *   _sqloss     : loss_out [B] (device, compute type).  One reducing launch of the `sample` flavours of the unbatched kernels
+ *                 (the 2D tile pass by the unbatched rule: both extents >= 34, 16-byte lanes, option "tile" != 0; else the
+ *                 generic pass) and one finishing launch, a wave per sample over that sample's partial sums in fixed order.
+ *                 workspace: 8-byte aligned, batch * R doubles, R = the partial rows the call writes per sample, chosen per
+ *                 call (percnn_pi_debug_residual_sqloss_accepts reports it; at most max(workgroups per frame, 16384 / batch)).
+ *                 percnn_pi_batch_residual_sqloss_workspace_bytes(batch) is the size that suffices for every grid (256 KiB per
+ *                 sample).
+ *   _sqloss_bwd : g_traj [nout_frames][B][2][*S] = g_loss[b] * dL_b/dtraj, written completely (frames the loss does not see are
+ *                 zeroed); g_loss: DEVICE array of B elements of the compute type (NULL = ones); scratch [nframes][B][2][*S].
+ *                 Two launches.  Per point the arithmetic is the unbatched kernels': g_traj[:, b] is bit-identical to
+ *                 percnn_pi_residual_sqloss_bwd_* on sample b alone under the same factor.
+ * The 3D brick pass (pi_res3d_brick_kernel) has no sample flavour: a batched 3D call takes the generic pass, also for batch == 1.
+ * batch == 1 runs the same launches with one sample.  Validation before any launch: batch < 1 or > 65535, a NULL pointer (traj,
+ * params, loss_out / scratch, g_traj), nframes < 1, nout_frames < nframes + 1 or > 65535, a bad ndim / shape -> PERCNN_PI_EINVAL;
+ * more than 32768 workgroups per frame and sample -> PERCNN_PI_ETOOLARGE; a workspace that is NULL, too small or not 8-byte aligned
+ * -> PERCNN_PI_EWORKSPACE.  No grid is declined that the unbatched entry takes for one sample: that entry takes 16384 generic
+ * workgroups or 16384 bricks of up to two planes, which are at most 32768 generic workgroups (some grids it declines are
+ * taken here).
+ * percnn_pi_debug_residual_sqloss_accepts (host only, nothing is launched): bit 0 of the result = the unbatched entry takes the
+ * grid, bit 1 = the batched / ensemble entries take it, *out_rows (nullable) = R; elem_size 4 / 8; aligned16 != 0: the
+ * trajectory starts at a multiple of 16 bytes.  Negative: PERCNN_PI_EINVAL. */
+size_t percnn_pi_batch_residual_sqloss_workspace_bytes(int batch);
+int percnn_pi_debug_residual_sqloss_accepts(int ndim, const int64_t *shape, int elem_size, int batch, int nframes, int aligned16,
+                                            int *out_rows);
+int percnn_pi_batch_residual_sqloss_f32(const float *traj, const float *params, int ndim, const int64_t *shape, int batch,
+                                        int nframes, int weighted, float *loss_out, void *workspace, size_t workspace_bytes,
+                                        void *stream);
+int percnn_pi_batch_residual_sqloss_f64(const double *traj, const double *params, int ndim, const int64_t *shape, int batch,
+                                        int nframes, int weighted, double *loss_out, void *workspace, size_t workspace_bytes,
+                                        void *stream);
+int percnn_pi_batch_residual_sqloss_bwd_f32(const float *traj, const float *g_loss, const float *params, int ndim,
+                                            const int64_t *shape, int batch, int nframes, int nout_frames, int weighted,
+                                            float *scratch, float *g_traj, void *stream);
+int percnn_pi_batch_residual_sqloss_bwd_f64(const double *traj, const double *g_loss, const double *params, int ndim,
+                                            const int64_t *shape, int batch, int nframes, int nout_frames, int weighted,
+                                            double *scratch, double *g_traj, void *stream);
+int percnn_pi_ensemble_residual_sqloss_f32(const float *traj, const float *params, int ndim, const int64_t *shape, int batch,
+                                           int nframes, int weighted, float *loss_out, void *workspace, size_t workspace_bytes,
+                                           void *stream);
+int percnn_pi_ensemble_residual_sqloss_f64(const double *traj, const double *params, int ndim, const int64_t *shape, int batch,
+                                           int nframes, int weighted, double *loss_out, void *workspace, size_t workspace_bytes,
+                                           void *stream);
+int percnn_pi_ensemble_residual_sqloss_bwd_f32(const float *traj, const float *g_loss, const float *params, int ndim,
+                                               const int64_t *shape, int batch, int nframes, int nout_frames, int weighted,
+                                               float *scratch, float *g_traj, void *stream);
+int percnn_pi_ensemble_residual_sqloss_bwd_f64(const double *traj, const double *g_loss, const double *params, int ndim,
+                                               const int64_t *shape, int batch, int nframes, int nout_frames, int weighted,
+                                               double *scratch, double *g_traj, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,5 +22,6 @@ from .modules import RCNNCell, RCNN, Upscaler, Stage3LambdaOmegaCell, Stage3Burg
 from . import ops  # noqa: F401  (registers torch.ops.percnn.*)
 from . import slab, synthetic, physics, stage1  # noqa: F401
 from .stage1 import Stage1Cell  # noqa: F401
+from .physics import physics_loss_batched  # noqa: F401
 
 __version__ = "0.1.0"

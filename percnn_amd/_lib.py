@@ -68,8 +68,10 @@ EXPORTS = [
                 "batch_step_fwd", "batch_step_bwd", "batch_rollout_fwd", "batch_rollout_bwd", "ensemble_step_fwd",
                 "ensemble_step_bwd", "ensemble_rollout_fwd", "ensemble_rollout_bwd", "batch_traj_sqerr",
                 "batch_rollout_bwd_sqerr", "ensemble_rollout_bwd_sqerr", "batch_traj_obs_sqerr",
-                "batch_rollout_bwd_obs_sqerr", "ensemble_rollout_bwd_obs_sqerr")] + [
-    "percnn_pi_batch_traj_sqerr_workspace_bytes",
+                "batch_rollout_bwd_obs_sqerr", "ensemble_rollout_bwd_obs_sqerr", "batch_residual_sqloss",
+                "batch_residual_sqloss_bwd", "ensemble_residual_sqloss", "ensemble_residual_sqloss_bwd")] + [
+    "percnn_pi_batch_traj_sqerr_workspace_bytes", "percnn_pi_batch_residual_sqloss_workspace_bytes",
+    "percnn_pi_debug_residual_sqloss_accepts",
     "percnn_pi_batch_bwd_workspace_bytes", "percnn_pi_batch_rollout_bwd_workspace_bytes",
     "percnn_pi_ensemble_bwd_workspace_bytes", "percnn_pi_ensemble_rollout_bwd_workspace_bytes",
     "percnn_pi_s1_param_count", "percnn_pi_s1_step_fwd_f32", "percnn_pi_s1_rollout_fwd_f32",
@@ -234,6 +236,11 @@ def lib() -> ctypes.CDLL:
         f.restype, f.argtypes = ci, [vp, vp, ci, i64p, ci, ci, vp, vp, sz, vp]
         f = getattr(L, f"percnn_pi_residual_sqloss_bwd_{suf}")
         f.restype, f.argtypes = ci, [vp, vp, vp, ci, i64p, ci, ci, ci, vp, vp, vp]
+        for kind in ("batch", "ensemble"):                  # the unbatched signatures with `batch` after `shape`
+            f = getattr(L, f"percnn_pi_{kind}_residual_sqloss_{suf}")
+            f.restype, f.argtypes = ci, [vp, vp, ci, i64p, ci, ci, ci, vp, vp, sz, vp]
+            f = getattr(L, f"percnn_pi_{kind}_residual_sqloss_bwd_{suf}")
+            f.restype, f.argtypes = ci, [vp, vp, vp, ci, i64p, ci, ci, ci, ci, vp, vp, vp]
         f = getattr(L, f"percnn_pi_rollout_fwd_{suf}")
         f.restype, f.argtypes = ci, [vp, vp, ci, ci, i64p, ci, vp]
         f = getattr(L, f"percnn_pi_rollout_bwd_{suf}")
@@ -291,6 +298,10 @@ def lib() -> ctypes.CDLL:
     L.percnn_pi_ensemble_rollout_bwd_workspace_bytes.restype = sz
     L.percnn_pi_ensemble_rollout_bwd_workspace_bytes.argtypes = [ci, ci, i64p, ci, ci, ci]
     L.percnn_pi_residual_sqloss_workspace_bytes.restype, L.percnn_pi_residual_sqloss_workspace_bytes.argtypes = sz, []
+    L.percnn_pi_batch_residual_sqloss_workspace_bytes.restype = sz
+    L.percnn_pi_batch_residual_sqloss_workspace_bytes.argtypes = [ci]
+    L.percnn_pi_debug_residual_sqloss_accepts.restype = ci
+    L.percnn_pi_debug_residual_sqloss_accepts.argtypes = [ci, i64p, ci, ci, ci, ci, ctypes.POINTER(ci)]
     L.percnn_pi_s1_param_count.restype = sz
     L.percnn_pi_s1_param_count.argtypes = []
     L.percnn_pi_s1_step_fwd_f32.restype, L.percnn_pi_s1_step_fwd_f32.argtypes = ci, [vp, vp, vp, i64p, vp]

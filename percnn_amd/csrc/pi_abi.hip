@@ -3419,6 +3419,162 @@ int residual_sqloss_bwd_impl(const T* traj, const T* g_loss, const T* Q, int ndi
     return (int)hipGetLastError();
 }
 
+
+// ---- the same loss per sample of a frame-major trajectory [F][B][2][*S] (include/percnn_pi.h "Batched residual loss") ----
+// The sample flavours of the kernels above: the batch is grid y of the generic passes and grid z of the 2D tile pass; every
+// workgroup runs the kernel's one body on one sample.  ens: Q is [B][NPOLY], sample b scored against its own equation.
+// No brick flavour: a batched 3D call takes the generic pass.  Its bound on the workgroups per frame is therefore twice the
+// unbatched one: the unbatched call takes a 3D grid on bricks of one or two planes while nblk = nrg * ceil(n0 / rz) <= 16384,
+// and the generic pass needs gx = ceil(n0 * n1 * cpr / 256) <= n0 * nrg <= 2 * nblk workgroups for it (same 16-byte lanes, nrg =
+// ceil(n1 * cpr / 256)) -- so no grid is declined here that the unbatched call takes for one sample.
+constexpr unsigned BATCH_RESLOSS_BLOCKS = 2 * RESLOSS_SLOTS;
+
+// does residual_sqloss_impl turn the grid down?  (its three dispatch rules, for the acceptance test of the batched entries)
+template <typename T>
+bool resloss_declines(const Problem& p, int vec, bool aligned16)
+{
+    if (p.ndim == 3 && p.opt.brick3d) {
+        const int brz = brick_rz_for<T>(p, vec, false, false);
+        if (brz == 1 || brz == 2) {
+            const pi::BrickGeom b = make_brick_geom(p, pi::vec_width<T>::value, brz, pi::BRICK_NT, false);
+            if (b.nblk > 0 && b.nblk <= RESLOSS_SLOTS) return false;
+        }
+    }
+    if (p.ndim == 2 && p.opt.tile && vec == pi::vec_width<T>::value && p.n0 >= TILE_B + 2 && p.W >= TILE_B + 2 && aligned16) {
+        const pi::TileGeom tg = make_tile_geom(p, TILE_B, TILE_B);
+        if ((unsigned)(((p.n0 + TILE_B - 1) / TILE_B) * tg.tiles_x) <= RESLOSS_SLOTS) return false;
+    }
+    const Geom g = make_geom(p);
+    return ((long)g.rows * (g.W / vec) + 255) / 256 > (long)RESLOSS_SLOTS;
+}
+
+// The loss pass of a batched call: the 2D tile pass by the unbatched rule, else the generic pass.  blocks = workgroups per frame
+// and sample, gy = frame slots -- about as many workgroups over the whole batch as the unbatched pass launches for one
+// trajectory.  Sample b's partial sums are rows [b * R, (b + 1) * R), R = blocks * gy: the bound is chosen per call.
+struct BatchResPlan { bool tile; unsigned blocks, gy; long nchunks; };
+template <typename T>
+int batch_resloss_plan(const Problem& p, int vec, bool aligned16, int batch, int nframes, BatchResPlan& pl)
+{
+    const unsigned B = (unsigned)batch;
+    if (p.ndim == 2 && p.opt.tile && vec == pi::vec_width<T>::value && p.n0 >= TILE_B + 2 && p.W >= TILE_B + 2 && aligned16) {
+        const pi::TileGeom tg = make_tile_geom(p, TILE_B, TILE_B);
+        const unsigned tiles = (unsigned)(((p.n0 + TILE_B - 1) / TILE_B) * tg.tiles_x);
+        if (tiles <= RESLOSS_SLOTS) {
+            pl = BatchResPlan{true, tiles, std::max(1u, RESLOSS_WGS / (tiles * B)), 0};
+            if (pl.gy > (unsigned)nframes) pl.gy = (unsigned)nframes;
+            return 0;
+        }
+    }
+    const Geom g = make_geom(p);
+    const long nchunks = (long)g.rows * (g.W / vec);
+    const long gx = (nchunks + 255) / 256;
+    if (gx > (long)BATCH_RESLOSS_BLOCKS) return PERCNN_PI_ETOOLARGE;
+    pl = BatchResPlan{false, (unsigned)gx, std::max(1u, RESLOSS_SLOTS / ((unsigned)gx * B)), nchunks};
+    if (pl.gy > (unsigned)nframes) pl.gy = (unsigned)nframes;
+    return 0;
+}
+
+template <typename T>
+int batch_residual_sqloss_impl(const T* traj, const T* Q, int ndim, const int64_t* shape, int batch, int nframes, int weighted,
+                               T* loss_out, void* ws, size_t ws_bytes, void* stream, bool ens)
+{
+    Problem p;
+    if (int rc = batch_problem(0, ndim, shape, batch, p, nullptr, false)) return rc;
+    if (!traj || !Q || !loss_out || nframes < 1) return PERCNN_PI_EINVAL;
+    const int vec = pick_vec<T>(p, {traj});
+    BatchResPlan pl;
+    if (int rc = batch_resloss_plan<T>(p, vec, reinterpret_cast<uintptr_t>(traj) % 16 == 0, batch, nframes, pl)) return rc;
+    const int rows = (int)(pl.blocks * pl.gy), np = pi::NPOLY;
+    if (!ws || ws_bytes < (size_t)batch * rows * sizeof(double) || reinterpret_cast<uintptr_t>(ws) % 8) return PERCNN_PI_EWORKSPACE;
+    const Geom g = make_geom(p);
+    auto st = static_cast<hipStream_t>(stream);
+    double* partials = static_cast<double*>(ws);
+    const long sample = 2 * p.n, frame = (long)batch * sample;
+    const double scale = resloss_scale(p, ndim, shape, nframes, weighted);
+    const unsigned B = (unsigned)batch;
+    if (pl.tile) {
+        const pi::TileGeom tg = make_tile_geom(p, TILE_B, TILE_B);
+        const size_t lds = (size_t)2 * (TILE_B + 8) * (TILE_B + 4) * sizeof(T);
+        const dim3 grid(pl.blocks, pl.gy, B);
+        if (ens) hipLaunchKernelGGL((pi::pi_res2d_tile_kernel<T, TILE_B, TILE_B, 256, long, int, int>), grid, dim3(256), lds, st, traj,
+                                    partials, Q, tg, frame, nframes, weighted, sample, rows, np);
+        else     hipLaunchKernelGGL((pi::pi_res2d_tile_kernel<T, TILE_B, TILE_B, 256, long, int>), grid, dim3(256), lds, st, traj,
+                                    partials, Q, tg, frame, nframes, weighted, sample, rows);
+    } else {
+        const pi::FrameGrid fg = make_frame_grid(pl.nchunks, pl.gy);
+        const pi::ResLoss rl{scale, nullptr, weighted};
+        const dim3 grid(pi::frame_grid_blocks(fg), B);
+        constexpr int V = pi::vec_width<T>::value;
+#define PI_RSQ(NDIM, VEC)                                                                                                       \
+    do {                                                                                                                        \
+        if (ens) hipLaunchKernelGGL((pi::pi_residual_sq_kernel<T, NDIM, VEC, false, long, int, int>), grid, dim3(256), 0, st,   \
+                                    traj, (T*)nullptr, partials, Q, g, nframes, rl, fg, sample, rows, np);                      \
+        else     hipLaunchKernelGGL((pi::pi_residual_sq_kernel<T, NDIM, VEC, false, long, int>), grid, dim3(256), 0, st, traj,  \
+                                    (T*)nullptr, partials, Q, g, nframes, rl, fg, sample, rows);                                \
+    } while (0)
+        if (ndim == 2) { if (vec == 1) PI_RSQ(2, 1); else PI_RSQ(2, V); }
+        else           { if (vec == 1) PI_RSQ(3, 1); else PI_RSQ(3, V); }
+#undef PI_RSQ
+    }
+    hipLaunchKernelGGL((pi::pi_sqerr_finish_kernel<T, int>), dim3(B), dim3(64), 0, st, partials, rows, scale, loss_out, rows);
+    return (int)hipGetLastError();
+}
+
+// host-only: does the unbatched / the batched residual loss take the grid?  bit 0 / bit 1; out_rows: partial rows per sample the
+// batched call writes (its workspace: batch * rows doubles).  aligned16: the trajectory starts at a multiple of 16 bytes
+template <typename T>
+int debug_resloss_accepts(int ndim, const int64_t* shape, int batch, int nframes, bool aligned16, int* out_rows)
+{
+    Problem p;
+    if (int rc = batch_problem(0, ndim, shape, batch, p, nullptr, false)) return rc;
+    if (nframes < 1) return PERCNN_PI_EINVAL;
+    const int vec = aligned16 ? pick_vec<T>(p, {}) : 1;
+    BatchResPlan pl{};
+    const bool many = batch_resloss_plan<T>(p, vec, aligned16, batch, nframes, pl) == 0;
+    if (out_rows) *out_rows = many ? (int)(pl.blocks * pl.gy) : 0;
+    return (resloss_declines<T>(p, vec, aligned16) ? 0 : 1) | (many ? 2 : 0);
+}
+
+// g_traj [nout][B][2][*S] = g_loss[b] * dL_b/dtraj, written completely; scratch [nframes][B][2][*S].  Two launches of grid
+// (blocks, B); g_loss: B elements on the device (NULL = ones).
+template <typename T>
+int batch_residual_sqloss_bwd_impl(const T* traj, const T* g_loss, const T* Q, int ndim, const int64_t* shape, int batch,
+                                   int nframes, int nout, int weighted, T* scratch, T* g_traj, void* stream, bool ens)
+{
+    Problem p;
+    if (int rc = batch_problem(0, ndim, shape, batch, p, nullptr, false)) return rc;
+    if (!traj || !Q || !scratch || !g_traj || nframes < 1 || nout < nframes + 1 || nout > 65535) return PERCNN_PI_EINVAL;
+    const Geom g = make_geom(p);
+    const int vec = pick_vec<T>(p, {traj, scratch, g_traj});
+    const long nchunks = (long)g.rows * (g.W / vec);
+    const pi::FrameGrid fg1 = make_frame_grid(nchunks, (unsigned)nframes), fg2 = make_frame_grid(nchunks, (unsigned)nout);
+    auto st = static_cast<hipStream_t>(stream);
+    const pi::ResLoss rl{resloss_scale(p, ndim, shape, nframes, weighted), g_loss, weighted};
+    const long sample = 2 * p.n;
+    const int np = pi::NPOLY;
+    const unsigned B = (unsigned)batch;
+    const dim3 grid1(pi::frame_grid_blocks(fg1), B), grid2(pi::frame_grid_blocks(fg2), B);
+    constexpr int V = pi::vec_width<T>::value;
+#define PI_RSB(NDIM, VEC)                                                                                                       \
+    do {                                                                                                                        \
+        if (ens) {                                                                                                              \
+            hipLaunchKernelGGL((pi::pi_residual_sq_kernel<T, NDIM, VEC, true, long, int, int>), grid1, dim3(256), 0, st, traj,  \
+                               scratch, (double*)nullptr, Q, g, nframes, rl, fg1, sample, 0, np);                               \
+            hipLaunchKernelGGL((pi::pi_residual_adj_kernel<T, NDIM, VEC, true, long, int>), grid2, dim3(256), 0, st, traj,      \
+                               (const T*)scratch, g_traj, Q, g, fg2, nframes, sample, np);                                      \
+        } else {                                                                                                                \
+            hipLaunchKernelGGL((pi::pi_residual_sq_kernel<T, NDIM, VEC, true, long, int>), grid1, dim3(256), 0, st, traj,       \
+                               scratch, (double*)nullptr, Q, g, nframes, rl, fg1, sample, 0);                                   \
+            hipLaunchKernelGGL((pi::pi_residual_adj_kernel<T, NDIM, VEC, true, long>), grid2, dim3(256), 0, st, traj,           \
+                               (const T*)scratch, g_traj, Q, g, fg2, nframes, sample);                                          \
+        }                                                                                                                       \
+    } while (0)
+    if (ndim == 2) { if (vec == 1) PI_RSB(2, 1); else PI_RSB(2, V); }
+    else           { if (vec == 1) PI_RSB(3, 1); else PI_RSB(3, V); }
+#undef PI_RSB
+    return (int)hipGetLastError();
+}
+
 }  // namespace
 
 namespace {
@@ -4443,5 +4599,33 @@ size_t percnn_pi_residual_sqloss_workspace_bytes(void) { return RESLOSS_SLOTS * 
 
 PI_EXPORT_RESLOSS(f32, float)
 PI_EXPORT_RESLOSS(f64, double)
+
+// the rows a call writes per sample: max(workgroups per frame, 16384 / batch) at the most, workgroups per frame <= 32768
+size_t percnn_pi_batch_residual_sqloss_workspace_bytes(int batch)
+{ return batch < 1 ? 0 : (size_t)batch * BATCH_RESLOSS_BLOCKS * sizeof(double); }
+int percnn_pi_debug_residual_sqloss_accepts(int ndim, const int64_t* shape, int elem_size, int batch, int nframes, int aligned16,
+                                            int* out_rows)
+{
+    if (elem_size == 4) return debug_resloss_accepts<float>(ndim, shape, batch, nframes, aligned16 != 0, out_rows);
+    if (elem_size == 8) return debug_resloss_accepts<double>(ndim, shape, batch, nframes, aligned16 != 0, out_rows);
+    return PERCNN_PI_EINVAL;
+}
+
+#define PI_EXPORT_BATCH_RESLOSS(KIND, ENS, SUF, T)                                                                  \
+    int percnn_pi_##KIND##_residual_sqloss_##SUF(const T* traj, const T* params, int ndim, const int64_t* shape,    \
+                                                 int batch, int nframes, int weighted, T* loss_out, void* workspace, \
+                                                 size_t workspace_bytes, void* stream)                              \
+    { return batch_residual_sqloss_impl<T>(traj, params, ndim, shape, batch, nframes, weighted, loss_out, workspace, \
+                                           workspace_bytes, stream, ENS); }                                         \
+    int percnn_pi_##KIND##_residual_sqloss_bwd_##SUF(const T* traj, const T* g_loss, const T* params, int ndim,     \
+                                                     const int64_t* shape, int batch, int nframes, int nout_frames, \
+                                                     int weighted, T* scratch, T* g_traj, void* stream)             \
+    { return batch_residual_sqloss_bwd_impl<T>(traj, g_loss, params, ndim, shape, batch, nframes, nout_frames,      \
+                                               weighted, scratch, g_traj, stream, ENS); }
+
+PI_EXPORT_BATCH_RESLOSS(batch, false, f32, float)
+PI_EXPORT_BATCH_RESLOSS(batch, false, f64, double)
+PI_EXPORT_BATCH_RESLOSS(ensemble, true, f32, float)
+PI_EXPORT_BATCH_RESLOSS(ensemble, true, f64, double)
 
 }  // extern "C"

@@ -1051,20 +1051,33 @@ pi_residual_kernel(const T* __restrict__ traj, T* __restrict__ R, const T* __res
 //   GRAD = false: partials[block] = sum over this block's chunks and its frames f = blockIdx.y, += gridDim.y of w * R^2 (double)
 //   GRAD = true : G(f, x) = a * w * R(f, x),  a = 2 * scale * (upstream gradient, read from the device) -- what
 //                 pi_residual_adj_kernel<FULL> turns into dL/dtraj
+// X... = `long sample, int rows` (grid (blocks, B)): frame-major trajectory [F][B][2][*S], sample = 2 * ss; the workgroups of
+// grid row b run the body on sample b -- frames B * sample apart, partial sums in rows [b * rows, (b + 1) * rows), G laid out as
+// traj, a_b from g_dev[b] (loss_factor's sample form).  X... = `long sample, int rows, int np`: + the equation block of sample
+// b, Q + b * np (wave-uniform: scalar loads as before).  pi_residual_adj_kernel: the same two without `rows`.
 struct ResLoss {
     double scale;          // 1 / (frames * prod(n + 1))  (weighted)  or  1 / (frames * prod(n))
     const void* g_dev;     // GRAD: device pointer to the upstream scalar gradient in the compute type (nullptr = 1)
     int weighted;
 };
 
-template <typename T, int NDIM, int VEC, bool GRAD>
+template <typename T, int NDIM, int VEC, bool GRAD, typename... X>
 __global__ void __launch_bounds__(256)
 pi_residual_sq_kernel(const T* __restrict__ traj, T* __restrict__ G, double* __restrict__ partials,
-                      const T* __restrict__ Q, Geom g, int nframes, ResLoss rl, FrameGrid fg)
+                      const T* __restrict__ Q, Geom g, int nframes, ResLoss rl, FrameGrid fg, X... x)
 {
     __shared__ double red[256 / WAVE];
     const FrameBlock fb = frame_block(fg);
     if (!fb.live) return;
+    long fstride = 2 * g.ss;                              // elements between two frames
+    if constexpr (sizeof...(X) >= 2) {
+        const long sbase = (long)blockIdx.y * flavour_arg<0>(x...);      // sample blockIdx.y
+        traj += sbase;
+        if constexpr (GRAD) G += sbase;
+        else partials += (long)blockIdx.y * flavour_arg<1>(x...);
+        fstride = (long)gridDim.y * flavour_arg<0>(x...);
+    }
+    if constexpr (sizeof...(X) == 3) Q += (long)blockIdx.y * flavour_arg<2>(x...);    // its equation
     const int cpr = g.W / VEC;
     const long nchunks = (long)g.rows * cpr;
     const long cid = (long)fb.bx * blockDim.x + threadIdx.x;
@@ -1072,11 +1085,14 @@ pi_residual_sq_kernel(const T* __restrict__ traj, T* __restrict__ G, double* __r
     int i0 = 0, i1 = 0, x0 = 0;
     long e = 0;
     if (live) chunk_coords<NDIM>(g, cid, cpr, VEC, i0, i1, x0, e);
-    const long frame = 2 * g.ss;
+    const long frame = fstride;
     const T dt = Q[P_DT];
     const T wrow = rl.weighted ? T((i0 == 0 ? 2 : 1) * ((NDIM == 3 && i1 == 0) ? 2 : 1)) : T(1);
     T a = T(1);
-    if constexpr (GRAD) a = (T)(2.0 * rl.scale) * (rl.g_dev ? *static_cast<const T*>(rl.g_dev) : T(1));
+    if constexpr (GRAD) {
+        if constexpr (sizeof...(X) >= 2) a = loss_factor<T>(LossInj{2.0 * rl.scale, rl.g_dev, 0}, (long)blockIdx.y);
+        else a = (T)(2.0 * rl.scale) * (rl.g_dev ? *static_cast<const T*>(rl.g_dev) : T(1));
+    }
     double acc = 0.0;
     for (int f = (int)fb.by; f < nframes && live; f += (int)fg.gy) {
         const T* h = traj + (long)f * frame;
@@ -1120,13 +1136,24 @@ pi_residual_sq_kernel(const T* __restrict__ traj, T* __restrict__ G, double* __r
 // FULL: `out` has nout >= nframes + 1 frames and is written completely -- frame f < nframes as above minus G_{f-1} / dt
 // (the pointwise part of step f - 1), frame nframes = -G_{nframes-1} / dt, later frames zero: dL/dtraj of a loss over
 // R_0 .. R_{nframes-1} in ONE launch (was: zero-fill, this kernel, a full-trajectory division and a subtraction).
-template <typename T, int NDIM, int VEC, bool FULL = false>
+template <typename T, int NDIM, int VEC, bool FULL = false, typename... X>
 __global__ void __launch_bounds__(256)
 pi_residual_adj_kernel(const T* __restrict__ traj, const T* __restrict__ G, T* __restrict__ out,
-                       const T* __restrict__ Q, Geom g, FrameGrid fg, int nframes = 0)
+                       const T* __restrict__ Q, Geom g, FrameGrid fg, int nframes = 0, X... x)
 {
     const FrameBlock fb = frame_block(fg);
     if (!fb.live) return;
+    if constexpr (sizeof...(X) >= 1) {
+        const long sbase = (long)blockIdx.y * flavour_arg<0>(x...);      // sample blockIdx.y
+        traj += sbase; G += sbase; out += sbase;
+    }
+    // elements between two frames -- evaluated where the kernel without a pack evaluated 2 * g.ss: hoisted to the kernel's
+    // entry, the FULL kernels without a pack compiled to other code than before (3-4 instructions, 2 SGPRs)
+    auto frame_elems = [&]() -> long {
+        if constexpr (sizeof...(X) >= 1) return (long)gridDim.y * flavour_arg<0>(x...);
+        else return 2 * g.ss;
+    };
+    if constexpr (sizeof...(X) == 2) Q += (long)blockIdx.y * flavour_arg<1>(x...);    // its equation
     if constexpr (FULL) {
         const int f = (int)fb.by;
         if (f >= nframes) {
@@ -1136,7 +1163,7 @@ pi_residual_adj_kernel(const T* __restrict__ traj, const T* __restrict__ G, T* _
             int j0, j1, y0;
             long eF;
             chunk_coords<NDIM>(g, cidF, cprF, VEC, j0, j1, y0, eF);
-            const long frameF = 2 * g.ss;
+            const long frameF = frame_elems();
             const T dtF = Q[P_DT];
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
@@ -1161,7 +1188,7 @@ pi_residual_adj_kernel(const T* __restrict__ traj, const T* __restrict__ G, T* _
     int i0, i1, x0;
     long e;
     chunk_coords<NDIM>(g, cid, cpr, VEC, i0, i1, x0, e);
-    const long frame = 2 * g.ss;
+    const long frame = frame_elems();
     const T* h = traj + (long)fb.by * frame;
     const T* Gf = G + (long)fb.by * frame;
     const Pack<T, VEC> u = ld<T, VEC>(h + e), v = ld<T, VEC>(h + g.ss + e);

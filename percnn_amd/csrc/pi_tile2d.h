@@ -630,12 +630,20 @@ pi_fwd2d_tile_kernel(T* __restrict__ frames /* frame t (of sample 0); t+1..t+K a
 // bit -- and the strip of frame f + 1 it requested with the window.  Workgroup (x, y) walks frames y, y + gridDim.y, ...
 // The generic kernel spends, per 512^2 frame, 0.6 us issuing 316 unpacked VALU instructions per wave, 0.5 us on 16 vector-L1
 // requests per chunk and 0.26 us on HBM, one after the other (1.38 us); here: 5 requests per lane and the packed strip body.
+// X... = `long sample, int rows` (grid (tiles, gy, B)): trajectory [F][B][2][*S], frame_stride = B * sample; the workgroups of
+// grid plane b run the body on sample b and write rows [b * rows, (b + 1) * rows) of the partial sums.
+// X... = `long sample, int rows, int np`: + the equation block of sample b, Q + b * np (wave-uniform: scalar loads as before).
 // ------------------------------------------------------------------------------------------------
-template <typename T, int BX, int BY, int NT>
+template <typename T, int BX, int BY, int NT, typename... X>
 __global__ void __launch_bounds__(NT)
 pi_res2d_tile_kernel(const T* __restrict__ traj, double* __restrict__ partials, const T* __restrict__ Q, TileGeom g,
-                     long frame_stride, int nframes, int weighted)
+                     long frame_stride, int nframes, int weighted, X... x)
 {
+    if constexpr (sizeof...(X) >= 2) {
+        traj += (long)blockIdx.z * flavour_arg<0>(x...);                 // sample blockIdx.z
+        partials += (long)blockIdx.z * flavour_arg<1>(x...);
+    }
+    if constexpr (sizeof...(X) == 3) Q += (long)blockIdx.z * flavour_arg<2>(x...);    // its equation
     // window: BY + 4 rows (2 above, 2 below) x BX + 8 columns -- FOUR halo columns per side although the star needs two, so
     // that every 16-byte piece of the window starts at a multiple of 4 columns and never straddles the periodic wrap (the
     // K-step kernels' windows start at tx0 - 2K with K even; a window starting at tx0 - 2 would)

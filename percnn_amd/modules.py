@@ -989,6 +989,21 @@ class RCNN(nn.Module):
         self.last_trajectory = traj
         return loss
 
+    def sample_physics_losses(self, Q: torch.Tensor, reference_weighting: bool = True) -> torch.Tensor:
+        """[B]: the physics-residual loss (``physics.physics_loss``, the reference's ``loss_gen``) of every sample of this
+        rollout on its own, as ONE autograd node after ``trajectory()`` (``physics.physics_loss_batched``).  ``Q`` [36]: the
+        equation every sample is scored against; ``Q`` [B, 36]: sample b against its own (an (f, k) study: row b =
+        ``physics.gray_scott_block(member_b, ...)``).  For a batched initial state, for a ``CellEnsemble`` (the gradient of
+        loss b reaches member b's parameters) and for one trajectory ([1]).  The gradient reaches the parameters through the
+        batched / ensemble rollout backward on the materialised dL/dtraj.  The detached trajectory is kept in
+        ``self.last_trajectory``."""
+        from . import physics
+        traj = self.trajectory()
+        if traj.dim() == self.init_state.dim():             # one trajectory [step+1, 2, *S]
+            traj = traj.unsqueeze(1)
+        self.last_trajectory = traj.detach()
+        return physics.physics_loss_batched(traj, Q, reference_weighting)
+
     def ic_loss(self, mode: Optional[str] = None) -> torch.Tensor:
         """``get_ic_loss(model)`` of the reference scripts (train_2drd.py:331-338, train_3drd.py:325-332): MSE between the IC
         generator's output and the low-resolution measurement interpolated to ITS output size (bicubic in 2D, trilinear in

@@ -129,6 +129,49 @@ class PhysicsLossFunction(torch.autograd.Function):
         return g, None, None, None
 
 
+class BatchedPhysicsLossFunction(torch.autograd.Function):
+    """output [F+2, B, 2, *S] (frame-major, as ``pi_rollout_batched`` / ``pi_rollout_ensemble`` return it) -> loss [B], the
+    residual loss of every sample on its own, as ONE node: the sample flavours of ``PhysicsLossFunction``'s launches
+    (``percnn_pi_{batch,ensemble}_residual_sqloss_*``) -- one reducing pass and one finishing launch forward, two launches
+    backward that write dL/d output completely, whatever B.  Q [36]: one equation; Q [B, 36]: sample b against row b."""
+
+    @staticmethod
+    def forward(ctx, output, Q, nres, weighted):
+        F_pi._require(output, "output"); F_pi._require(Q, "pde block", output.dtype)
+        B, shape = output.shape[1], output.shape[3:]
+        kind = "ensemble" if Q.dim() == 2 else "batch"
+        L = _lib.lib()
+        # the partial rows this call writes per sample (0: it declines the grid, which the call itself reports)
+        rows = ctypes.c_int(0)
+        _lib.check(min(0, L.percnn_pi_debug_residual_sqloss_accepts(len(shape), _lib.shape_arg(shape), output.element_size(), B,
+                                                                    int(nres), int(output.data_ptr() % 16 == 0),
+                                                                    ctypes.byref(rows))), "residual_sqloss plan")
+        ws = torch.empty(max(1, B * rows.value), dtype=torch.float64, device=output.device)
+        loss = torch.empty((B,), dtype=output.dtype, device=output.device)
+        f = getattr(L, f"percnn_pi_{kind}_residual_sqloss_" + F_pi._SUF[output.dtype])
+        with torch.cuda.device(output.device):
+            _lib.check(f(output.data_ptr(), Q.data_ptr(), len(shape), _lib.shape_arg(shape), B, int(nres), int(bool(weighted)),
+                         loss.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                         ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), kind + "_residual_sqloss")
+        ctx.save_for_backward(output, Q)
+        ctx.nres, ctx.weighted, ctx.kind = int(nres), bool(weighted), kind
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        output, Q = ctx.saved_tensors
+        gl = gl.to(output.dtype).contiguous()
+        B, shape = output.shape[1], output.shape[3:]
+        scratch = torch.empty((ctx.nres,) + tuple(output.shape[1:]), dtype=output.dtype, device=output.device)
+        g = torch.empty_like(output)
+        f = getattr(_lib.lib(), f"percnn_pi_{ctx.kind}_residual_sqloss_bwd_" + F_pi._SUF[output.dtype])
+        with torch.cuda.device(output.device):
+            _lib.check(f(output.data_ptr(), gl.data_ptr(), Q.data_ptr(), len(shape), _lib.shape_arg(shape), B, ctx.nres,
+                         output.shape[0], int(ctx.weighted), scratch.data_ptr(), g.data_ptr(),
+                         ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), ctx.kind + "_residual_sqloss_bwd")
+        return g, None, None, None
+
+
 def physics_residual(traj: torch.Tensor, Q: torch.Tensor) -> torch.Tensor:
     return PhysicsResidualFunction.apply(traj.contiguous(), Q)
 
@@ -160,3 +203,32 @@ def physics_loss(output: torch.Tensor, Q: torch.Tensor, reference_weighting: boo
         denom = R.shape[0] * float(torch.tensor([n + 1 for n in R.shape[2:]]).prod())
         return sq[:, 0].sum() / denom + sq[:, 1].sum() / denom
     return sq[:, 0].mean() + sq[:, 1].mean()
+
+
+def physics_loss_batched(output: torch.Tensor, Q: torch.Tensor, reference_weighting: bool = True,
+                         fused: bool = True) -> torch.Tensor:
+    """[B]: ``physics_loss(output[:, b], Q or Q[b])`` of every sample of a frame-major trajectory ``output`` [F+2, B, 2, *S]
+    (what ``RCNN.trajectory()`` returns for a batched initial state or a ``CellEnsemble``), as ONE autograd node
+    (``BatchedPhysicsLossFunction``): four launches per training iteration whatever B, and no ``output[:, b].contiguous()``
+    copies.  ``Q`` [36]: one equation for every sample; ``Q`` [B, 36]: sample b against its own equation (an (f, k) study
+    scored against each member's PDE; ``dt``, the diffusivities and the taps may differ between rows).  The block is a
+    constant, as for ``physics_loss``.  ``fused=False``, a grid the fused pass turns down, or a size outside
+    ``physics_loss``'s guard: the unbatched ``physics_loss`` of every sample, stacked (tests compare the two).  A batched 3D
+    call runs the generic pass -- the brick loss pass of ``physics_loss`` has no batched form yet."""
+    if output.dim() not in (5, 6) or output.shape[2] != 2:
+        raise ValueError(f"physics_loss_batched: output must be [F+2, B, 2, *S] with a 2D or 3D grid, got {tuple(output.shape)}")
+    if output.shape[0] < 3:
+        raise ValueError("physics_loss_batched: the residual of frame f needs frame f + 1 and the last frame is dropped: "
+                         f"at least 3 frames, got {output.shape[0]}")
+    B = output.shape[1]
+    if tuple(Q.shape) not in ((F_pi.NPOLY,), (B, F_pi.NPOLY)):
+        raise ValueError(f"physics_loss_batched: Q must be [{F_pi.NPOLY}] or [{B}, {F_pi.NPOLY}], got {tuple(Q.shape)}")
+    if not output.is_cuda:
+        raise RuntimeError(f"percnn_amd: output must live on a HIP device (got {output.device}); there is no CPU path")
+    if fused and output.shape[0] <= 65535 and B <= 65535 and output[0, 0, 0].numel() <= (1 << 24):
+        try:
+            return BatchedPhysicsLossFunction.apply(output.contiguous(), Q.contiguous(), output.shape[0] - 2, reference_weighting)
+        except _lib.GridTooLargeError:
+            pass
+    return torch.stack([physics_loss(output[:, b].contiguous(), Q if Q.dim() == 1 else Q[b].contiguous(), reference_weighting, fused)
+                        for b in range(B)])
