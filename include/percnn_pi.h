@@ -412,6 +412,11 @@ int percnn_pi_debug_blockmap(int ndim, const int64_t* shape, int elem_size, cons
  * 1 2D tile kernels, 2 3D plane streaming, 3 3D brick kernels, 4 advective block.  (The lanes are those of the launch-per-group
  * tile kernels; the resident launches of the 8- and 16-row regimes run twice as many on half-strips: fwd_small_half, adj_small_half.) */
 int percnn_pi_debug_plan(int hc, int ndim, const int64_t* shape, int elem_size, const char* options, int* out);
+/* Host-only: the kernel family of the launch-per-step part of a batched / ensemble call over `batch` samples (every step of a 3D
+ * call; what a 2D call runs beside its tile groups), for 16-byte-aligned buffers and the plain injection form.
+ * out[4] = {forward family, adjoint family, planes per pass forward, adjoint}; families as percnn_pi_debug_plan.  batch == 1 is
+ * the unbatched path and reports percnn_pi_debug_plan's families. */
+int percnn_pi_debug_batch_plan(int hc, int ndim, const int64_t* shape, int elem_size, int batch, const char* options, int* out);
 
 size_t percnn_pi_peer_box_bytes(size_t slot_bytes);                 /* size of a mailbox allocation */
 int percnn_pi_peer_box_alloc(void** box, size_t slot_bytes);        /* fine-grained device memory on the current device, zeroed */
@@ -613,8 +618,12 @@ int percnn_pi_traj_sqerr_f64(const double *traj, const double *target, const uns
  * param_grad equals the sum of the per-sample gradients to reduction round-off and is bit-identical from run to run.
  * Validation before any launch: batch < 1 (or > 65535), the advective block (hc == -1) with batch > 1 or bad options ->
  * PERCNN_PI_EINVAL; a workspace below *_workspace_bytes -> PERCNN_PI_EWORKSPACE; PERCNN_PI_ETOOLARGE is judged per sample.
- * batch == 1 is the unbatched entry point (same kernels, same workspace size).  The resident ("tile_persist", "fwd_persist",
- * "res3d"), 3D brick and plane-streaming kernels have no batched flavour and are not dispatched for batch > 1. */
+ * batch == 1 is the unbatched entry point (same kernels, same workspace size).  3D steps of a batch run on the brick kernels'
+ * sample flavours (256-lane bricks of one or two planes) where a sample is eligible for them and every base is 16-byte aligned:
+ * "brick3d" 0 = never, 2 = wherever eligible, 1 (default) = where they measured faster (pre-contracted blocks of 48^3 .. 128^3
+ * points per sample in launches of at least 8 x 48^3 points); "brick_nt" and "brick_wide" do not apply to a batch
+ * (percnn_pi_debug_batch_plan reports the choice).  The resident ("tile_persist", "fwd_persist", "res3d") and plane-streaming
+ * kernels have no batched flavour and are not dispatched for batch > 1. */
 size_t percnn_pi_batch_bwd_workspace_bytes(int hc, int ndim, const int64_t *shape, int batch, int elem_size);
 size_t percnn_pi_batch_rollout_bwd_workspace_bytes(int hc, int ndim, const int64_t *shape, int batch, int T, int elem_size);
 int percnn_pi_batch_step_fwd_f32(const float *h, float *out, const float *params, int hc, int ndim, const int64_t *shape,
@@ -652,7 +661,8 @@ int percnn_pi_batch_rollout_bwd_f64(const double *traj, const double *g_traj, co
  * Validation before any launch: batch < 1 (or > 65535), the advective block (hc == -1), NULL pointers, an output that aliases
  * an input, or bad options -> PERCNN_PI_EINVAL; a workspace below *_workspace_bytes -> PERCNN_PI_EWORKSPACE.  batch == 1 is the
  * unbatched entry point on params[0] (same kernels, same workspace size).  The workspace queries return 0 for invalid problems
- * (the advective block included).  Resident, 3D brick and plane-streaming kernels are not dispatched for batch > 1. */
+ * (the advective block included).  3D steps take the brick kernels' ensemble flavour by the rule of the batched entry points;
+ * resident and plane-streaming kernels are not dispatched for batch > 1. */
 size_t percnn_pi_ensemble_bwd_workspace_bytes(int hc, int ndim, const int64_t *shape, int batch, int elem_size);
 size_t percnn_pi_ensemble_rollout_bwd_workspace_bytes(int hc, int ndim, const int64_t *shape, int batch, int T, int elem_size);
 int percnn_pi_ensemble_step_fwd_f32(const float *h, float *out, const float *params, int hc, int ndim, const int64_t *shape,

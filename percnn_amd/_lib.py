@@ -57,7 +57,7 @@ EXPORTS = [
     "percnn_pi_pack_fwd_f32", "percnn_pi_pack_fwd_f64", "percnn_pi_pack_bwd_f32", "percnn_pi_pack_bwd_f64",
     "percnn_pi_pack_fwd_guard_f32", "percnn_pi_pack_fwd_guard_f64", "percnn_pi_host_words_alloc", "percnn_pi_host_words_free",
     "percnn_pi_debug_hog",
-    "percnn_pi_debug_blockmap", "percnn_pi_debug_plan", "percnn_pi_residual_sqloss_workspace_bytes",
+    "percnn_pi_debug_blockmap", "percnn_pi_debug_plan", "percnn_pi_debug_batch_plan", "percnn_pi_residual_sqloss_workspace_bytes",
     "percnn_pi_residual_sqloss_f32", "percnn_pi_residual_sqloss_f64", "percnn_pi_residual_sqloss_bwd_f32",
     "percnn_pi_residual_sqloss_bwd_f64",
 ] + [f"percnn_pi_{op}_{suf}" for suf in ("f32", "f64")
@@ -191,6 +191,8 @@ def lib() -> ctypes.CDLL:
     L.percnn_pi_debug_blockmap.argtypes = [ci, i64p, ci, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
     L.percnn_pi_debug_plan.restype = ci
     L.percnn_pi_debug_plan.argtypes = [ci, ci, i64p, ci, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
+    L.percnn_pi_debug_batch_plan.restype = ci
+    L.percnn_pi_debug_batch_plan.argtypes = [ci, ci, i64p, ci, ci, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
     cd = ctypes.c_double
     for suf in ("f32", "f64"):
         f = getattr(L, f"percnn_pi_pack_fwd_{suf}")
@@ -418,6 +420,14 @@ def rollout_plan(hc: int, shape, elem_size: int, options=None) -> dict:
             "brick_lanes": out[7], "tile": (out[8], out[9], out[10]) if out[10] else None,
             "tile_fwd": (out[11], out[12], out[13]) if out[13] else None, "bwd_persistent": bool(out[14] & 1),
             "fwd_persistent": bool(out[14] & 2)}
+
+
+def batch_plan(hc: int, shape, elem_size: int, batch: int, options=None) -> dict:
+    """Kernel families of the launch-per-step part of a batched / ensemble call (``percnn_pi_debug_batch_plan``)."""
+    out = (ctypes.c_int * 4)()
+    check(lib().percnn_pi_debug_batch_plan(int(hc), len(shape), shape_arg(shape), int(elem_size), int(batch), options_arg(options),
+                                           out), "debug_batch_plan")
+    return {"fwd": FAMILIES[out[0]], "bwd": FAMILIES[out[1]], "fwd_planes_per_pass": out[2], "bwd_planes_per_pass": out[3]}
 
 
 def set_option(key: str, value: int) -> None:

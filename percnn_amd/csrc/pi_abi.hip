@@ -826,11 +826,10 @@ hipError_t brick_fwd(int rz, const T* h, T* out, const T* P, const Problem& p, h
 // grid of what is resident at once (4 workgroups per CU with one-plane bricks, 2 with more) walks the bricks instead, every
 // workgroup the same number of them where the count allows.  Probe (128^3, us per adjoint step): 2048 one-brick workgroups
 // 17.4, 1024 two-brick ones 17.2, 768 (uneven) 17.8; two-plane bricks 1024 / 512 workgroups 18.1 / 17.0.
-unsigned brick_bwd_grid(const Problem& p, int vec, int rz)
+// (brick_bwd_cap: the workgroups resident at once, CUs x workgroups per CU, at most MAX_BWD_BLOCKS)
+unsigned brick_bwd_cap(const Problem& p, int vec, int rz, int nt)
 {
     const int elem = 16 / vec;                              // bricks run on 16-byte lanes: 4 = float32, 8 = float64
-    const int nt = rz <= 2 ? brick_nt_for(p, vec) : 256;
-    const pi::BrickGeom b = make_brick_geom(p, vec, rz, nt);
     static int cu_count[16] = {};                           // per device, asked once (benign race: same value)
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16) {
@@ -844,8 +843,15 @@ unsigned brick_bwd_grid(const Problem& p, int vec, int rz)
     int per_cu = p.opt.brick_wgs ? p.opt.brick_wgs
                                  : ((rz == 1 && p.hc == 0 && p.loss.mode != 2 && elem == 4) ? 4 : (rz == 1 ? 3 : 2));
     if (nt == 512 && !p.opt.brick_wgs) per_cu = (per_cu + 1) / 2;      // the same waves per CU in half as many workgroups
-    unsigned cap = (unsigned)(cus * per_cu);
-    if (cap > (unsigned)MAX_BWD_BLOCKS) cap = MAX_BWD_BLOCKS;
+    const unsigned cap = (unsigned)(cus * per_cu);
+    return cap > (unsigned)MAX_BWD_BLOCKS ? (unsigned)MAX_BWD_BLOCKS : cap;
+}
+
+unsigned brick_bwd_grid(const Problem& p, int vec, int rz)
+{
+    const int nt = rz <= 2 ? brick_nt_for(p, vec) : 256;
+    const pi::BrickGeom b = make_brick_geom(p, vec, rz, nt);
+    unsigned cap = brick_bwd_cap(p, vec, rz, nt);
     if (b.nblk <= cap) return b.nblk;
     // ... while that is at most two bricks each: a workgroup takes its bricks one after the other, nothing of the next one is
     // in flight while it computes (200^3, one-plane bricks: 4000 two-brick workgroups 59.3 us per step, 1000 eight-brick ones 69.6)
@@ -2596,7 +2602,10 @@ int rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* mask, 
 // The batch is the y dimension of the launch-per-group kernels (the `long sample` flavours of pi_fwd2d_tile_kernel,
 // pi_adj2d_tile_kernel, pi_fwd_kernel, pi_bwd_kernel): every workgroup runs the kernel's one body on one sample, so every state field
 // of sample b is the unbatched result of that sample alone, bit for bit.  Partial rows: one per (sample, workgroup), reduced in
-// one fixed order.  The resident, brick and plane-streaming kernels have no batched flavour and are never dispatched here.
+// one fixed order.  3D steps of rows of up to 64 chunks run on the sample flavours of the brick kernels (pi_brick3d.h; 256-lane
+// bricks of one or two planes) where batch_brick_rz says so.  The resident and plane-streaming kernels, the 512-lane and
+// four-plane bricks, the brick residual pass and the sparse-observation form on bricks have no batched flavour and are never
+// dispatched here.
 constexpr int MAX_BATCH = 65535;                            // grid y
 
 int batch_problem(int hc, int ndim, const int64_t* shape, int batch, Problem& p, const char* options, bool launches = true)
@@ -2766,10 +2775,138 @@ hipError_t launch_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* par
     return e;
 }
 
+// brick3d = 1: which batches take the bricks by default (brick3d = 2: every eligible one).
+// Measured on one MI355X (profiles/batch_brick_throughput.json, tools/batch_brick_throughput.py: pi_rollout_batched + backward,
+// float32, k sample-steps/s, brick3d=0 -> brick3d=2, the routes alternating in one process, best of two 1 s regions; brick3d=0
+// against itself: within 0.12 % on every row):
+//   pre-contracted blocks   48^3 x 300, B = 8: 422.7 -> 443.2 (+4.9 %); B = 64: 724.2 -> 787.8 (+8.8 %); 128^3 x 32, B = 4: 40.06 -> 46.63 (+16.4 %)
+//   factored blocks, Hc = 2 48^3 x 300, B = 8: 372.3 -> 329.9 (-11.4 %); B = 64: 568.1 -> 512.7 (-9.8 %); 128^3 x 32, B = 4: 30.64 -> 29.72 (-3.0 %)
+// -> pre-contracted blocks of 48^3 .. 128^3 points per sample (110592 .. 2097152) in launches of at least 8 x 48^3 points, the
+// smallest batch that was measured; factored blocks lose everywhere and stay direct, as does every class without a figure
+// (smaller or larger samples, smaller launches): brick3d = 2 reaches the bricks there.  The class is (block kind, points per
+// sample, points per launch); float64 batches follow the float32 figures and have none of their own.
+bool batch_brick_default(const Problem& p, int batch)
+{
+    constexpr int64_t N_MIN = 48 * 48 * 48, N_MAX = 128 * 128 * 128;
+    return p.hc == 0 && p.n >= N_MIN && p.n <= N_MAX && (int64_t)batch * p.n >= 8 * N_MIN;
+}
+
+// ---- batch on bricks: the sample flavours of pi_fwd3d_brick_kernel / pi_adj3d_brick_kernel, grid (bricks of one sample, B) ----
+// Planes per brick of a batched / ensemble step launch, 0 = the direct kernels.  Per sample the rule is brick_rz_for's (256-lane
+// bricks: rows of up to 64 chunks); on top of it the lanes must be the 16-byte ones (`vec` is pick_vec's answer over the call's
+// pointers), the sample stride must keep every sample's base 16-byte aligned, the sparse-observation form (`obs`) and factored
+// blocks that need all gradients in the launch (`wgrad`, the rule of step_bwd) stay direct, and four-plane bricks have no sample
+// flavour.  brick_nt and brick_wide do not apply.  One function for the launchers, ens_rows_for and percnn_pi_debug_batch_plan.
+template <typename T>
+int batch_brick_rz(const Problem& p, int vec, int batch, bool adjoint, bool wgrad, bool obs)
+{
+    if (obs || batch < 2 || (adjoint && wgrad && p.hc != 0)) return 0;
+    if (((size_t)2 * p.n * sizeof(T)) % 16) return 0;
+    const int rz = brick_rz_for<T>(p, vec, adjoint, /*wide=*/false);
+    if (rz < 1 || rz > 2) return 0;
+    if (p.opt.brick3d == 1 && !batch_brick_default(p, batch)) return 0;
+    return rz;
+}
+
+// workgroups per sample of the adjoint brick launch: brick_bwd_grid's rule with its cap spread over the batch -- max(1, cap / B)
+// per sample, never more than a sample has bricks, every workgroup about the same number of them; the whole launch plays the
+// part of the one sample there (more than two bricks per workgroup: the partial rows bound the grid, not the CUs)
+unsigned batch_brick_bwd_grid(const Problem& p, int vec, int rz, int batch)
+{
+    const pi::BrickGeom b = make_brick_geom(p, vec, rz, pi::BRICK_NT);
+    unsigned cap = brick_bwd_cap(p, vec, rz, pi::BRICK_NT);
+    if (!p.opt.brick_wgs && (uint64_t)b.nblk * (unsigned)batch > 2 * (uint64_t)cap) cap = MAX_BWD_BLOCKS;
+    const unsigned per = std::max(1u, cap / (unsigned)batch);
+    if (b.nblk <= per) return b.nblk;
+    const unsigned k = (b.nblk + per - 1) / per;            // bricks per workgroup
+    return (b.nblk + k - 1) / k;
+}
+
+template <typename T, int HC, int RZ>
+hipError_t launch_brick_fwd_b(const T* h, T* out, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows = -1)
+{
+    constexpr int VEC = 16 / (int)sizeof(T);
+    const pi::BrickGeom b = make_brick_geom(p, VEC, RZ, pi::BRICK_NT, false);
+    if (b.n0 <= 0) return hipSuccess;
+    const size_t lds = (size_t)2 * RZ * pi::BRICK_WB + (size_t)p.opt.lds_pad;
+    auto go = [&](auto* k, auto... tail) {
+        if (hipError_t e = allow_lds(k, lds)) return e;
+        hipLaunchKernelGGL(k, dim3(b.nblk, (unsigned)batch), dim3(pi::BRICK_NT), lds, st, h, out, P, b, p.hc, pi::PeerPutFused{},
+                           (long)(2 * p.n), tail...);
+        return hipGetLastError();
+    };
+    return ens_rows >= 0 ? go(pi::pi_fwd3d_brick_kernel<T, HC, RZ, pi::BRICK_NT, long, int>, pi::nparams(p.hc))
+                         : go(pi::pi_fwd3d_brick_kernel<T, HC, RZ, pi::BRICK_NT, long>);
+}
+
+template <typename T>
+hipError_t brick_fwd_b(int rz, const T* h, T* out, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows)
+{
+#define CALL_BFB(HC, RZ) launch_brick_fwd_b<T, HC, RZ>(h, out, P, p, batch, st, ens_rows)
+    switch (p.hc) {
+        case 0:  return rz == 2 ? CALL_BFB(pi::POLY, 2) : CALL_BFB(pi::POLY, 1);
+        case 2:  return CALL_BFB(2, 1);
+        case 4:  return CALL_BFB(4, 1);
+        case 8:  return CALL_BFB(8, 1);
+        default: return CALL_BFB(0, 1);
+    }
+#undef CALL_BFB
+}
+
+template <typename T, int HC, int RZ, bool MOM>
+hipError_t launch_brick_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* partials, const T* P, const Problem& p, int batch,
+                              hipStream_t st, unsigned* rows_out, int ens_rows = -1)
+{
+    constexpr int VEC = 16 / (int)sizeof(T), NT = pi::BRICK_NT;
+    const pi::BrickGeom b = make_brick_geom(p, VEC, RZ, NT, true);
+    if (b.n0 <= 0) return hipSuccess;
+    unsigned grid = batch_brick_bwd_grid(p, VEC, RZ, batch);
+    if (ens_rows >= 0 && grid > (unsigned)ens_rows) grid = (unsigned)ens_rows;   // (ens_rows_for counts this launch: no-op)
+    if (!grid) return (hipError_t)PERCNN_PI_ETOOLARGE;
+    const size_t head = (size_t)(NT / pi::WAVE) * 2 * sizeof(double);
+    const size_t windows = (size_t)2 * RZ * pi::BRICK_WB, scratch = MOM ? (size_t)(32 + 20 * (NT + 8)) * sizeof(T) : 0;
+    const size_t lds = head + (windows > scratch ? windows : scratch) + (size_t)p.opt.lds_pad;
+    auto go = [&](auto* k, auto... tail) {
+        if (hipError_t e = allow_lds(k, lds)) return e;
+        hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(NT), lds, st, h, G, inj, Gp, partials, P, b, p.hc, pi::NoPut{},
+                           (long)(2 * p.n), tail...);
+        return hipGetLastError();
+    };
+    auto flavour = [&](auto loss) {
+        constexpr int LOSS = decltype(loss)::value;
+        return ens_rows >= 0 ? go(pi::pi_adj3d_brick_kernel<T, HC, RZ, MOM, LOSS, NT, false, long, int>, ens_rows)
+                             : go(pi::pi_adj3d_brick_kernel<T, HC, RZ, MOM, LOSS, NT, false, long>);
+    };
+    const hipError_t e = p.loss.mode == 1 ? flavour(std::integral_constant<int, 1>{})
+                       : p.loss.mode == 2 ? flavour(std::integral_constant<int, 2>{})
+                                          : flavour(std::integral_constant<int, 0>{});
+    if (e == hipSuccess && rows_out) *rows_out = grid * (unsigned)batch;
+    return e;
+}
+
+template <typename T>
+hipError_t brick_bwd_b(int rz, bool mom, const T* h, const T* G, const T* inj, T* Gp, double* partials, const T* P, const Problem& p,
+                       int batch, hipStream_t st, unsigned* rows_out, int ens_rows)
+{
+#define CALL_BBB(HC, RZ, MOM) launch_brick_bwd_b<T, HC, RZ, MOM>(h, G, inj, Gp, partials, P, p, batch, st, rows_out, ens_rows)
+    if (p.hc == 0) {
+        if (mom) return rz == 2 ? CALL_BBB(pi::POLY, 2, true) : CALL_BBB(pi::POLY, 1, true);
+        return rz == 2 ? CALL_BBB(pi::POLY, 2, false) : CALL_BBB(pi::POLY, 1, false);
+    }
+    switch (p.hc) {
+        case 2:  return CALL_BBB(2, 1, false);
+        case 4:  return CALL_BBB(4, 1, false);
+        case 8:  return CALL_BBB(8, 1, false);
+        default: return CALL_BBB(0, 1, false);
+    }
+#undef CALL_BBB
+}
+
 template <typename T>
 hipError_t step_fwd_b(const T* h, T* out, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows = -1)
 {
     const int vec = pick_vec<T>(p, {h, out});
+    if (const int brz = batch_brick_rz<T>(p, vec, batch, false, false, false)) return brick_fwd_b<T>(brz, h, out, P, p, batch, st, ens_rows);
 #define CALL_FWDB(NDIM, HC, VEC) launch_fwd_b<T, NDIM, HC, VEC>(h, out, P, p, batch, st, ens_rows)
     PI_DISPATCH(CALL_FWDB);
 #undef CALL_FWDB
@@ -2781,6 +2918,8 @@ hipError_t step_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* parti
 {
     // (the compact target of the sparse-observation flavours is read element-wise: its alignment does not pick the lanes)
     const int vec = pick_vec<T>(p, {h, G, ol ? nullptr : inj, Gp});
+    if (const int brz = batch_brick_rz<T>(p, vec, batch, true, WGRAD, ol != nullptr))
+        return brick_bwd_b<T>(brz, WGRAD, h, G, inj, Gp, partials, P, p, batch, st, rows_out, ens_rows);
 #define CALL_BWDB(NDIM, HC, VEC) launch_bwd_b<T, NDIM, HC, VEC, WGRAD>(h, G, inj, Gp, partials, P, p, batch, st, rows_out, ens_rows, ol)
     PI_DISPATCH(CALL_BWDB);
 #undef CALL_BWDB
@@ -3061,7 +3200,8 @@ long ens_wgrad_blocks(const Problem& p, int batch, int t_top, int vec)
 }
 
 // partial rows per sample: the most that any launch of the call writes for one sample -- the tile sweep one per tile, the direct
-// sweep its grid (either lane width), the gradient pass two per workgroup (t_top = 0: no gradient pass).  Each of these is at
+// sweep its grid (either lane width; on bricks: batch_brick_bwd_grid), the gradient pass two per workgroup (t_top = 0: no gradient
+// pass).  Each of these is at
 // most MAX_BWD_BLOCKS, so B rows of the unbatched workspace's partials hold them.
 template <typename T>
 int ens_rows_for(const Problem& p, int batch, bool tile, int t_top)
@@ -3071,6 +3211,8 @@ int ens_rows_for(const Problem& p, int batch, bool tile, int t_top)
         const long d = bwd_grid(p, v, sizeof(T), 1);
         if (d > r) r = d;
         if (t_top > 0 && 2 * ens_wgrad_blocks(p, batch, t_top, v) > r) r = 2 * ens_wgrad_blocks(p, batch, t_top, v);
+        if (const int brz = batch_brick_rz<T>(p, v, batch, true, false, false))
+            if (const long d2 = batch_brick_bwd_grid(p, v, brz, batch); d2 > r) r = d2;
     }
     return (int)(r < MAX_BWD_BLOCKS ? r : MAX_BWD_BLOCKS);
 }
@@ -4010,6 +4152,28 @@ int debug_plan_impl(int hc, int ndim, const int64_t* shape, const char* options,
     return 0;
 }
 
+// out = {forward family, adjoint family, planes per pass forward, adjoint} of the launch-per-step part of a batched / ensemble
+// call (step_fwd_b / step_bwd_b: what is left of a 2D call beside its tile groups, every step of a 3D one), for 16-byte-aligned
+// buffers and the plain injection form; families as debug_plan_impl.  batch == 1 is the unbatched path: its plan.
+template <typename T>
+int debug_batch_plan_impl(int hc, int ndim, const int64_t* shape, int batch, const char* options, int* out)
+{
+    if (batch == 1) {
+        int o[32] = {};
+        if (int rc = debug_plan_impl<T>(hc, ndim, shape, options, o)) return rc;
+        out[0] = o[0]; out[1] = o[1]; out[2] = o[5]; out[3] = o[6];
+        return 0;
+    }
+    Problem p;
+    if (int rc = batch_problem(hc, ndim, shape, batch, p, options, false)) return rc;
+    const int vec = pick_vec<T>(p, {});
+    const bool fuse = !p.opt.skip_wgrad && (p.opt.fuse_wgrad == 1 || (p.opt.fuse_wgrad == 2 && hc == 0));   // the direct sweep's rule
+    const int fz = batch_brick_rz<T>(p, vec, batch, false, false, false), az = batch_brick_rz<T>(p, vec, batch, true, fuse, false);
+    out[0] = fz ? 3 : 0; out[1] = az ? 3 : 0;
+    out[2] = fz ? fz : 1; out[3] = az ? az : 1;              // (the batched direct kernels take one plane per pass)
+    return 0;
+}
+
 }  // namespace
 
 // ---- exported symbols ---------------------------------------------------------------------------
@@ -4123,6 +4287,13 @@ int percnn_pi_debug_blockmap(int ndim, const int64_t* shape, int elem_size, cons
                       p.opt.lane_x)) return PERCNN_PI_EINVAL;
     out[0] = g.lxs; out[1] = g.nxb; out[2] = g.nrg; out[3] = (int)g.nblk; out[4] = rz; out[5] = block;
     return 0;
+}
+
+int percnn_pi_debug_batch_plan(int hc, int ndim, const int64_t* shape, int elem_size, int batch, const char* options, int* out)
+{
+    if (!out || (elem_size != 4 && elem_size != 8)) return PERCNN_PI_EINVAL;
+    return elem_size == 4 ? debug_batch_plan_impl<float>(hc, ndim, shape, batch, options, out)
+                          : debug_batch_plan_impl<double>(hc, ndim, shape, batch, options, out);
 }
 
 int percnn_pi_debug_plan(int hc, int ndim, const int64_t* shape, int elem_size, const char* options, int* out)

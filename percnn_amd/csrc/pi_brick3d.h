@@ -189,24 +189,41 @@ __device__ __forceinline__ Geom brick_as_geom(const BrickGeom& b)
 // ---------------------------------------------------------------------------------------------
 // forward: out = h + dt * (coef * Lap(h) + react(h))      (one brick per workgroup: gridDim.x == g.nblk)
 // ---------------------------------------------------------------------------------------------
-template <typename T, int HC, int RZ, int NT = BRICK_NT>
+// X... = the flavour, as pi_fwd_kernel (flavour_arg): none; `long sample` (states [B][2][*S], one block); `long sample, int np`
+// (+ blocks P [B][np]).  Grid (bricks of one sample, B): workgroup (x, b) is brick x of sample b.  The sample offset is
+// wave-uniform and folded into the bases HERE, ahead of every sgpr_ptr: plane bases stay scalar and the lane offset stays the
+// one 32-bit `eb`, so sample b's frame is the unbatched launch's, bit for bit.  The sample flavours carry no fused put (`put`
+// is passed empty and never read).  Placement: Brick::locate is handed blockIdx.x as it is.  With grid (nblk, B) sample b's
+// workgroups are dispatched b * gridDim.x further on, i.e. brick x runs on XCD (x + b * gridDim.x) % 8 -- a rotation of the
+// XCDs per sample.  All locate relies on is that ids with equal residue mod 8 share an L2, which a constant shift keeps, so the
+// regions of every sample are as compact as the unbatched ones; shifting the id would only rename the XCDs.
+template <typename T, int HC, int RZ, int NT = BRICK_NT, typename... X>
 __global__ void __launch_bounds__(NT)
 pi_fwd3d_brick_kernel(const T* __restrict__ h, T* __restrict__ out, const T* __restrict__ P, BrickGeom g, int hc_rt,
-                      PeerPutFused put)
+                      PeerPutFused put, X... x)
 {
+    if constexpr (sizeof...(X) >= 1) {
+        static_assert(NT == BRICK_NT, "sample flavours: 256-lane bricks");
+        h += (long)blockIdx.y * flavour_arg<0>(x...);
+        out += (long)blockIdx.y * flavour_arg<0>(x...);
+    }
+    if constexpr (sizeof...(X) == 2) P += (long)blockIdx.y * flavour_arg<1>(x...);   // block of sample blockIdx.y
     constexpr int VEC = 16 / (int)sizeof(T);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     // slab layout, peer-mailbox ring: the lowest `put.nput` workgroups carry the faces of the frame being written into the
     // neighbours' mailboxes as soon as the bricks that hold them have stored them (pi_peer.h "put fused into the step kernel")
-    if (put.nput && (int)blockIdx.x < put.nput) {
-        if (put.vec16) peer_put_block<true>(put, (int)blockIdx.x);
-        else peer_put_block<false>(put, (int)blockIdx.x);
-        return;
+    if constexpr (sizeof...(X) == 0) {
+        if (put.nput && (int)blockIdx.x < put.nput) {
+            if (put.vec16) peer_put_block<true>(put, (int)blockIdx.x);
+            else peer_put_block<false>(put, (int)blockIdx.x);
+            return;
+        }
     }
     const int hc = HC > 0 ? HC : hc_rt;
     PI_STAMP3(0);
     Brick<T, RZ, NT> B;
-    B.locate(g, blockIdx.x - (unsigned)put.nput, gridDim.x - (unsigned)put.nput, 0u);
+    if constexpr (sizeof...(X) == 0) B.locate(g, blockIdx.x - (unsigned)put.nput, gridDim.x - (unsigned)put.nput, 0u);
+    else B.locate(g, blockIdx.x, gridDim.x, 0u);
     Lane L;
     L.i0 = B.i0; L.eb = B.eb;
     Geom gg = brick_as_geom(g);
@@ -280,7 +297,9 @@ pi_fwd3d_brick_kernel(const T* __restrict__ h, T* __restrict__ out, const T* __r
         }
         PI_STAMP3(4 + (j > 0));
     }
-    if (put.nput) peer_face_stored(put, B.i0, min(B.i0 + RZ, g.n0));
+    if constexpr (sizeof...(X) == 0) {
+        if (put.nput) peer_face_stored(put, B.i0, min(B.i0 + RZ, g.n0));
+    }
     PI_STAMP3(7);
 }
 
@@ -399,17 +418,26 @@ struct NoPut {};
 template <bool PUT> struct AdjPutArg { using type = NoPut; };
 template <> struct AdjPutArg<true> { using type = PeerPutFused; };
 
-template <typename T, int HC, int RZ, bool MOM, int LOSS = 0, int NT = BRICK_NT, bool PUT = false>
+// X... = the flavour, as pi_bwd_kernel: none; `long sample` (partial row blockIdx.y * gridDim.x + blockIdx.x); `long sample, int
+// rows` (block of sample blockIdx.y, partial row blockIdx.y * rows + blockIdx.x).  Workgroup (x, b) walks bricks x, x + gridDim.x,
+// ... of sample b; bases and placement as in the forward kernel's sample flavours; the loss forms read their sample's factor.
+template <typename T, int HC, int RZ, bool MOM, int LOSS = 0, int NT = BRICK_NT, bool PUT = false, typename... X>
 #ifndef PI_ADJ_RZ2_WAVES
 #define PI_ADJ_RZ2_WAVES 2
 #endif
 __global__ void __launch_bounds__(NT, (RZ == 1 && HC == POLY && LOSS != 2 && sizeof(T) == 4 && !PUT) ? 4 : (RZ == 2 && HC == POLY && LOSS == 0 && sizeof(T) == 4 && NT == 256 && !PUT ? PI_ADJ_RZ2_WAVES : 2))   // one-plane bricks of pre-contracted float32
 pi_adj3d_brick_kernel(const T* __restrict__ h, const T* __restrict__ G, const T* __restrict__ inj, T* __restrict__ Gp,
                       double* __restrict__ partials, const T* __restrict__ P, BrickGeom g, int hc_rt,
-                      typename AdjPutArg<PUT>::type put)
+                      typename AdjPutArg<PUT>::type put, X... x)
 {
     static_assert(!MOM || HC == POLY, "fused moments are those of the pre-contracted block");
-    unsigned bid = blockIdx.x, nwg = gridDim.x;              // this workgroup among the brick workgroups
+    if constexpr (sizeof...(X) >= 1) {
+        static_assert(NT == BRICK_NT && !PUT, "sample flavours: 256-lane bricks, no fused put");
+        const long sbase = (long)blockIdx.y * flavour_arg<0>(x...);      // sample blockIdx.y
+        h += sbase; G += sbase; Gp += sbase;
+        if (inj) inj += sbase;
+    }
+    unsigned bid = blockIdx.x, nwg = gridDim.x;              // this workgroup among the brick workgroups (of its sample)
     if constexpr (PUT) {
         if ((int)blockIdx.x < put.nput) {
             if (put.vec16) peer_put_block<true>(put, (int)blockIdx.x);
@@ -423,13 +451,17 @@ pi_adj3d_brick_kernel(const T* __restrict__ h, const T* __restrict__ G, const T*
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int hc = HC == POLY ? 0 : (HC > 0 ? HC : hc_rt);
     const int np = nparams(hc);
+    if constexpr (sizeof...(X) == 2) P += (long)blockIdx.y * np;         // block of sample blockIdx.y
     // LDS: [NW][2] coefficient sums (double) | windows, overlaid after the last pass by the moment transpose scratch
     double* redc = reinterpret_cast<double*>(smem_raw);
     constexpr unsigned WIN0 = NW * 2 * sizeof(double);
     const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
     // this workgroup's partial row: requested now, needed at the very end
     auto slot_of = [&](int k) { return k < 2 ? P_COEF + k : P_W + k - 2; };
-    double* const prow = partials + (long)bid * np;
+    long row = bid;
+    if constexpr (sizeof...(X) == 1) row = (long)blockIdx.y * gridDim.x + blockIdx.x;
+    if constexpr (sizeof...(X) == 2) row = (long)blockIdx.y * flavour_arg<1>(x...) + blockIdx.x;
+    double* const prow = partials + row * np;
     const int nsum = MOM ? 22 : 2;
     const double pold = (int)threadIdx.x < nsum ? prow[slot_of((int)threadIdx.x)] : 0.0;
 
@@ -595,7 +627,9 @@ pi_adj3d_brick_kernel(const T* __restrict__ h, const T* __restrict__ G, const T*
             }
             if (inj) {
                 if constexpr (LOSS != 0) {
-                    const T la = loss_factor<T>(g.loss);
+                    T la;
+                    if constexpr (sizeof...(X) >= 1) la = loss_factor<T>(g.loss, (long)blockIdx.y);   // its sample's factor
+                    else la = loss_factor<T>(g.loss);
 #pragma unroll
                     for (int i = 0; i < VEC; ++i) {
                         ou.v[i] += la * (LOSS == 2 ? u.v[i] - ju[j].v[i] : u.v[i]);
