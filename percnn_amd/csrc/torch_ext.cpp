@@ -9,6 +9,12 @@
 //   percnn::pi_rollout(Tensor h0, Tensor params, int steps, str options="") -> Tensor        (+ autograd)
 //   percnn::pi_rollout_backward(Tensor traj, Tensor params, Tensor g_traj, str options="") -> (Tensor, Tensor)
 //
+// and the same four on B independent samples [B,2,*S] (trajectory [T+1,B,2,*S]), twelve operators in all:
+//   percnn::pi_{step,rollout}_batched[_backward]    one parameter block [np]; its gradient is the sum over the samples
+//   percnn::pi_{step,rollout}_ensemble[_backward]   one block per sample [B,np]; its gradient is [B,np], one row per sample
+// One body per operator, instantiated with a flavour (`Batched` / `Ensemble`: entry points, names, how the hidden width is
+// read); one step and one rollout autograd node for all three flavours; float32 / float64 chosen in `with_dtype` alone.
+//
 // dispatcher -> launcher: no Python / ctypes frame between `cell(h)` and the C-ABI of include/percnn_pi.h (libpercnn_pi.so,
 // which this library links).  PyTorch supplies device memory, the current HIP stream and the autograd graph -- nothing else.
 // FakeTensor implementations are registered from Python (percnn_amd/ops.py: torch.library.register_fake).
@@ -65,8 +71,8 @@ inline void check(int rc, const char* what) { if (rc != 0) fail(rc, what); }
 inline void require(const Tensor& t, const char* name)
 {
     TORCH_CHECK(t.is_cuda(), "percnn_amd: ", name, " must live on a HIP device (got ", t.device(), "); there is no CPU path");
-    TORCH_CHECK(t.scalar_type() == at::kFloat || t.scalar_type() == at::kDouble, "percnn_amd: ", name,
-                " must be float32 or float64, got ", t.scalar_type());
+    const at::ScalarType dtype = t.scalar_type();
+    TORCH_CHECK(dtype == at::kFloat || dtype == at::kDouble, "percnn_amd: ", name, " must be float32 or float64, got ", dtype);
 }
 inline void require_like(const Tensor& t, const Tensor& ref, const char* name)
 {
@@ -107,6 +113,35 @@ struct Shape {
 inline void* stream_of(const Tensor& t) { return c10::hip::getCurrentHIPStream(t.device().index()).stream(); }
 inline const char* opt_c(const std::string& o) { return o.empty() ? nullptr : o.c_str(); }
 
+// ---- float32 / float64: the entry points of one element type, and the one place that picks between them --------------------
+template <class T> struct Abi;
+#define PERCNN_ABI(T, suf)                                                                                                    \
+    template <> struct Abi<T> {                                                                                               \
+        static constexpr auto step_fwd = percnn_pi_step_fwd_opt_##suf;                                                        \
+        static constexpr auto step_bwd = percnn_pi_step_bwd_opt_##suf;                                                        \
+        static constexpr auto step_bwd_rows = percnn_pi_step_bwd_rows_##suf;                                                  \
+        static constexpr auto bwd_rows_finish = percnn_pi_bwd_rows_finish_##suf;                                              \
+        static constexpr auto rollout_fwd = percnn_pi_rollout_fwd_opt_##suf;                                                  \
+        static constexpr auto rollout_bwd = percnn_pi_rollout_bwd_opt_##suf;                                                  \
+        static constexpr auto rollout_bwd_top = percnn_pi_rollout_bwd_top_##suf;                                              \
+        static constexpr auto batch_step_fwd = percnn_pi_batch_step_fwd_##suf;                                                \
+        static constexpr auto batch_step_bwd = percnn_pi_batch_step_bwd_##suf;                                                \
+        static constexpr auto batch_rollout_fwd = percnn_pi_batch_rollout_fwd_##suf;                                          \
+        static constexpr auto batch_rollout_bwd = percnn_pi_batch_rollout_bwd_##suf;                                          \
+        static constexpr auto ensemble_step_fwd = percnn_pi_ensemble_step_fwd_##suf;                                          \
+        static constexpr auto ensemble_step_bwd = percnn_pi_ensemble_step_bwd_##suf;                                          \
+        static constexpr auto ensemble_rollout_fwd = percnn_pi_ensemble_rollout_fwd_##suf;                                    \
+        static constexpr auto ensemble_rollout_bwd = percnn_pi_ensemble_rollout_bwd_##suf;                                    \
+    }
+PERCNN_ABI(float, f32);
+PERCNN_ABI(double, f64);
+#undef PERCNN_ABI
+
+// fn(T{}) with T = float or double (callers have been through require(): nothing else arrives).  A template over the callable:
+// the lambda is inlined into both arms, what is left is the branch a hand-written if / else has.
+template <class Fn> inline auto with_dtype(at::ScalarType dtype, Fn&& fn) { return dtype == at::kFloat ? fn(float{}) : fn(double{}); }
+template <class Fn> inline auto with_dtype(const Tensor& t, Fn&& fn) { return with_dtype(t.scalar_type(), std::forward<Fn>(fn)); }
+
 // ---- raw calls -----------------------------------------------------------------------------------------------------
 Tensor step_fwd_raw(const Tensor& h, const Tensor& P, const std::string& options)
 {
@@ -114,14 +149,11 @@ Tensor step_fwd_raw(const Tensor& h, const Tensor& P, const std::string& options
     Tensor out = at::empty_like(h);
     void* st = stream_of(h);
     const int hc = hc_of(P);
-    int rc;
-    if (h.scalar_type() == at::kFloat)
-        rc = percnn_pi_step_fwd_opt_f32(h.const_data_ptr<float>(), out.mutable_data_ptr<float>(), P.const_data_ptr<float>(), hc,
-                                        sh.ndim, sh.s, opt_c(options), st);
-    else
-        rc = percnn_pi_step_fwd_opt_f64(h.const_data_ptr<double>(), out.mutable_data_ptr<double>(), P.const_data_ptr<double>(), hc,
-                                        sh.ndim, sh.s, opt_c(options), st);
-    check(rc, "step_fwd");
+    check(with_dtype(h, [&](auto tag) {
+              using T = decltype(tag);
+              return Abi<T>::step_fwd(h.const_data_ptr<T>(), out.mutable_data_ptr<T>(), P.const_data_ptr<T>(), hc, sh.ndim, sh.s,
+                                      opt_c(options), st);
+          }), "step_fwd");
     return out;
 }
 
@@ -141,20 +173,16 @@ Tensor step_bwd_raw(const Tensor& h, const Tensor& g_out, const Tensor& P, Tenso
     Tensor g_in = at::empty_like(h);
     Tensor ws = step_workspace(h, hc, sh);
     void* st = stream_of(h);
-    int rc;
-    if (h.scalar_type() == at::kFloat)
-        rc = percnn_pi_step_bwd_opt_f32(h.const_data_ptr<float>(), g_out.const_data_ptr<float>(), nullptr,
-                                        g_in.mutable_data_ptr<float>(), param_grad.mutable_data_ptr<double>(), ws.mutable_data_ptr(),
-                                        (size_t)ws.numel(), P.const_data_ptr<float>(), hc, sh.ndim, sh.s, opt_c(options), st);
-    else
-        rc = percnn_pi_step_bwd_opt_f64(h.const_data_ptr<double>(), g_out.const_data_ptr<double>(), nullptr,
-                                        g_in.mutable_data_ptr<double>(), param_grad.mutable_data_ptr<double>(), ws.mutable_data_ptr(),
-                                        (size_t)ws.numel(), P.const_data_ptr<double>(), hc, sh.ndim, sh.s, opt_c(options), st);
-    check(rc, "step_bwd");
+    check(with_dtype(h, [&](auto tag) {
+              using T = decltype(tag);
+              return Abi<T>::step_bwd(h.const_data_ptr<T>(), g_out.const_data_ptr<T>(), nullptr, g_in.mutable_data_ptr<T>(),
+                                      param_grad.mutable_data_ptr<double>(), ws.mutable_data_ptr(), (size_t)ws.numel(),
+                                      P.const_data_ptr<T>(), hc, sh.ndim, sh.s, opt_c(options), st);
+          }), "step_bwd");
     return g_in;
 }
 
-// ---- registered operators (HIP tensors carry the CUDA dispatch key on PyTorch-ROCm) -----------------------------------
+// ---- registered operators, unbatched: state [1,2,*S], trajectory [T+1,2,*S] ------------------------------------------------
 Tensor pi_step_impl(const Tensor& h, const Tensor& params, std::string options)
 {
     check_state(h);
@@ -192,14 +220,11 @@ Tensor pi_rollout_impl(const Tensor& h0, const Tensor& params, int64_t steps, st
     const Shape sh(traj, 2);
     void* st = stream_of(traj);
     const int hc = hc_of(P);
-    int rc;
-    if (traj.scalar_type() == at::kFloat)
-        rc = percnn_pi_rollout_fwd_opt_f32(traj.mutable_data_ptr<float>(), P.const_data_ptr<float>(), hc, sh.ndim, sh.s, (int)steps,
-                                           opt_c(options), st);
-    else
-        rc = percnn_pi_rollout_fwd_opt_f64(traj.mutable_data_ptr<double>(), P.const_data_ptr<double>(), hc, sh.ndim, sh.s, (int)steps,
-                                           opt_c(options), st);
-    check(rc, "rollout_fwd");
+    check(with_dtype(traj, [&](auto tag) {
+              using T = decltype(tag);
+              return Abi<T>::rollout_fwd(traj.mutable_data_ptr<T>(), P.const_data_ptr<T>(), hc, sh.ndim, sh.s, (int)steps,
+                                         opt_c(options), st);
+          }), "rollout_fwd");
     return traj;
 }
 
@@ -222,142 +247,23 @@ std::tuple<Tensor, Tensor> pi_rollout_backward_impl(const Tensor& traj, const Te
     TORCH_CHECK(nbytes != 0, "percnn_amd: invalid problem shape");
     Tensor ws = at::empty({(int64_t)nbytes}, traj.options().dtype(at::kByte));
     void* st = stream_of(traj);
-    int rc;
-    if (traj.scalar_type() == at::kFloat)
-        rc = percnn_pi_rollout_bwd_opt_f32(traj.const_data_ptr<float>(), g.const_data_ptr<float>(), nullptr, g_h0.mutable_data_ptr<float>(),
-                                           pg.mutable_data_ptr<double>(), ws.mutable_data_ptr(), (size_t)ws.numel(),
-                                           P.const_data_ptr<float>(), hc, sh.ndim, sh.s, T, opt_c(options), st);
-    else
-        rc = percnn_pi_rollout_bwd_opt_f64(traj.const_data_ptr<double>(), g.const_data_ptr<double>(), nullptr,
-                                           g_h0.mutable_data_ptr<double>(), pg.mutable_data_ptr<double>(), ws.mutable_data_ptr(),
-                                           (size_t)ws.numel(), P.const_data_ptr<double>(), hc, sh.ndim, sh.s, T, opt_c(options), st);
-    check(rc, "rollout_bwd");
+    check(with_dtype(traj, [&](auto tag) {
+              using E = decltype(tag);
+              return Abi<E>::rollout_bwd(traj.const_data_ptr<E>(), g.const_data_ptr<E>(), nullptr, g_h0.mutable_data_ptr<E>(),
+                                         pg.mutable_data_ptr<double>(), ws.mutable_data_ptr(), (size_t)ws.numel(),
+                                         P.const_data_ptr<E>(), hc, sh.ndim, sh.s, T, opt_c(options), st);
+          }), "rollout_bwd");
     return {g_h0, pg.to(P.scalar_type())};
 }
 
-// ---- batched operators: B independent samples [B,2,*S], one parameter block (percnn_pi_batch_*) ----------------------------
+// ---- sample-parallel operators: B independent samples [B,2,*S], trajectory [T+1,B,2,*S] -----------------------------------
+// One body per operator; what the two flavours differ in is stated here and nowhere else.
 inline void check_batched_state(const Tensor& h)
 {
     TORCH_CHECK((h.dim() == 4 || h.dim() == 5) && h.size(0) >= 1 && h.size(1) == 2,
                 "percnn_amd: batched state must be [B,2,*S] (two species), got ", h.sizes());
 }
 
-Tensor pi_step_batched_impl(const Tensor& h, const Tensor& params, std::string options)
-{
-    check_batched_state(h);
-    require(h, "h");
-    require_like(params, h, "params");
-    c10::hip::HIPGuard guard(h.device().index());
-    const Tensor x = h.contiguous(), P = params.contiguous();
-    const Shape sh(x, 2);
-    Tensor out = at::empty_like(x);
-    void* st = stream_of(x);
-    const int hc = hc_of(P), B = (int)x.size(0);
-    int rc;
-    if (x.scalar_type() == at::kFloat)
-        rc = percnn_pi_batch_step_fwd_f32(x.const_data_ptr<float>(), out.mutable_data_ptr<float>(), P.const_data_ptr<float>(), hc,
-                                          sh.ndim, sh.s, B, opt_c(options), st);
-    else
-        rc = percnn_pi_batch_step_fwd_f64(x.const_data_ptr<double>(), out.mutable_data_ptr<double>(), P.const_data_ptr<double>(),
-                                          hc, sh.ndim, sh.s, B, opt_c(options), st);
-    check(rc, "batch_step_fwd");
-    return out;
-}
-
-std::tuple<Tensor, Tensor> pi_step_batched_backward_impl(const Tensor& h, const Tensor& params, const Tensor& g_out,
-                                                         std::string options)
-{
-    check_batched_state(h);
-    require(h, "h");
-    require_like(params, h, "params");
-    require_like(g_out, h, "g_out");
-    TORCH_CHECK(g_out.sizes() == h.sizes(), "percnn_amd: g_out must have the state's shape ", h.sizes(), ", got ", g_out.sizes());
-    c10::hip::HIPGuard guard(h.device().index());
-    const Tensor x = h.contiguous(), g = g_out.contiguous(), P = params.contiguous();
-    const Shape sh(x, 2);
-    const int hc = hc_of(P), B = (int)x.size(0);
-    Tensor g_in = at::empty_like(x);
-    Tensor pg = at::zeros({P.numel()}, x.options().dtype(at::kDouble));
-    const size_t nbytes = percnn_pi_batch_bwd_workspace_bytes(hc, sh.ndim, sh.s, B, (int)x.element_size());
-    TORCH_CHECK(nbytes != 0, "percnn_amd: invalid batched problem (shape, batch size or block kind)");
-    Tensor ws = at::empty({(int64_t)nbytes}, x.options().dtype(at::kByte));
-    void* st = stream_of(x);
-    int rc;
-    if (x.scalar_type() == at::kFloat)
-        rc = percnn_pi_batch_step_bwd_f32(x.const_data_ptr<float>(), g.const_data_ptr<float>(), nullptr, g_in.mutable_data_ptr<float>(),
-                                          pg.mutable_data_ptr<double>(), ws.mutable_data_ptr(), (size_t)ws.numel(),
-                                          P.const_data_ptr<float>(), hc, sh.ndim, sh.s, B, opt_c(options), st);
-    else
-        rc = percnn_pi_batch_step_bwd_f64(x.const_data_ptr<double>(), g.const_data_ptr<double>(), nullptr,
-                                          g_in.mutable_data_ptr<double>(), pg.mutable_data_ptr<double>(), ws.mutable_data_ptr(),
-                                          (size_t)ws.numel(), P.const_data_ptr<double>(), hc, sh.ndim, sh.s, B, opt_c(options), st);
-    check(rc, "batch_step_bwd");
-    return {g_in, pg.to(P.scalar_type())};
-}
-
-// -> trajectory [T+1, B, 2, *S] (frame 0 = h0)
-Tensor pi_rollout_batched_impl(const Tensor& h0, const Tensor& params, int64_t steps, std::string options)
-{
-    check_batched_state(h0);
-    require(h0, "h0");
-    require_like(params, h0, "params");
-    TORCH_CHECK(steps >= 0, "percnn_amd: steps must be >= 0");
-    c10::hip::HIPGuard guard(h0.device().index());
-    const Tensor P = params.contiguous();
-    std::vector<int64_t> sizes{steps + 1};
-    for (int64_t s : h0.sizes()) sizes.push_back(s);
-    Tensor traj = at::empty(sizes, h0.options());
-    traj.select(0, 0).copy_(h0);
-    const Shape sh(traj, 3);
-    void* st = stream_of(traj);
-    const int hc = hc_of(P), B = (int)h0.size(0);
-    int rc;
-    if (traj.scalar_type() == at::kFloat)
-        rc = percnn_pi_batch_rollout_fwd_f32(traj.mutable_data_ptr<float>(), P.const_data_ptr<float>(), hc, sh.ndim, sh.s, B,
-                                             (int)steps, opt_c(options), st);
-    else
-        rc = percnn_pi_batch_rollout_fwd_f64(traj.mutable_data_ptr<double>(), P.const_data_ptr<double>(), hc, sh.ndim, sh.s, B,
-                                             (int)steps, opt_c(options), st);
-    check(rc, "batch_rollout_fwd");
-    return traj;
-}
-
-std::tuple<Tensor, Tensor> pi_rollout_batched_backward_impl(const Tensor& traj, const Tensor& params, const Tensor& g_traj,
-                                                            std::string options)
-{
-    require(traj, "traj");
-    require_like(params, traj, "params");
-    require_like(g_traj, traj, "g_traj");
-    TORCH_CHECK(traj.is_contiguous(), "percnn_amd: traj must be contiguous");
-    TORCH_CHECK((traj.dim() == 5 || traj.dim() == 6) && traj.size(2) == 2 && traj.size(0) >= 1 && traj.size(1) >= 1,
-                "percnn_amd: batched traj must be [T+1,B,2,*S]");
-    TORCH_CHECK(g_traj.sizes() == traj.sizes(), "percnn_amd: g_traj must have the trajectory's shape");
-    c10::hip::HIPGuard guard(traj.device().index());
-    const Tensor P = params.contiguous(), g = g_traj.contiguous();
-    const Shape sh(traj, 3);
-    const int hc = hc_of(P), T = (int)traj.size(0) - 1, B = (int)traj.size(1);
-    Tensor g_h0 = at::empty(traj.sizes().slice(1), traj.options());
-    Tensor pg = at::zeros({P.numel()}, traj.options().dtype(at::kDouble));
-    const size_t nbytes = percnn_pi_batch_rollout_bwd_workspace_bytes(hc, sh.ndim, sh.s, B, T, (int)traj.element_size());
-    TORCH_CHECK(nbytes != 0, "percnn_amd: invalid batched problem (shape, batch size or block kind)");
-    Tensor ws = at::empty({(int64_t)nbytes}, traj.options().dtype(at::kByte));
-    void* st = stream_of(traj);
-    int rc;
-    if (traj.scalar_type() == at::kFloat)
-        rc = percnn_pi_batch_rollout_bwd_f32(traj.const_data_ptr<float>(), g.const_data_ptr<float>(), nullptr,
-                                             g_h0.mutable_data_ptr<float>(), pg.mutable_data_ptr<double>(), ws.mutable_data_ptr(),
-                                             (size_t)ws.numel(), P.const_data_ptr<float>(), hc, sh.ndim, sh.s, B, T, opt_c(options),
-                                             st);
-    else
-        rc = percnn_pi_batch_rollout_bwd_f64(traj.const_data_ptr<double>(), g.const_data_ptr<double>(), nullptr,
-                                             g_h0.mutable_data_ptr<double>(), pg.mutable_data_ptr<double>(), ws.mutable_data_ptr(),
-                                             (size_t)ws.numel(), P.const_data_ptr<double>(), hc, sh.ndim, sh.s, B, T, opt_c(options),
-                                             st);
-    check(rc, "batch_rollout_bwd");
-    return {g_h0, pg.to(P.scalar_type())};
-}
-
-// ---- ensemble operators: B independent samples [B,2,*S], one parameter block per sample [B,np] (percnn_pi_ensemble_*) -------
 // hidden width of a stack of blocks [B,np] (all of one kind), checked against the batch size of the state
 inline int hc_of_ensemble(const Tensor& P, int64_t B)
 {
@@ -368,70 +274,95 @@ inline int hc_of_ensemble(const Tensor& P, int64_t B)
     return hc;
 }
 
-Tensor pi_step_ensemble_impl(const Tensor& h, const Tensor& params, std::string options)
+struct Single {                                             // (operator names only: the unbatched bodies are their own, above)
+    static constexpr const char *step = "percnn::pi_step", *step_backward = "percnn::pi_step_backward",
+                                *rollout = "percnn::pi_rollout", *rollout_backward = "percnn::pi_rollout_backward";
+};
+struct Batched {                                            // one parameter block [np] (percnn_pi_batch_*)
+    static constexpr const char *step = "percnn::pi_step_batched", *step_backward = "percnn::pi_step_batched_backward",
+                                *rollout = "percnn::pi_rollout_batched", *rollout_backward = "percnn::pi_rollout_batched_backward";
+    static constexpr const char *word = "batched", *step_fwd_what = "batch_step_fwd", *step_bwd_what = "batch_step_bwd",
+                                *rollout_fwd_what = "batch_rollout_fwd", *rollout_bwd_what = "batch_rollout_bwd";
+    template <class T> static constexpr auto step_fwd = Abi<T>::batch_step_fwd;
+    template <class T> static constexpr auto step_bwd = Abi<T>::batch_step_bwd;
+    template <class T> static constexpr auto rollout_fwd = Abi<T>::batch_rollout_fwd;
+    template <class T> static constexpr auto rollout_bwd = Abi<T>::batch_rollout_bwd;
+    static constexpr auto step_workspace_bytes = percnn_pi_batch_bwd_workspace_bytes;
+    static constexpr auto rollout_workspace_bytes = percnn_pi_batch_rollout_bwd_workspace_bytes;
+    static int hc(const Tensor& params, int64_t) { return hc_of(params); }
+};
+struct Ensemble {                                           // one parameter block per sample [B,np] (percnn_pi_ensemble_*)
+    static constexpr const char *step = "percnn::pi_step_ensemble", *step_backward = "percnn::pi_step_ensemble_backward",
+                                *rollout = "percnn::pi_rollout_ensemble", *rollout_backward = "percnn::pi_rollout_ensemble_backward";
+    static constexpr const char *word = "ensemble", *step_fwd_what = "ensemble_step_fwd", *step_bwd_what = "ensemble_step_bwd",
+                                *rollout_fwd_what = "ensemble_rollout_fwd", *rollout_bwd_what = "ensemble_rollout_bwd";
+    template <class T> static constexpr auto step_fwd = Abi<T>::ensemble_step_fwd;
+    template <class T> static constexpr auto step_bwd = Abi<T>::ensemble_step_bwd;
+    template <class T> static constexpr auto rollout_fwd = Abi<T>::ensemble_rollout_fwd;
+    template <class T> static constexpr auto rollout_bwd = Abi<T>::ensemble_rollout_bwd;
+    static constexpr auto step_workspace_bytes = percnn_pi_ensemble_bwd_workspace_bytes;
+    static constexpr auto rollout_workspace_bytes = percnn_pi_ensemble_rollout_bwd_workspace_bytes;
+    static int hc(const Tensor& params, int64_t B) { return hc_of_ensemble(params, B); }
+};
+// F::hc follows the argument checks and precedes the device guard; nothing that can refuse a call lies between it and the
+// workspace check.  The parameter gradient has the block's shape in both flavours: [np] is all hc_of lets through.
+
+template <class F> Tensor pi_step_samples(const Tensor& h, const Tensor& params, std::string options)
 {
     check_batched_state(h);
     require(h, "h");
     require_like(params, h, "params");
-    const int hc = hc_of_ensemble(params, h.size(0));
+    const int hc = F::hc(params, h.size(0));
     c10::hip::HIPGuard guard(h.device().index());
     const Tensor x = h.contiguous(), P = params.contiguous();
     const Shape sh(x, 2);
     Tensor out = at::empty_like(x);
     void* st = stream_of(x);
     const int B = (int)x.size(0);
-    int rc;
-    if (x.scalar_type() == at::kFloat)
-        rc = percnn_pi_ensemble_step_fwd_f32(x.const_data_ptr<float>(), out.mutable_data_ptr<float>(), P.const_data_ptr<float>(),
-                                             hc, sh.ndim, sh.s, B, opt_c(options), st);
-    else
-        rc = percnn_pi_ensemble_step_fwd_f64(x.const_data_ptr<double>(), out.mutable_data_ptr<double>(),
-                                             P.const_data_ptr<double>(), hc, sh.ndim, sh.s, B, opt_c(options), st);
-    check(rc, "ensemble_step_fwd");
+    check(with_dtype(x, [&](auto tag) {
+              using T = decltype(tag);
+              return F::template step_fwd<T>(x.const_data_ptr<T>(), out.mutable_data_ptr<T>(), P.const_data_ptr<T>(), hc, sh.ndim,
+                                             sh.s, B, opt_c(options), st);
+          }), F::step_fwd_what);
     return out;
 }
 
-std::tuple<Tensor, Tensor> pi_step_ensemble_backward_impl(const Tensor& h, const Tensor& params, const Tensor& g_out,
-                                                          std::string options)
+template <class F>
+std::tuple<Tensor, Tensor> pi_step_samples_backward(const Tensor& h, const Tensor& params, const Tensor& g_out, std::string options)
 {
     check_batched_state(h);
     require(h, "h");
     require_like(params, h, "params");
     require_like(g_out, h, "g_out");
     TORCH_CHECK(g_out.sizes() == h.sizes(), "percnn_amd: g_out must have the state's shape ", h.sizes(), ", got ", g_out.sizes());
-    const int hc = hc_of_ensemble(params, h.size(0));
+    const int hc = F::hc(params, h.size(0));
     c10::hip::HIPGuard guard(h.device().index());
     const Tensor x = h.contiguous(), g = g_out.contiguous(), P = params.contiguous();
     const Shape sh(x, 2);
     const int B = (int)x.size(0);
     Tensor g_in = at::empty_like(x);
     Tensor pg = at::zeros(P.sizes(), x.options().dtype(at::kDouble));
-    const size_t nbytes = percnn_pi_ensemble_bwd_workspace_bytes(hc, sh.ndim, sh.s, B, (int)x.element_size());
-    TORCH_CHECK(nbytes != 0, "percnn_amd: invalid ensemble problem (shape, batch size or block kind)");
+    const size_t nbytes = F::step_workspace_bytes(hc, sh.ndim, sh.s, B, (int)x.element_size());
+    TORCH_CHECK(nbytes != 0, "percnn_amd: invalid ", F::word, " problem (shape, batch size or block kind)");
     Tensor ws = at::empty({(int64_t)nbytes}, x.options().dtype(at::kByte));
     void* st = stream_of(x);
-    int rc;
-    if (x.scalar_type() == at::kFloat)
-        rc = percnn_pi_ensemble_step_bwd_f32(x.const_data_ptr<float>(), g.const_data_ptr<float>(), nullptr,
-                                             g_in.mutable_data_ptr<float>(), pg.mutable_data_ptr<double>(), ws.mutable_data_ptr(),
-                                             (size_t)ws.numel(), P.const_data_ptr<float>(), hc, sh.ndim, sh.s, B, opt_c(options), st);
-    else
-        rc = percnn_pi_ensemble_step_bwd_f64(x.const_data_ptr<double>(), g.const_data_ptr<double>(), nullptr,
-                                             g_in.mutable_data_ptr<double>(), pg.mutable_data_ptr<double>(), ws.mutable_data_ptr(),
-                                             (size_t)ws.numel(), P.const_data_ptr<double>(), hc, sh.ndim, sh.s, B, opt_c(options),
-                                             st);
-    check(rc, "ensemble_step_bwd");
+    check(with_dtype(x, [&](auto tag) {
+              using T = decltype(tag);
+              return F::template step_bwd<T>(x.const_data_ptr<T>(), g.const_data_ptr<T>(), nullptr, g_in.mutable_data_ptr<T>(),
+                                             pg.mutable_data_ptr<double>(), ws.mutable_data_ptr(), (size_t)ws.numel(),
+                                             P.const_data_ptr<T>(), hc, sh.ndim, sh.s, B, opt_c(options), st);
+          }), F::step_bwd_what);
     return {g_in, pg.to(P.scalar_type())};
 }
 
 // -> trajectory [T+1, B, 2, *S] (frame 0 = h0)
-Tensor pi_rollout_ensemble_impl(const Tensor& h0, const Tensor& params, int64_t steps, std::string options)
+template <class F> Tensor pi_rollout_samples(const Tensor& h0, const Tensor& params, int64_t steps, std::string options)
 {
     check_batched_state(h0);
     require(h0, "h0");
     require_like(params, h0, "params");
     TORCH_CHECK(steps >= 0, "percnn_amd: steps must be >= 0");
-    const int hc = hc_of_ensemble(params, h0.size(0));
+    const int hc = F::hc(params, h0.size(0));
     c10::hip::HIPGuard guard(h0.device().index());
     const Tensor P = params.contiguous();
     std::vector<int64_t> sizes{steps + 1};
@@ -441,60 +372,53 @@ Tensor pi_rollout_ensemble_impl(const Tensor& h0, const Tensor& params, int64_t 
     const Shape sh(traj, 3);
     void* st = stream_of(traj);
     const int B = (int)h0.size(0);
-    int rc;
-    if (traj.scalar_type() == at::kFloat)
-        rc = percnn_pi_ensemble_rollout_fwd_f32(traj.mutable_data_ptr<float>(), P.const_data_ptr<float>(), hc, sh.ndim, sh.s, B,
-                                                (int)steps, opt_c(options), st);
-    else
-        rc = percnn_pi_ensemble_rollout_fwd_f64(traj.mutable_data_ptr<double>(), P.const_data_ptr<double>(), hc, sh.ndim, sh.s, B,
-                                                (int)steps, opt_c(options), st);
-    check(rc, "ensemble_rollout_fwd");
+    check(with_dtype(traj, [&](auto tag) {
+              using T = decltype(tag);
+              return F::template rollout_fwd<T>(traj.mutable_data_ptr<T>(), P.const_data_ptr<T>(), hc, sh.ndim, sh.s, B, (int)steps,
+                                                opt_c(options), st);
+          }), F::rollout_fwd_what);
     return traj;
 }
 
-std::tuple<Tensor, Tensor> pi_rollout_ensemble_backward_impl(const Tensor& traj, const Tensor& params, const Tensor& g_traj,
-                                                             std::string options)
+template <class F>
+std::tuple<Tensor, Tensor> pi_rollout_samples_backward(const Tensor& traj, const Tensor& params, const Tensor& g_traj,
+                                                       std::string options)
 {
     require(traj, "traj");
     require_like(params, traj, "params");
     require_like(g_traj, traj, "g_traj");
     TORCH_CHECK(traj.is_contiguous(), "percnn_amd: traj must be contiguous");
     TORCH_CHECK((traj.dim() == 5 || traj.dim() == 6) && traj.size(2) == 2 && traj.size(0) >= 1 && traj.size(1) >= 1,
-                "percnn_amd: ensemble traj must be [T+1,B,2,*S]");
+                "percnn_amd: ", F::word, " traj must be [T+1,B,2,*S]");
     TORCH_CHECK(g_traj.sizes() == traj.sizes(), "percnn_amd: g_traj must have the trajectory's shape");
-    const int hc = hc_of_ensemble(params, traj.size(1));
+    const int hc = F::hc(params, traj.size(1));
     c10::hip::HIPGuard guard(traj.device().index());
     const Tensor P = params.contiguous(), g = g_traj.contiguous();
     const Shape sh(traj, 3);
-    const int T = (int)traj.size(0) - 1, B = (int)traj.size(1);
+    const int steps = (int)traj.size(0) - 1, B = (int)traj.size(1);
     Tensor g_h0 = at::empty(traj.sizes().slice(1), traj.options());
     Tensor pg = at::zeros(P.sizes(), traj.options().dtype(at::kDouble));
-    const size_t nbytes = percnn_pi_ensemble_rollout_bwd_workspace_bytes(hc, sh.ndim, sh.s, B, T, (int)traj.element_size());
-    TORCH_CHECK(nbytes != 0, "percnn_amd: invalid ensemble problem (shape, batch size or block kind)");
+    const size_t nbytes = F::rollout_workspace_bytes(hc, sh.ndim, sh.s, B, steps, (int)traj.element_size());
+    TORCH_CHECK(nbytes != 0, "percnn_amd: invalid ", F::word, " problem (shape, batch size or block kind)");
     Tensor ws = at::empty({(int64_t)nbytes}, traj.options().dtype(at::kByte));
     void* st = stream_of(traj);
-    int rc;
-    if (traj.scalar_type() == at::kFloat)
-        rc = percnn_pi_ensemble_rollout_bwd_f32(traj.const_data_ptr<float>(), g.const_data_ptr<float>(), nullptr,
-                                                g_h0.mutable_data_ptr<float>(), pg.mutable_data_ptr<double>(),
-                                                ws.mutable_data_ptr(), (size_t)ws.numel(), P.const_data_ptr<float>(), hc, sh.ndim,
-                                                sh.s, B, T, opt_c(options), st);
-    else
-        rc = percnn_pi_ensemble_rollout_bwd_f64(traj.const_data_ptr<double>(), g.const_data_ptr<double>(), nullptr,
-                                                g_h0.mutable_data_ptr<double>(), pg.mutable_data_ptr<double>(),
-                                                ws.mutable_data_ptr(), (size_t)ws.numel(), P.const_data_ptr<double>(), hc, sh.ndim,
-                                                sh.s, B, T, opt_c(options), st);
-    check(rc, "ensemble_rollout_bwd");
+    check(with_dtype(traj, [&](auto tag) {
+              using T = decltype(tag);
+              return F::template rollout_bwd<T>(traj.const_data_ptr<T>(), g.const_data_ptr<T>(), nullptr, g_h0.mutable_data_ptr<T>(),
+                                                pg.mutable_data_ptr<double>(), ws.mutable_data_ptr(), (size_t)ws.numel(),
+                                                P.const_data_ptr<T>(), hc, sh.ndim, sh.s, B, steps, opt_c(options), st);
+          }), F::rollout_bwd_what);
     return {g_h0, pg.to(P.scalar_type())};
 }
 
-// ---- autograd formulas of the registered operators ----------------------------------------------------------------------
-struct PiStepFn : public torch::autograd::Function<PiStepFn> {
+// ---- autograd formulas of the registered operators: one step node and one rollout node, named by the flavour --------------
+using BackwardSig = std::tuple<Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, std::string);
+
+template <class F> struct PiStepFn : public torch::autograd::Function<PiStepFn<F>> {
     static Tensor forward(AutogradContext* ctx, const Tensor& h, const Tensor& params, std::string options)
     {
         at::AutoDispatchBelowADInplaceOrView below;
-        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("percnn::pi_step", "")
-                             .typed<Tensor(const Tensor&, const Tensor&, std::string)>();
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow(F::step, "").template typed<Tensor(const Tensor&, const Tensor&, std::string)>();
         Tensor out = op.call(h, params, options);
         ctx->save_for_backward({h, params});
         ctx->saved_data["options"] = options;
@@ -503,20 +427,22 @@ struct PiStepFn : public torch::autograd::Function<PiStepFn> {
     static variable_list backward(AutogradContext* ctx, variable_list grads)
     {
         const auto saved = ctx->get_saved_variables();
-        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("percnn::pi_step_backward", "")
-                             .typed<std::tuple<Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, std::string)>();
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow(F::step_backward, "").template typed<BackwardSig>();
         auto [g_in, g_p] = op.call(saved[0], saved[1], grads[0], ctx->saved_data["options"].toStringRef());
         return {g_in, g_p, Tensor()};
     }
 };
-Tensor pi_step_autograd(const Tensor& h, const Tensor& params, std::string options) { return PiStepFn::apply(h, params, options); }
+template <class F> Tensor pi_step_autograd(const Tensor& h, const Tensor& params, std::string options)
+{
+    return PiStepFn<F>::apply(h, params, options);
+}
 
-struct PiRolloutFn : public torch::autograd::Function<PiRolloutFn> {
+template <class F> struct PiRolloutFn : public torch::autograd::Function<PiRolloutFn<F>> {
     static Tensor forward(AutogradContext* ctx, const Tensor& h0, const Tensor& params, int64_t steps, std::string options)
     {
         at::AutoDispatchBelowADInplaceOrView below;
-        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("percnn::pi_rollout", "")
-                             .typed<Tensor(const Tensor&, const Tensor&, int64_t, std::string)>();
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow(F::rollout, "")
+                             .template typed<Tensor(const Tensor&, const Tensor&, int64_t, std::string)>();
         Tensor traj = op.call(h0, params, steps, options);
         ctx->save_for_backward({traj, params});
         ctx->saved_data["options"] = options;
@@ -525,115 +451,14 @@ struct PiRolloutFn : public torch::autograd::Function<PiRolloutFn> {
     static variable_list backward(AutogradContext* ctx, variable_list grads)
     {
         const auto saved = ctx->get_saved_variables();
-        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("percnn::pi_rollout_backward", "")
-                             .typed<std::tuple<Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, std::string)>();
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow(F::rollout_backward, "").template typed<BackwardSig>();
         auto [g_h0, g_p] = op.call(saved[0], saved[1], grads[0], ctx->saved_data["options"].toStringRef());
         return {g_h0, g_p, Tensor(), Tensor()};
     }
 };
-Tensor pi_rollout_autograd(const Tensor& h0, const Tensor& params, int64_t steps, std::string options)
+template <class F> Tensor pi_rollout_autograd(const Tensor& h0, const Tensor& params, int64_t steps, std::string options)
 {
-    return PiRolloutFn::apply(h0, params, steps, options);
-}
-
-struct PiStepBatchedFn : public torch::autograd::Function<PiStepBatchedFn> {
-    static Tensor forward(AutogradContext* ctx, const Tensor& h, const Tensor& params, std::string options)
-    {
-        at::AutoDispatchBelowADInplaceOrView below;
-        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("percnn::pi_step_batched", "")
-                             .typed<Tensor(const Tensor&, const Tensor&, std::string)>();
-        Tensor out = op.call(h, params, options);
-        ctx->save_for_backward({h, params});
-        ctx->saved_data["options"] = options;
-        return out;
-    }
-    static variable_list backward(AutogradContext* ctx, variable_list grads)
-    {
-        const auto saved = ctx->get_saved_variables();
-        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("percnn::pi_step_batched_backward", "")
-                             .typed<std::tuple<Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, std::string)>();
-        auto [g_in, g_p] = op.call(saved[0], saved[1], grads[0], ctx->saved_data["options"].toStringRef());
-        return {g_in, g_p, Tensor()};
-    }
-};
-Tensor pi_step_batched_autograd(const Tensor& h, const Tensor& params, std::string options)
-{
-    return PiStepBatchedFn::apply(h, params, options);
-}
-
-struct PiRolloutBatchedFn : public torch::autograd::Function<PiRolloutBatchedFn> {
-    static Tensor forward(AutogradContext* ctx, const Tensor& h0, const Tensor& params, int64_t steps, std::string options)
-    {
-        at::AutoDispatchBelowADInplaceOrView below;
-        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("percnn::pi_rollout_batched", "")
-                             .typed<Tensor(const Tensor&, const Tensor&, int64_t, std::string)>();
-        Tensor traj = op.call(h0, params, steps, options);
-        ctx->save_for_backward({traj, params});
-        ctx->saved_data["options"] = options;
-        return traj;
-    }
-    static variable_list backward(AutogradContext* ctx, variable_list grads)
-    {
-        const auto saved = ctx->get_saved_variables();
-        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("percnn::pi_rollout_batched_backward", "")
-                             .typed<std::tuple<Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, std::string)>();
-        auto [g_h0, g_p] = op.call(saved[0], saved[1], grads[0], ctx->saved_data["options"].toStringRef());
-        return {g_h0, g_p, Tensor(), Tensor()};
-    }
-};
-Tensor pi_rollout_batched_autograd(const Tensor& h0, const Tensor& params, int64_t steps, std::string options)
-{
-    return PiRolloutBatchedFn::apply(h0, params, steps, options);
-}
-
-struct PiStepEnsembleFn : public torch::autograd::Function<PiStepEnsembleFn> {
-    static Tensor forward(AutogradContext* ctx, const Tensor& h, const Tensor& params, std::string options)
-    {
-        at::AutoDispatchBelowADInplaceOrView below;
-        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("percnn::pi_step_ensemble", "")
-                             .typed<Tensor(const Tensor&, const Tensor&, std::string)>();
-        Tensor out = op.call(h, params, options);
-        ctx->save_for_backward({h, params});
-        ctx->saved_data["options"] = options;
-        return out;
-    }
-    static variable_list backward(AutogradContext* ctx, variable_list grads)
-    {
-        const auto saved = ctx->get_saved_variables();
-        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("percnn::pi_step_ensemble_backward", "")
-                             .typed<std::tuple<Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, std::string)>();
-        auto [g_in, g_p] = op.call(saved[0], saved[1], grads[0], ctx->saved_data["options"].toStringRef());
-        return {g_in, g_p, Tensor()};
-    }
-};
-Tensor pi_step_ensemble_autograd(const Tensor& h, const Tensor& params, std::string options)
-{
-    return PiStepEnsembleFn::apply(h, params, options);
-}
-
-struct PiRolloutEnsembleFn : public torch::autograd::Function<PiRolloutEnsembleFn> {
-    static Tensor forward(AutogradContext* ctx, const Tensor& h0, const Tensor& params, int64_t steps, std::string options)
-    {
-        at::AutoDispatchBelowADInplaceOrView below;
-        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("percnn::pi_rollout_ensemble", "")
-                             .typed<Tensor(const Tensor&, const Tensor&, int64_t, std::string)>();
-        Tensor traj = op.call(h0, params, steps, options);
-        ctx->save_for_backward({traj, params});
-        ctx->saved_data["options"] = options;
-        return traj;
-    }
-    static variable_list backward(AutogradContext* ctx, variable_list grads)
-    {
-        const auto saved = ctx->get_saved_variables();
-        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("percnn::pi_rollout_ensemble_backward", "")
-                             .typed<std::tuple<Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, std::string)>();
-        auto [g_h0, g_p] = op.call(saved[0], saved[1], grads[0], ctx->saved_data["options"].toStringRef());
-        return {g_h0, g_p, Tensor(), Tensor()};
-    }
-};
-Tensor pi_rollout_ensemble_autograd(const Tensor& h0, const Tensor& params, int64_t steps, std::string options)
-{
-    return PiRolloutEnsembleFn::apply(h0, params, steps, options);
+    return PiRolloutFn<F>::apply(h0, params, steps, options);
 }
 
 // ---- eager fast path of a reference-style step loop -----------------------------------------------------------------------
@@ -666,12 +491,10 @@ struct GradSink : torch::CustomClassHolder {
     void flush_rows(void* st)                                // rows -> acc (one launch); the next step launch resets the rows
     {
         if (!rows_dirty) return;
-        int rc;
-        if (ws_dtype == at::kFloat)
-            rc = percnn_pi_bwd_rows_finish_f32(ws.mutable_data_ptr(), (size_t)ws.numel(), ws_hc, ws_ndim, ws_shape, acc.mutable_data_ptr<double>(), st);
-        else
-            rc = percnn_pi_bwd_rows_finish_f64(ws.mutable_data_ptr(), (size_t)ws.numel(), ws_hc, ws_ndim, ws_shape, acc.mutable_data_ptr<double>(), st);
-        check(rc, "bwd_rows_finish");
+        check(with_dtype(ws_dtype, [&](auto tag) {
+                  return Abi<decltype(tag)>::bwd_rows_finish(ws.mutable_data_ptr(), (size_t)ws.numel(), ws_hc, ws_ndim, ws_shape,
+                                                             acc.mutable_data_ptr<double>(), st);
+              }), "bwd_rows_finish");
         rows_dirty = false;
         acc_dirty = true;
     }
@@ -701,14 +524,12 @@ struct GradSink : torch::CustomClassHolder {
         }
         Tensor g_in = at::empty_like(h);
         const int flags = rows_dirty ? PERCNN_PI_NO_RESET : 0;
-        int rc;
-        if (h.scalar_type() == at::kFloat)
-            rc = percnn_pi_step_bwd_rows_f32(h.const_data_ptr<float>(), g.const_data_ptr<float>(), nullptr, g_in.mutable_data_ptr<float>(),
-                                             ws.mutable_data_ptr(), (size_t)ws.numel(), P.const_data_ptr<float>(), hc, sh.ndim, sh.s, flags, st);
-        else
-            rc = percnn_pi_step_bwd_rows_f64(h.const_data_ptr<double>(), g.const_data_ptr<double>(), nullptr, g_in.mutable_data_ptr<double>(),
-                                             ws.mutable_data_ptr(), (size_t)ws.numel(), P.const_data_ptr<double>(), hc, sh.ndim, sh.s, flags, st);
-        check(rc, "step_bwd");
+        check(with_dtype(h, [&](auto tag) {
+                  using T = decltype(tag);
+                  return Abi<T>::step_bwd_rows(h.const_data_ptr<T>(), g.const_data_ptr<T>(), nullptr, g_in.mutable_data_ptr<T>(),
+                                               ws.mutable_data_ptr(), (size_t)ws.numel(), P.const_data_ptr<T>(), hc, sh.ndim, sh.s,
+                                               flags, st);
+              }), "step_bwd");
         rows_dirty = true;
         return g_in;
     }
@@ -814,12 +635,10 @@ struct BlockState : torch::CustomClassHolder {
         const int hc = hc_of(P);
         void* st = stream_of(h);
         char* base = static_cast<char*>(chunk.mutable_data_ptr()) + from * chunk.stride(0) * (int64_t)chunk.element_size();
-        int rc;
-        if (h.scalar_type() == at::kFloat)
-            rc = percnn_pi_rollout_fwd_opt_f32(reinterpret_cast<float*>(base), P.const_data_ptr<float>(), hc, sh.ndim, sh.s, (int)want, nullptr, st);
-        else
-            rc = percnn_pi_rollout_fwd_opt_f64(reinterpret_cast<double*>(base), P.const_data_ptr<double>(), hc, sh.ndim, sh.s, (int)want, nullptr, st);
-        check(rc, "rollout_fwd");
+        check(with_dtype(h, [&](auto tag) {
+                  using T = decltype(tag);
+                  return Abi<T>::rollout_fwd(reinterpret_cast<T*>(base), P.const_data_ptr<T>(), hc, sh.ndim, sh.s, (int)want, nullptr, st);
+              }), "rollout_fwd");
         variable_list outs;
         outs.reserve((size_t)want);
         for (int64_t i = from + 1; i <= from + want; ++i) outs.push_back(frame_tensor(i));
@@ -832,14 +651,10 @@ struct BlockState : torch::CustomClassHolder {
         void* st = stream_of(h);
         new_chunk(h, true);
         char* o = static_cast<char*>(chunk.mutable_data_ptr()) + chunk.stride(0) * (int64_t)chunk.element_size();
-        int rc;
-        if (h.scalar_type() == at::kFloat)
-            rc = percnn_pi_step_fwd_opt_f32(h.const_data_ptr<float>(), reinterpret_cast<float*>(o), P.const_data_ptr<float>(), hc, sh.ndim,
-                                            sh.s, nullptr, st);
-        else
-            rc = percnn_pi_step_fwd_opt_f64(h.const_data_ptr<double>(), reinterpret_cast<double*>(o), P.const_data_ptr<double>(), hc, sh.ndim,
-                                            sh.s, nullptr, st);
-        check(rc, "step_fwd");
+        check(with_dtype(h, [&](auto tag) {
+                  using T = decltype(tag);
+                  return Abi<T>::step_fwd(h.const_data_ptr<T>(), reinterpret_cast<T*>(o), P.const_data_ptr<T>(), hc, sh.ndim, sh.s, nullptr, st);
+              }), "step_fwd");
         return frame_tensor(1);
     }
     // one forward step of a loop; h, P contiguous; record: autograd is recording for this call
@@ -1004,18 +819,13 @@ struct GroupStepFn : public torch::autograd::Function<GroupStepFn> {
         }
         // (short sweeps: the launch-per-group tile sweep; the persistent flavour pays a host handshake per call)
         const char* sweep_opts = "tile_persist=0";
-        int rc;
-        if (h.scalar_type() == at::kFloat)
-            rc = percnn_pi_rollout_bwd_top_f32(base.const_data_ptr<float>(), reinterpret_cast<const float*>(gptr),
-                                               g_top.const_data_ptr<float>(), mask.data(), g_h.mutable_data_ptr<float>(),
-                                               pg.mutable_data_ptr<double>(), ws.mutable_data_ptr(), nbytes, P.const_data_ptr<float>(), hc,
-                                               sh.ndim, sh.s, (int)T, sweep_opts, st);
-        else
-            rc = percnn_pi_rollout_bwd_top_f64(base.const_data_ptr<double>(), reinterpret_cast<const double*>(gptr),
-                                               g_top.const_data_ptr<double>(), mask.data(), g_h.mutable_data_ptr<double>(),
-                                               pg.mutable_data_ptr<double>(), ws.mutable_data_ptr(), nbytes, P.const_data_ptr<double>(), hc,
-                                               sh.ndim, sh.s, (int)T, sweep_opts, st);
-        check(rc, "rollout_bwd");
+        check(with_dtype(h, [&](auto tag) {
+                  using E = decltype(tag);
+                  return Abi<E>::rollout_bwd_top(base.const_data_ptr<E>(), reinterpret_cast<const E*>(gptr), g_top.const_data_ptr<E>(),
+                                                 mask.data(), g_h.mutable_data_ptr<E>(), pg.mutable_data_ptr<double>(),
+                                                 ws.mutable_data_ptr(), nbytes, P.const_data_ptr<E>(), hc, sh.ndim, sh.s, (int)T,
+                                                 sweep_opts, st);
+              }), "rollout_bwd");
         return {g_h, Tensor(), Tensor(), Tensor(), Tensor()};
     }
 };
@@ -1174,47 +984,34 @@ TORCH_LIBRARY_FRAGMENT(percnn, m)
     m.class_<BlockState>("BlockState").def(torch::init<Tensor>());
 }
 
-TORCH_LIBRARY_IMPL(percnn, CUDA, m)
+// the twelve implementations, registered under two keys: CUDA (HIP tensors carry the CUDA dispatch key on PyTorch-ROCm) and CPU,
+// where every one of them fails loudly in require() -- there is no CPU path -- with the package's message instead of the dispatcher's
+static void register_impls(torch::Library& m)
 {
     m.impl("pi_step", pi_step_impl);
     m.impl("pi_step_backward", pi_step_backward_impl);
     m.impl("pi_rollout", pi_rollout_impl);
     m.impl("pi_rollout_backward", pi_rollout_backward_impl);
-    m.impl("pi_step_batched", pi_step_batched_impl);
-    m.impl("pi_step_batched_backward", pi_step_batched_backward_impl);
-    m.impl("pi_rollout_batched", pi_rollout_batched_impl);
-    m.impl("pi_rollout_batched_backward", pi_rollout_batched_backward_impl);
-    m.impl("pi_step_ensemble", pi_step_ensemble_impl);
-    m.impl("pi_step_ensemble_backward", pi_step_ensemble_backward_impl);
-    m.impl("pi_rollout_ensemble", pi_rollout_ensemble_impl);
-    m.impl("pi_rollout_ensemble_backward", pi_rollout_ensemble_backward_impl);
+    m.impl("pi_step_batched", pi_step_samples<Batched>);
+    m.impl("pi_step_batched_backward", pi_step_samples_backward<Batched>);
+    m.impl("pi_rollout_batched", pi_rollout_samples<Batched>);
+    m.impl("pi_rollout_batched_backward", pi_rollout_samples_backward<Batched>);
+    m.impl("pi_step_ensemble", pi_step_samples<Ensemble>);
+    m.impl("pi_step_ensemble_backward", pi_step_samples_backward<Ensemble>);
+    m.impl("pi_rollout_ensemble", pi_rollout_samples<Ensemble>);
+    m.impl("pi_rollout_ensemble_backward", pi_rollout_samples_backward<Ensemble>);
 }
-
-// CPU tensors fail loudly (there is no CPU path), with the package's message instead of the dispatcher's
-TORCH_LIBRARY_IMPL(percnn, CPU, m)
-{
-    m.impl("pi_step", pi_step_impl);
-    m.impl("pi_step_backward", pi_step_backward_impl);
-    m.impl("pi_rollout", pi_rollout_impl);
-    m.impl("pi_rollout_backward", pi_rollout_backward_impl);
-    m.impl("pi_step_batched", pi_step_batched_impl);
-    m.impl("pi_step_batched_backward", pi_step_batched_backward_impl);
-    m.impl("pi_rollout_batched", pi_rollout_batched_impl);
-    m.impl("pi_rollout_batched_backward", pi_rollout_batched_backward_impl);
-    m.impl("pi_step_ensemble", pi_step_ensemble_impl);
-    m.impl("pi_step_ensemble_backward", pi_step_ensemble_backward_impl);
-    m.impl("pi_rollout_ensemble", pi_rollout_ensemble_impl);
-    m.impl("pi_rollout_ensemble_backward", pi_rollout_ensemble_backward_impl);
-}
+TORCH_LIBRARY_IMPL(percnn, CUDA, m) { register_impls(m); }
+TORCH_LIBRARY_IMPL(percnn, CPU, m) { register_impls(m); }
 
 TORCH_LIBRARY_IMPL(percnn, Autograd, m)
 {
-    m.impl("pi_step", pi_step_autograd);
-    m.impl("pi_rollout", pi_rollout_autograd);
-    m.impl("pi_step_batched", pi_step_batched_autograd);
-    m.impl("pi_rollout_batched", pi_rollout_batched_autograd);
-    m.impl("pi_step_ensemble", pi_step_ensemble_autograd);
-    m.impl("pi_rollout_ensemble", pi_rollout_ensemble_autograd);
+    m.impl("pi_step", pi_step_autograd<Single>);
+    m.impl("pi_rollout", pi_rollout_autograd<Single>);
+    m.impl("pi_step_batched", pi_step_autograd<Batched>);
+    m.impl("pi_rollout_batched", pi_rollout_autograd<Batched>);
+    m.impl("pi_step_ensemble", pi_step_autograd<Ensemble>);
+    m.impl("pi_rollout_ensemble", pi_rollout_autograd<Ensemble>);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)

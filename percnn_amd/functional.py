@@ -583,14 +583,23 @@ def pi_rollout_sqerr(h0: torch.Tensor, P: torch.Tensor, steps: int, target: Opti
 
 
 # ---- the same loss per sample of a batch (one block) / an ensemble (one block per sample): [B] losses, one autograd node ----
-def traj_sqerr_batched(traj: torch.Tensor, target: Optional[torch.Tensor] = None, frame_mask: Optional[Sequence[bool]] = None,
-                       scale: float = 1.0) -> torch.Tensor:
-    """traj / target [F,B,2,*S] -> [B] of traj's dtype: scale * sum over the frames with frame_mask[f] of sum_x (traj[f,b] -
-    target[f,b])^2, one streaming pass and one fixed-order sum per sample (``percnn_pi_batch_traj_sqerr_*``; target None = 0)."""
-    _require(traj, "traj")
+def _strides_arg(strides):
+    return (ctypes.c_int * len(strides))(*[int(x) for x in strides])
+
+
+def _check_target(target, traj, frame_mask, strides):
+    """the target of a per-sample loss: of the trajectory's shape (strides None: dense) or compact in time and space"""
+    if strides is not None:
+        return _check_compact(target, traj, frame_mask, strides)
     if target is not None:
         _require(target, "target", traj.dtype)
         assert target.shape == traj.shape
+
+
+def _traj_loss_samples(traj, target, frame_mask, strides, scale):
+    """``traj_sqerr_batched`` (strides None) and ``traj_obs_sqerr_batched``: one streaming pass, one fixed-order sum per sample"""
+    _require(traj, "traj")
+    _check_target(target, traj, frame_mask, strides)
     B, shape = int(traj.shape[1]), traj.shape[3:]
     L = _lib.lib()
     nbytes = L.percnn_pi_batch_traj_sqerr_workspace_bytes(B)
@@ -598,31 +607,30 @@ def traj_sqerr_batched(traj: torch.Tensor, target: Optional[torch.Tensor] = None
         raise RuntimeError(f"percnn_amd: invalid batch size {B}")
     out = torch.empty(B, dtype=traj.dtype, device=traj.device)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=traj.device)
-    f = getattr(L, "percnn_pi_batch_traj_sqerr_" + _SUF[traj.dtype])
+    what = "batch_traj_sqerr" if strides is None else "batch_traj_obs_sqerr"
+    lattice = () if strides is None else (_strides_arg(strides),)
+    f = getattr(L, f"percnn_pi_{what}_" + _SUF[traj.dtype])
     with torch.cuda.device(traj.device):
         _lib.check(f(traj.data_ptr(), target.data_ptr() if target is not None else None, _mask_bytes(frame_mask, traj.shape[0]),
-                     traj.shape[0], len(shape), _lib.shape_arg(shape), B, float(scale), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                     _stream()), "batch_traj_sqerr")
+                     traj.shape[0], len(shape), _lib.shape_arg(shape), *lattice, B, float(scale), out.data_ptr(), ws.data_ptr(),
+                     ws.numel(), _stream()), what)
     return out
 
 
-def rollout_bwd_sqerr_batched(traj: torch.Tensor, P: torch.Tensor, target: Optional[torch.Tensor] = None,
-                              frame_mask: Optional[Sequence[bool]] = None, scale: float = 1.0,
-                              dev_scale: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None, options=None,
-                              g_h0: Optional[torch.Tensor] = None):
-    """Backward of the B losses  L_b = (scale / 2) * sum_{t in mask} sum_x (traj[t,b] - target[t,b])^2, each times its own
-    factor ``dev_scale[b]`` (a [B] device tensor, None = 1), WITHOUT a dL/dtraj buffer (``percnn_pi_{batch,ensemble}_rollout_
-    bwd_sqerr_*``).  traj / target [T+1,B,2,*S]; P [np]: one block -> (dL/dh0 [B,2,*S], double [np] summed over the samples);
-    P [B,np]: one block per sample -> (dL/dh0, double [B,np])."""
+def _rollout_bwd_loss_samples(traj, P, target, frame_mask, strides, scale, dev_scale, ws, options, g_h0, ensemble=None):
+    """``rollout_bwd_sqerr_batched`` (strides None) and ``rollout_bwd_obs_sqerr_batched``: the batched / ensemble sweep with the
+    loss gradient formed in-kernel."""
     _require(traj, "traj"); _require(P, "params", traj.dtype)
-    if target is not None:
-        _require(target, "target", traj.dtype)
-        assert target.shape == traj.shape
+    _check_target(target, traj, frame_mask, strides)
     T, B, shape = traj.shape[0] - 1, int(traj.shape[1]), traj.shape[3:]
-    kind = "ensemble" if P.dim() == 2 else "batch"
-    if kind == "ensemble" and P.shape[0] != B:
+    if ensemble is None:
+        ensemble = P.dim() == 2
+    if strides is not None and P.dim() != (2 if ensemble else 1):    # (the dense form leaves a block of another rank to _hc_of)
+        raise ValueError(f"{'one parameter block per sample [B,np]' if ensemble else 'one parameter block [np]'}, got {tuple(P.shape)}")
+    kind = "ensemble" if ensemble else "batch"
+    if ensemble and P.shape[0] != B:
         raise ValueError(f"one parameter block per sample: P [{B},np], got {tuple(P.shape)}")
-    hc = _hc_of(P[0] if kind == "ensemble" else P)
+    hc = _hc_of(P[0] if ensemble else P)
     if dev_scale is not None:
         dev_scale = dev_scale.reshape(B).to(traj.dtype).contiguous()
     L = _lib.lib()
@@ -635,30 +643,47 @@ def rollout_bwd_sqerr_batched(traj: torch.Tensor, P: torch.Tensor, target: Optio
         if nbytes == 0:
             raise RuntimeError("percnn_amd: invalid problem shape, batch size or block kind")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=traj.device)
-    f = getattr(L, f"percnn_pi_{kind}_rollout_bwd_sqerr_" + _SUF[traj.dtype])
+    what = f"{kind}_rollout_bwd_sqerr" if strides is None else f"{kind}_rollout_bwd_obs_sqerr"
+    lattice = () if strides is None else (_strides_arg(strides),)
+    f = getattr(L, f"percnn_pi_{what}_" + _SUF[traj.dtype])
     with torch.cuda.device(traj.device):
-        _lib.check(f(traj.data_ptr(), target.data_ptr() if target is not None else None, _mask_bytes(frame_mask, T + 1),
+        _lib.check(f(traj.data_ptr(), target.data_ptr() if target is not None else None, _mask_bytes(frame_mask, T + 1), *lattice,
                      float(scale), dev_scale.data_ptr() if dev_scale is not None else None, g_h0.data_ptr(), pg.data_ptr(),
                      ws.data_ptr(), ws.numel(), P.data_ptr(), hc, len(shape), _lib.shape_arg(shape), B, T,
-                     _lib.options_arg(options), _stream()), f"{kind}_rollout_bwd_sqerr")
+                     _lib.options_arg(options), _stream()), what)
     return g_h0, pg
 
 
-class PiRolloutSqErrBatchedFunction(torch.autograd.Function):
-    """``PiRolloutSqErrFunction`` for B trajectories: loss[b] = weight * sum_{t in frames} sum_x (h_t[b] - target_t[b])^2, a
-    [B] tensor, as ONE autograd node.  Forward = the batched (P [np]) or ensemble (P [B,np]) rollout + one streaming
-    reduction per sample; backward = the sweep with the incoming [B] gradient as per-sample factors, the loss gradient formed
-    in-kernel -- no dL/dtraj [T+1,B,2,*S], no host synchronisation.  Returns (loss, traj); traj is not differentiable."""
+def traj_sqerr_batched(traj: torch.Tensor, target: Optional[torch.Tensor] = None, frame_mask: Optional[Sequence[bool]] = None,
+                       scale: float = 1.0) -> torch.Tensor:
+    """traj / target [F,B,2,*S] -> [B] of traj's dtype: scale * sum over the frames with frame_mask[f] of sum_x (traj[f,b] -
+    target[f,b])^2, one streaming pass and one fixed-order sum per sample (``percnn_pi_batch_traj_sqerr_*``; target None = 0)."""
+    return _traj_loss_samples(traj, target, frame_mask, None, scale)
+
+
+def rollout_bwd_sqerr_batched(traj: torch.Tensor, P: torch.Tensor, target: Optional[torch.Tensor] = None,
+                              frame_mask: Optional[Sequence[bool]] = None, scale: float = 1.0,
+                              dev_scale: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None, options=None,
+                              g_h0: Optional[torch.Tensor] = None):
+    """Backward of the B losses  L_b = (scale / 2) * sum_{t in mask} sum_x (traj[t,b] - target[t,b])^2, each times its own
+    factor ``dev_scale[b]`` (a [B] device tensor, None = 1), WITHOUT a dL/dtraj buffer (``percnn_pi_{batch,ensemble}_rollout_
+    bwd_sqerr_*``).  traj / target [T+1,B,2,*S]; P [np]: one block -> (dL/dh0 [B,2,*S], double [np] summed over the samples);
+    P [B,np]: one block per sample -> (dL/dh0, double [B,np])."""
+    return _rollout_bwd_loss_samples(traj, P, target, frame_mask, None, scale, dev_scale, ws, options, g_h0)
+
+
+class _PiRolloutLossSamplesFunction(torch.autograd.Function):
+    """The node of ``PiRolloutSqErrBatchedFunction`` (strides None: dense) and ``PiRolloutObsSqErrBatchedFunction``."""
 
     @staticmethod
-    def forward(ctx, h0, P, steps, target, frame_mask, weight, options):
+    def forward(ctx, h0, P, steps, target, frame_mask, strides, weight, options):
         _native()
         P = P.contiguous()
         op = torch.ops.percnn.pi_rollout_ensemble if P.dim() == 2 else torch.ops.percnn.pi_rollout_batched
         traj = op(h0, P, steps, _options_str(options))
-        loss = traj_sqerr_batched(traj, target, frame_mask, weight)
+        loss = _traj_loss_samples(traj, target, frame_mask, strides, weight)
         ctx.save_for_backward(traj, P) if target is None else ctx.save_for_backward(traj, P, target)
-        ctx.meta = (frame_mask, float(weight), options)
+        ctx.meta = (frame_mask, strides, float(weight), options)
         ctx.mark_non_differentiable(traj)
         ctx.set_materialize_grads(False)
         return loss, traj
@@ -666,13 +691,25 @@ class PiRolloutSqErrBatchedFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_traj):
         if g_loss is None:
-            return None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None
         saved = ctx.saved_tensors
         traj, P = saved[0], saved[1]
         target = saved[2] if len(saved) > 2 else None
-        frame_mask, weight, options = ctx.meta
-        g_h0, pg = rollout_bwd_sqerr_batched(traj, P, target, frame_mask, 2.0 * weight, g_loss.contiguous(), options=options)
-        return g_h0, pg.to(P.dtype), None, None, None, None, None
+        frame_mask, strides, weight, options = ctx.meta
+        g_h0, pg = _rollout_bwd_loss_samples(traj, P, target, frame_mask, strides, 2.0 * weight, g_loss.contiguous(), None,
+                                             options, None)
+        return g_h0, pg.to(P.dtype), None, None, None, None, None, None
+
+
+class PiRolloutSqErrBatchedFunction(_PiRolloutLossSamplesFunction):
+    """``PiRolloutSqErrFunction`` for B trajectories: loss[b] = weight * sum_{t in frames} sum_x (h_t[b] - target_t[b])^2, a
+    [B] tensor, as ONE autograd node.  Forward = the batched (P [np]) or ensemble (P [B,np]) rollout + one streaming
+    reduction per sample; backward = the sweep with the incoming [B] gradient as per-sample factors, the loss gradient formed
+    in-kernel -- no dL/dtraj [T+1,B,2,*S], no host synchronisation.  Returns (loss, traj); traj is not differentiable."""
+
+    @classmethod
+    def apply(cls, h0, P, steps, target, frame_mask, weight, options):         # the dense form takes no strides
+        return super().apply(h0, P, steps, target, frame_mask, None, weight, options)
 
 
 def _pi_rollout_sqerr_samples(what, h0, P, steps, target, frames, reduction, options):
@@ -736,10 +773,6 @@ def obs_selection(steps: int, t_idx: Sequence[int], strides, shape: Sequence[int
     return sel, mask, strides, Sc, weight
 
 
-def _strides_arg(strides):
-    return (ctypes.c_int * len(strides))(*[int(x) for x in strides])
-
-
 def _check_compact(target, traj, frame_mask, strides):
     F, B, shape = traj.shape[0], int(traj.shape[1]), traj.shape[3:]
     n = F if frame_mask is None else sum(1 for m in frame_mask if m)
@@ -757,21 +790,7 @@ def traj_obs_sqerr_batched(traj: torch.Tensor, target: Optional[torch.Tensor] = 
                            frame_mask: Optional[Sequence[bool]] = None, strides: Sequence[int] = (), scale: float = 1.0) -> torch.Tensor:
     """traj [F,B,2,*S], target [n,B,2,*Sc] compact in time and space (None = 0) -> [B] of traj's dtype: scale * sum over the
     frames with frame_mask[f] and the lattice points x_d % s_d == 0 of (traj - target)^2 (``percnn_pi_batch_traj_obs_sqerr_*``)."""
-    _require(traj, "traj")
-    _check_compact(target, traj, frame_mask, strides)
-    B, shape = int(traj.shape[1]), traj.shape[3:]
-    L = _lib.lib()
-    nbytes = L.percnn_pi_batch_traj_sqerr_workspace_bytes(B)
-    if nbytes == 0:
-        raise RuntimeError(f"percnn_amd: invalid batch size {B}")
-    out = torch.empty(B, dtype=traj.dtype, device=traj.device)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=traj.device)
-    f = getattr(L, "percnn_pi_batch_traj_obs_sqerr_" + _SUF[traj.dtype])
-    with torch.cuda.device(traj.device):
-        _lib.check(f(traj.data_ptr(), target.data_ptr() if target is not None else None, _mask_bytes(frame_mask, traj.shape[0]),
-                     traj.shape[0], len(shape), _lib.shape_arg(shape), _strides_arg(strides), B, float(scale), out.data_ptr(),
-                     ws.data_ptr(), ws.numel(), _stream()), "batch_traj_obs_sqerr")
-    return out
+    return _traj_loss_samples(traj, target, frame_mask, strides, scale)
 
 
 def rollout_bwd_obs_sqerr_batched(traj: torch.Tensor, P: torch.Tensor, target: Optional[torch.Tensor] = None,
@@ -781,69 +800,15 @@ def rollout_bwd_obs_sqerr_batched(traj: torch.Tensor, P: torch.Tensor, target: O
     """``rollout_bwd_sqerr_batched`` for the loss on the lattice of the selected frames against the compact target
     [n,B,2,*Sc] (``percnn_pi_{batch,ensemble}_rollout_bwd_obs_sqerr_*``): no dL/dtraj, no scatter of the observed frames.
     ensemble: None = by the rank of P ([np] / [B,np]).  B = 1 runs the same launches with one sample."""
-    _require(traj, "traj"); _require(P, "params", traj.dtype)
-    _check_compact(target, traj, frame_mask, strides)
-    T, B, shape = traj.shape[0] - 1, int(traj.shape[1]), traj.shape[3:]
-    if ensemble is None:
-        ensemble = P.dim() == 2
-    if P.dim() != (2 if ensemble else 1):
-        raise ValueError(f"{'one parameter block per sample [B,np]' if ensemble else 'one parameter block [np]'}, got {tuple(P.shape)}")
-    kind = "ensemble" if ensemble else "batch"
-    if ensemble and P.shape[0] != B:
-        raise ValueError(f"one parameter block per sample: P [{B},np], got {tuple(P.shape)}")
-    hc = _hc_of(P[0] if ensemble else P)
-    if dev_scale is not None:
-        dev_scale = dev_scale.reshape(B).to(traj.dtype).contiguous()
-    L = _lib.lib()
-    if g_h0 is None:
-        g_h0 = torch.empty_like(traj[0])
-    pg = torch.zeros(tuple(P.shape), dtype=torch.float64, device=traj.device)
-    if ws is None:
-        nbytes = getattr(L, f"percnn_pi_{kind}_rollout_bwd_workspace_bytes")(hc, len(shape), _lib.shape_arg(shape), B, T,
-                                                                            traj.dtype.itemsize)
-        if nbytes == 0:
-            raise RuntimeError("percnn_amd: invalid problem shape, batch size or block kind")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=traj.device)
-    f = getattr(L, f"percnn_pi_{kind}_rollout_bwd_obs_sqerr_" + _SUF[traj.dtype])
-    with torch.cuda.device(traj.device):
-        _lib.check(f(traj.data_ptr(), target.data_ptr() if target is not None else None, _mask_bytes(frame_mask, T + 1),
-                     _strides_arg(strides), float(scale), dev_scale.data_ptr() if dev_scale is not None else None,
-                     g_h0.data_ptr(), pg.data_ptr(), ws.data_ptr(), ws.numel(), P.data_ptr(), hc, len(shape),
-                     _lib.shape_arg(shape), B, T, _lib.options_arg(options), _stream()), f"{kind}_rollout_bwd_obs_sqerr")
-    return g_h0, pg
+    return _rollout_bwd_loss_samples(traj, P, target, frame_mask, strides, scale, dev_scale, ws, options, g_h0, ensemble)
 
 
-class PiRolloutObsSqErrBatchedFunction(torch.autograd.Function):
+class PiRolloutObsSqErrBatchedFunction(_PiRolloutLossSamplesFunction):
     """``PiRolloutSqErrBatchedFunction`` on sparse observations: loss[b] = weight * sum_k sum over the lattice of
     (h_{t_k}[b] - target[k, b])^2, a [B] tensor, as ONE autograd node.  Forward = the batched (P [np]) or ensemble (P [B,np])
     rollout + one reduction per sample over the lattice; backward = the sweep with the incoming [B] gradient as per-sample
     factors, the loss gradient formed in-kernel at the lattice points -- no dL/dtraj [T+1,B,2,*S], no scatter, no host
     synchronisation.  Returns (loss, traj); traj is not differentiable."""
-
-    @staticmethod
-    def forward(ctx, h0, P, steps, target, frame_mask, strides, weight, options):
-        _native()
-        P = P.contiguous()
-        op = torch.ops.percnn.pi_rollout_ensemble if P.dim() == 2 else torch.ops.percnn.pi_rollout_batched
-        traj = op(h0, P, steps, _options_str(options))
-        loss = traj_obs_sqerr_batched(traj, target, frame_mask, strides, weight)
-        ctx.save_for_backward(traj, P) if target is None else ctx.save_for_backward(traj, P, target)
-        ctx.meta = (frame_mask, strides, float(weight), options)
-        ctx.mark_non_differentiable(traj)
-        ctx.set_materialize_grads(False)
-        return loss, traj
-
-    @staticmethod
-    def backward(ctx, g_loss, _g_traj):
-        if g_loss is None:
-            return None, None, None, None, None, None, None, None
-        saved = ctx.saved_tensors
-        traj, P = saved[0], saved[1]
-        target = saved[2] if len(saved) > 2 else None
-        frame_mask, strides, weight, options = ctx.meta
-        g_h0, pg = rollout_bwd_obs_sqerr_batched(traj, P, target, frame_mask, strides, 2.0 * weight, g_loss.contiguous(),
-                                                 options=options)
-        return g_h0, pg.to(P.dtype), None, None, None, None, None, None
 
 
 def _pi_rollout_obs_sqerr_samples(what, h0, P, steps, target, t_idx, strides, reduction, options):
@@ -1221,16 +1186,18 @@ def pi_rollout_frames(h0: torch.Tensor, P: torch.Tensor, steps: int, frames: Seq
 
 
 class PiRolloutBatchedFramesFunction(torch.autograd.Function):
-    """``PiRolloutFramesFunction`` for a batched initial state [B,2,*S]: one ``torch.ops.percnn.pi_rollout_batched`` call, the
-    frames are [B,2,*S] views of its [T+1,B,2,*S] buffer, the LAST output is that buffer as [(T+1)*B,2,*S] -- what
-    ``torch.cat(tuple(outputs), dim=0)`` of the batched frames is (train_2drd.py:394).  The backward runs ONE batched rollout
-    backward on the dense dL/dtraj."""
+    """``PiRolloutFramesFunction`` for a batched initial state [B,2,*S]: one ``torch.ops.percnn.pi_rollout_batched`` call (P [np]:
+    one block) or ``pi_rollout_ensemble`` call (P [B,np]: one block per sample), the frames are [B,2,*S] views of its
+    [T+1,B,2,*S] buffer, the LAST output is that buffer as [(T+1)*B,2,*S] -- what ``torch.cat(tuple(outputs), dim=0)`` of the
+    batched frames is (train_2drd.py:394).  The backward runs ONE batched or ensemble rollout backward on the dense dL/dtraj;
+    the parameter gradient has P's shape."""
 
     @staticmethod
     def forward(ctx, h0, P, steps, frames):
         _native()
         P = P.contiguous()
-        traj = torch.ops.percnn.pi_rollout_batched(h0, P, steps, "")
+        op = torch.ops.percnn.pi_rollout_ensemble if P.dim() == 2 else torch.ops.percnn.pi_rollout_batched
+        traj = op(h0, P, steps, "")
         ctx.save_for_backward(traj, P)
         ctx.frames = tuple(int(k) for k in frames)
         ctx.set_materialize_grads(False)
@@ -1257,53 +1224,17 @@ class PiRolloutBatchedFramesFunction(torch.autograd.Function):
         for k, g in zip(ctx.frames, grads):
             if g is not None:
                 g_traj[k].add_(g)
-        g_h0, pg = torch.ops.percnn.pi_rollout_batched_backward(traj, P, g_traj.contiguous(), "")
+        op = torch.ops.percnn.pi_rollout_ensemble_backward if P.dim() == 2 else torch.ops.percnn.pi_rollout_batched_backward
+        g_h0, pg = op(traj, P, g_traj.contiguous(), "")
         return g_h0, pg, None, None
+
+
+PiRolloutEnsembleFramesFunction = PiRolloutBatchedFramesFunction    # (one node: the rank of P chooses the operator)
 
 
 def pi_rollout_batched_frames(h0: torch.Tensor, P: torch.Tensor, steps: int, frames: Sequence[int], with_stacked: bool = False):
     out = PiRolloutBatchedFramesFunction.apply(h0, P, int(steps), tuple(frames))
     return out if with_stacked else out[:-1]
-
-
-class PiRolloutEnsembleFramesFunction(torch.autograd.Function):
-    """``PiRolloutBatchedFramesFunction`` with one parameter block per sample, P [B,np]: one
-    ``torch.ops.percnn.pi_rollout_ensemble`` call; frames and the stacked last output as there.  The backward runs ONE ensemble
-    rollout backward on the dense dL/dtraj and returns the [B,np] parameter gradient."""
-
-    @staticmethod
-    def forward(ctx, h0, P, steps, frames):
-        _native()
-        P = P.contiguous()
-        traj = torch.ops.percnn.pi_rollout_ensemble(h0, P, steps, "")
-        ctx.save_for_backward(traj, P)
-        ctx.frames = tuple(int(k) for k in frames)
-        ctx.set_materialize_grads(False)
-        views = traj.unbind(0)
-        outs = []
-        for k in ctx.frames:
-            f = views[k].as_subclass(Frame)
-            f._pi_index = k
-            outs.append(f)
-        return tuple(outs) + (traj.view((-1,) + tuple(traj.shape[2:])),)
-
-    @staticmethod
-    def backward(ctx, *grads):
-        traj, P = ctx.saved_tensors
-        g_stacked, grads = grads[-1], grads[:-1]
-        if g_stacked is None and all(g is None for g in grads):
-            return None, None, None, None
-        if g_stacked is not None:
-            g_traj = g_stacked.reshape(traj.shape)
-            if any(g is not None for g in grads):
-                g_traj = g_traj.clone()
-        else:
-            g_traj = torch.zeros_like(traj)
-        for k, g in zip(ctx.frames, grads):
-            if g is not None:
-                g_traj[k].add_(g)
-        g_h0, pg = torch.ops.percnn.pi_rollout_ensemble_backward(traj, P, g_traj.contiguous(), "")
-        return g_h0, pg, None, None
 
 
 def pi_rollout_ensemble_frames(h0: torch.Tensor, P: torch.Tensor, steps: int, frames: Sequence[int], with_stacked: bool = False):

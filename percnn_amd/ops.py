@@ -134,6 +134,39 @@ pack_block.register_autograd(_pack_bwd, setup_context=_pack_setup)
 # torch::autograd::Function registered on the Autograd key; dispatcher -> C-ABI launcher with no Python frame).  Here: loading
 # the library and the FakeTensor implementations (what torch.compile / opcheck trace with).
 # ------------------------------------------------------------------------------------------------
+def _check_ensemble(params, B):
+    torch._check(params.dim() == 2 and params.shape[0] == B,
+                 lambda: f"percnn_amd: ensemble parameter blocks must be [B,np] with B = {B}, got {tuple(params.shape)}")
+
+
+def _register_fakes(flavour: str) -> None:
+    """The fake implementations of pi_step / pi_rollout (+ backward) of one flavour: "" (h [1,2,*S], trajectory [T+1,2,*S]),
+    "_batched" (h [B,2,*S], trajectory [T+1,B,2,*S]) or "_ensemble" (as batched, with params and its gradient [B,np]).  A step
+    answers with the state's shape, a backward operator with the state's and the block's."""
+    single = flavour == ""
+    check = _check_ensemble if flavour == "_ensemble" else (lambda params, B: None)
+
+    def step(h, params, options=""):
+        check(params, h.shape[0])
+        return torch.empty_like(h, memory_format=torch.contiguous_format)
+
+    def step_backward(h, params, g_out, options=""):
+        check(params, h.shape[0])
+        return torch.empty_like(h, memory_format=torch.contiguous_format), torch.empty_like(params)
+
+    def rollout(h0, params, steps, options=""):
+        check(params, h0.shape[0])
+        return h0.new_empty((steps + 1,) + tuple(h0.shape[1:] if single else h0.shape))
+
+    def rollout_backward(traj, params, g_traj, options=""):
+        check(params, traj.shape[1])
+        return traj.new_empty(((1,) if single else ()) + tuple(traj.shape[1:])), torch.empty_like(params)
+
+    for name, fake in ((f"pi_step{flavour}", step), (f"pi_step{flavour}_backward", step_backward),
+                       (f"pi_rollout{flavour}", rollout), (f"pi_rollout{flavour}_backward", rollout_backward)):
+        torch.library.register_fake(f"{_lib_ns}::{name}", fake)
+
+
 _native_loaded = False
 
 
@@ -146,64 +179,8 @@ def load_native() -> None:
     from . import _lib
     _lib.torch_ext()
 
-    @torch.library.register_fake(f"{_lib_ns}::pi_step")
-    def _(h, params, options=""):
-        return torch.empty_like(h, memory_format=torch.contiguous_format)
-
-    @torch.library.register_fake(f"{_lib_ns}::pi_step_backward")
-    def _(h, params, g_out, options=""):
-        return torch.empty_like(h, memory_format=torch.contiguous_format), torch.empty_like(params)
-
-    @torch.library.register_fake(f"{_lib_ns}::pi_rollout")
-    def _(h0, params, steps, options=""):
-        return h0.new_empty((steps + 1,) + tuple(h0.shape[1:]))
-
-    @torch.library.register_fake(f"{_lib_ns}::pi_rollout_backward")
-    def _(traj, params, g_traj, options=""):
-        return traj.new_empty((1,) + tuple(traj.shape[1:])), torch.empty_like(params)
-
-    # batched: h [B,2,*S], trajectory [T+1,B,2,*S]
-    @torch.library.register_fake(f"{_lib_ns}::pi_step_batched")
-    def _(h, params, options=""):
-        return torch.empty_like(h, memory_format=torch.contiguous_format)
-
-    @torch.library.register_fake(f"{_lib_ns}::pi_step_batched_backward")
-    def _(h, params, g_out, options=""):
-        return torch.empty_like(h, memory_format=torch.contiguous_format), torch.empty_like(params)
-
-    @torch.library.register_fake(f"{_lib_ns}::pi_rollout_batched")
-    def _(h0, params, steps, options=""):
-        return h0.new_empty((steps + 1,) + tuple(h0.shape))
-
-    @torch.library.register_fake(f"{_lib_ns}::pi_rollout_batched_backward")
-    def _(traj, params, g_traj, options=""):
-        return traj.new_empty(tuple(traj.shape[1:])), torch.empty_like(params)
-
-    # ensembles: h [B,2,*S], params [B,np], trajectory [T+1,B,2,*S], parameter gradient [B,np]
-    def _check_ensemble(params, B):
-        torch._check(params.dim() == 2 and params.shape[0] == B,
-                     lambda: f"percnn_amd: ensemble parameter blocks must be [B,np] with B = {B}, got {tuple(params.shape)}")
-
-    @torch.library.register_fake(f"{_lib_ns}::pi_step_ensemble")
-    def _(h, params, options=""):
-        _check_ensemble(params, h.shape[0])
-        return torch.empty_like(h, memory_format=torch.contiguous_format)
-
-    @torch.library.register_fake(f"{_lib_ns}::pi_step_ensemble_backward")
-    def _(h, params, g_out, options=""):
-        _check_ensemble(params, h.shape[0])
-        return torch.empty_like(h, memory_format=torch.contiguous_format), torch.empty_like(params)
-
-    @torch.library.register_fake(f"{_lib_ns}::pi_rollout_ensemble")
-    def _(h0, params, steps, options=""):
-        _check_ensemble(params, h0.shape[0])
-        return h0.new_empty((steps + 1,) + tuple(h0.shape))
-
-    @torch.library.register_fake(f"{_lib_ns}::pi_rollout_ensemble_backward")
-    def _(traj, params, g_traj, options=""):
-        _check_ensemble(params, traj.shape[1])
-        return traj.new_empty(tuple(traj.shape[1:])), torch.empty_like(params)
-
+    for flavour in ("", "_batched", "_ensemble"):
+        _register_fakes(flavour)
     _native_loaded = True
 
 
