@@ -397,6 +397,17 @@ int direct_block(const Problem& p, const Geom& g, int vec)
     return p.opt.block;
 }
 
+// Which samples a launch covers ("batched rollouts" and "ensembles" further down); the default is the unbatched launch.
+// on: the launch takes the kernels' sample flavours (`long sample` stride, sample = grid y) -- for batch == 1 too, which the
+// sparse-observation form runs on them.  ens_rows = -1: one block P for every sample (batched); ens_rows >= 0: one block per
+// sample, P [B][np], and the partial rows of sample b at b * ens_rows (ensemble; 0 where a launch writes no partial rows).
+struct Samples {
+    int batch = 1;
+    int ens_rows = -1;
+    bool on = false;
+    bool ens() const { return ens_rows >= 0; }
+};
+
 // ---- kernel instantiation dispatch ------------------------------------------------------------
 // planes per workgroup pass of the direct 3D kernels (the RZ > 1 flavours exist for pre-contracted blocks on 16-byte lanes)
 // Measured on MI355X (profiles/r02_direct_kernel_option_sweeps.txt, us per step rz = 1 / 2 / 4): forward 384^3 363 / 312 /
@@ -473,48 +484,72 @@ hipError_t launch_bwd(const T* h, const T* G, const T* inj, T* Gp, double* parti
     return hipGetLastError();
 }
 
-// time-parallel weight gradients over steps (t_lo, t_hi]
+// workgroups of the time-parallel gradient pass over `steps` steps
+long wgrad_blocks(const Problem& p, long steps, int vec)
+{
+    const long total = steps * (p.n / vec);
+    long nb = (total + 256L * 16 - 1) / (256L * 16);          // >= 16 chunks per lane before adding blocks
+    if (nb > p.opt.wgrad_blocks) nb = p.opt.wgrad_blocks;
+    return nb < 1 ? 1 : nb;
+}
+
+// workgroups per sample of the ensemble gradient pass: wgrad_blocks' count for the steps of the whole batch, split over the
+// samples (the same number of workgroups and chunks per lane as the batched pass over the flattened frame index)
+long ens_wgrad_blocks(const Problem& p, int batch, int t_top, int vec)
+{
+    return (wgrad_blocks(p, (long)t_top * batch, vec) + batch - 1) / batch;
+}
+
+// time-parallel weight gradients over steps (t_lo, t_hi].  Samples count in the ensemble flavour alone (the batched sweep
+// flattens its samples into the frame index and runs the unbatched kernels): ONE launch per hidden-channel group covers the
+// steps (0, t_hi] of every sample, sample = grid y (moments) or z -- state frame t-1 and adjoint frame t of sample b at
+// (t-1) * B + b and t * B + b -- on ens_wgrad_blocks' workgroups per sample.
 template <typename T, int JC, int NS, int VEC>
 hipError_t launch_wgrad_pass(const T* traj, const T* adj, double* partials, const T* P, const Problem& p, int t_lo,
-                             int t_hi, int j0, unsigned nb, hipStream_t st)
+                             int t_hi, int j0, unsigned nb, hipStream_t st, const Samples& s)
 {
     const int block = 256;
     const size_t lds = (size_t)(block / pi::WAVE) * NS * (10 * JC + 1) * sizeof(T);
     const Geom g = make_geom(p);
     const long ss = p.slab ? g.ss : (long)p.n, off = p.slab ? (long)p.halo * g.s0 : 0;
-    hipLaunchKernelGGL((pi::pi_wgrad_kernel<T, JC, NS, VEC>), dim3(nb, NS == 2 ? 1 : 2), dim3(block), lds, st, traj,
-                       adj, partials, P, (long)p.n, ss, off, t_lo, t_hi, p.hc, j0);
-    return hipGetLastError();
+    auto go = [&](auto* k, auto... tail) {
+        hipLaunchKernelGGL(k, dim3(nb, NS == 2 ? 1 : 2, s.ens() ? (unsigned)s.batch : 1), dim3(block), lds, st, traj, adj, partials,
+                           P, (long)p.n, ss, off, t_lo, t_hi, p.hc, j0, tail...);
+        return hipGetLastError();
+    };
+    return s.ens() ? go(pi::pi_wgrad_kernel<T, JC, NS, VEC, long, int>, (long)s.batch * 2 * p.n, s.ens_rows)
+                   : go(pi::pi_wgrad_kernel<T, JC, NS, VEC>);
 }
 
 template <typename T, int VEC>
 hipError_t launch_wgrad(const T* traj, const T* adj, double* partials, const T* P, const Problem& p, int t_lo,
-                        int t_hi, unsigned* rows_out, hipStream_t st)
+                        int t_hi, unsigned* rows_out, hipStream_t st, const Samples& s = {})
 {
-    const long total = (long)(t_hi - t_lo) * (p.n / VEC);
-    long nb = (total + 256L * 16 - 1) / (256L * 16);          // >= 16 chunks per lane before adding blocks
-    if (nb > p.opt.wgrad_blocks) nb = p.opt.wgrad_blocks;
-    if (nb < 1) nb = 1;
-    *rows_out = (unsigned)(2 * nb);
+    const unsigned nb = (unsigned)(s.ens() ? ens_wgrad_blocks(p, s.batch, t_hi - t_lo, VEC) : wgrad_blocks(p, t_hi - t_lo, VEC));
+    *rows_out = 2 * nb;                                        // (ensemble: per sample)
     if (p.hc == 0) {                                           // pre-contracted mode: coefficient moments
         const size_t lds = (size_t)(256 / pi::WAVE) * 20 * sizeof(T);
         const Geom g = make_geom(p);
         const long ss = p.slab ? g.ss : (long)p.n, off = p.slab ? (long)p.halo * g.s0 : 0;
-        hipLaunchKernelGGL((pi::pi_moments_kernel<T, VEC>), dim3((unsigned)nb), dim3(256), lds, st, traj, adj, partials,
-                           P, (long)p.n, ss, off, t_lo, t_hi);
-        return hipGetLastError();
+        auto go = [&](auto* k, auto... tail) {
+            hipLaunchKernelGGL(k, dim3(nb, s.ens() ? (unsigned)s.batch : 1), dim3(256), lds, st, traj, adj, partials, P, (long)p.n,
+                               ss, off, t_lo, t_hi, tail...);
+            return hipGetLastError();
+        };
+        return s.ens() ? go(pi::pi_moments_kernel<T, VEC, long, int>, (long)s.batch * 2 * p.n, s.ens_rows)
+                       : go(pi::pi_moments_kernel<T, VEC>);
     }
     // small hidden widths: one workgroup handles both species (the state is streamed once)
-    if (p.hc == 2) return launch_wgrad_pass<T, 2, 2, VEC>(traj, adj, partials, P, p, t_lo, t_hi, 0, (unsigned)nb, st);
-    if (p.hc == 4) return launch_wgrad_pass<T, 4, 2, VEC>(traj, adj, partials, P, p, t_lo, t_hi, 0, (unsigned)nb, st);
+    if (p.hc == 2) return launch_wgrad_pass<T, 2, 2, VEC>(traj, adj, partials, P, p, t_lo, t_hi, 0, nb, st, s);
+    if (p.hc == 4) return launch_wgrad_pass<T, 4, 2, VEC>(traj, adj, partials, P, p, t_lo, t_hi, 0, nb, st, s);
     const int jc = p.hc % 8 == 0 ? 8 : p.hc % 4 == 0 ? 4 : p.hc % 2 == 0 ? 2 : 1;
     for (int j0 = 0; j0 < p.hc; j0 += jc) {
         hipError_t e;
         switch (jc) {
-            case 8:  e = launch_wgrad_pass<T, 8, 1, VEC>(traj, adj, partials, P, p, t_lo, t_hi, j0, (unsigned)nb, st); break;
-            case 4:  e = launch_wgrad_pass<T, 4, 1, VEC>(traj, adj, partials, P, p, t_lo, t_hi, j0, (unsigned)nb, st); break;
-            case 2:  e = launch_wgrad_pass<T, 2, 1, VEC>(traj, adj, partials, P, p, t_lo, t_hi, j0, (unsigned)nb, st); break;
-            default: e = launch_wgrad_pass<T, 1, 1, VEC>(traj, adj, partials, P, p, t_lo, t_hi, j0, (unsigned)nb, st); break;
+            case 8:  e = launch_wgrad_pass<T, 8, 1, VEC>(traj, adj, partials, P, p, t_lo, t_hi, j0, nb, st, s); break;
+            case 4:  e = launch_wgrad_pass<T, 4, 1, VEC>(traj, adj, partials, P, p, t_lo, t_hi, j0, nb, st, s); break;
+            case 2:  e = launch_wgrad_pass<T, 2, 1, VEC>(traj, adj, partials, P, p, t_lo, t_hi, j0, nb, st, s); break;
+            default: e = launch_wgrad_pass<T, 1, 1, VEC>(traj, adj, partials, P, p, t_lo, t_hi, j0, nb, st, s); break;
         }
         if (e) return e;
     }
@@ -1100,22 +1135,39 @@ pi::TileGeom make_tile_geom(const Problem& p, int by, int bx = TILE_B)
     return g;
 }
 
+// One launch of K steps on tiles.  The unbatched launch runs the kernel's plain flavour; the sample launches (s.on) its `long sample`
+// flavour on grid (tiles, B) with the frame stride of the whole batch -- the function-pointer types pick the trailing pack:
+// none (batched), or `int np` (ensemble).
 template <typename T, int HC, int K, int NT, int BY = TILE_B, int BX = TILE_B>
-hipError_t launch_fwd_tile(T* frame_t, const T* P, const Problem& p, hipStream_t st)
+hipError_t launch_fwd_tile(T* frame_t, const T* P, const Problem& p, hipStream_t st, const Samples& s = {})
 {
     using TL = pi::Tile<K, BX, BY>;
     const pi::TileGeom g = make_tile_geom(p, BY, BX);
     const unsigned grid = (unsigned)(((p.n0 + BY - 1) / BY) * g.tiles_x);
     const size_t lds = (size_t)4 * TL::PLANE * sizeof(T) + 32 /* lds_pad0/1 */ + (size_t)p.opt.lds_pad;
-    auto* k = pi::pi_fwd2d_tile_kernel<T, HC, K, BX, BY, NT>;
-    if (hipError_t e = allow_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(NT), lds, st, frame_t, (long)(2 * p.n), P, g);
-    return hipGetLastError();
+    if (!s.on) {
+        auto* k = pi::pi_fwd2d_tile_kernel<T, HC, K, BX, BY, NT>;
+        if (hipError_t e = allow_lds(k, lds)) return e;
+        hipLaunchKernelGGL(k, dim3(grid), dim3(NT), lds, st, frame_t, (long)(2 * p.n), P, g);
+        return hipGetLastError();
+    }
+    auto go = [&](auto* k, auto... tail) {
+        if (hipError_t e = allow_lds(k, lds)) return e;
+        hipLaunchKernelGGL(k, dim3(grid, (unsigned)s.batch), dim3(NT), lds, st, frame_t, (long)s.batch * 2 * p.n, (long)(2 * p.n), P, g,
+                           tail...);
+        return hipGetLastError();
+    };
+    // the target type picks the trailing pack (`int np`); `long` is the sample stride in the middle of the list
+    void (*ens)(T*, long, long, const T*, pi::TileGeom, int) = pi::pi_fwd2d_tile_kernel<T, HC, K, BX, BY, NT, long>;
+    return s.ens() ? go(ens, pi::nparams(p.hc)) : go(pi::pi_fwd2d_tile_kernel<T, HC, K, BX, BY, NT, long>);
 }
 
+// The adjoint of launch_fwd_tile, same flavours; trailing packs: none (batched), `int rows` (ensemble), and behind either the
+// lattice of the sparse-observation form (`ob`, sample launches only).
 template <typename T, int HC, int K, int NT, int BY = TILE_B, bool MOM = false, int BX = TILE_B>
 hipError_t launch_adj_tile(const T* hframe_t, const T* gframe_t, T* aframe_t, unsigned inj_mask, T* g_h0,
-                           int steps_to_zero, double* partials, const T* P, const Problem& p, hipStream_t st)
+                           int steps_to_zero, double* partials, const T* P, const Problem& p, hipStream_t st,
+                           const Samples& s = {}, const pi::ObsTile* ob = nullptr)
 {
     using TL = pi::Tile<K, BX, BY>;
     const pi::TileGeom g = make_tile_geom(p, BY, BX);
@@ -1129,11 +1181,31 @@ hipError_t launch_adj_tile(const T* hframe_t, const T* gframe_t, T* aframe_t, un
     if (MOM && sizeof(T) == 8)                  // float64: [20][NT] per-lane moment accumulators behind the state buffers
         lds = pi::tile_state_bytes<T, K, BX, BY>() + (size_t)20 * NT * sizeof(double);
     lds += (size_t)p.opt.lds_pad;
-    auto* k = pi::pi_adj2d_tile_kernel<T, HC, K, BX, BY, NT, MOM>;
-    if (hipError_t e = allow_lds(k, lds)) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(NT), lds, st, hframe_t, gframe_t, aframe_t, (long)(2 * p.n), inj_mask, g_h0,
-                       steps_to_zero, partials, pi::nparams(p.hc), P, g);
-    return hipGetLastError();
+    if (!s.on) {
+        auto* k = pi::pi_adj2d_tile_kernel<T, HC, K, BX, BY, NT, MOM>;
+        if (hipError_t e = allow_lds(k, lds)) return e;
+        hipLaunchKernelGGL(k, dim3(grid), dim3(NT), lds, st, hframe_t, gframe_t, aframe_t, (long)(2 * p.n), inj_mask, g_h0,
+                           steps_to_zero, partials, pi::nparams(p.hc), P, g);
+        return hipGetLastError();
+    }
+    auto go = [&](auto* k, auto... tail) {
+        if (hipError_t e = allow_lds(k, lds)) return e;
+        hipLaunchKernelGGL(k, dim3(grid, (unsigned)s.batch), dim3(NT), lds, st, hframe_t, gframe_t, aframe_t, (long)s.batch * 2 * p.n,
+                           (long)(2 * p.n), inj_mask, g_h0, steps_to_zero, partials, pi::nparams(p.hc), P, g, tail...);
+        return hipGetLastError();
+    };
+    // as launch_fwd_tile: the target type picks the trailing pack (`int rows`)
+    void (*ens)(const T*, const T*, T*, long, long, unsigned, T*, int, double*, int, const T*, pi::TileGeom, int) =
+        pi::pi_adj2d_tile_kernel<T, HC, K, BX, BY, NT, MOM, long>;
+    if (ob) {                                   // sparse-observation flavours: the lattice behind the other trailing arguments
+        static_assert(K <= 8, "ObsTile::coff");
+        void (*bo)(const T*, const T*, T*, long, long, unsigned, T*, int, double*, int, const T*, pi::TileGeom, pi::ObsTile) =
+            pi::pi_adj2d_tile_kernel<T, HC, K, BX, BY, NT, MOM, long>;
+        void (*eo)(const T*, const T*, T*, long, long, unsigned, T*, int, double*, int, const T*, pi::TileGeom, int, pi::ObsTile) =
+            pi::pi_adj2d_tile_kernel<T, HC, K, BX, BY, NT, MOM, long>;
+        return s.ens() ? go(eo, s.ens_rows, *ob) : go(bo, *ob);
+    }
+    return s.ens() ? go(ens, s.ens_rows) : go(pi::pi_adj2d_tile_kernel<T, HC, K, BX, BY, NT, MOM, long>);
 }
 
 #define PI_TILE_VARIANTS(CALL, HC)                                              \
@@ -1158,17 +1230,18 @@ hipError_t launch_adj_tile(const T* hframe_t, const T* gframe_t, T* aframe_t, un
         }                                                                       \
     } while (0)
 
+// the tile variant of one sample, on every sample the launch covers
 template <typename T>
-hipError_t fwd_tile(T* frame_t, const T* P, const Problem& p, hipStream_t st)
+hipError_t fwd_tile(T* frame_t, const T* P, const Problem& p, hipStream_t st, const Samples& s = {})
 {
     if constexpr (sizeof(T) == 4) {
         switch (tile_wide_for<T>(p, false)) {
-            case 1: return launch_fwd_tile<T, pi::POLY, 4, 640, 40, 32>(frame_t, P, p, st);
-            case 2: return launch_fwd_tile<T, pi::POLY, 4, 768, 40, 40>(frame_t, P, p, st);
+            case 1: return launch_fwd_tile<T, pi::POLY, 4, 640, 40, 32>(frame_t, P, p, st, s);
+            case 2: return launch_fwd_tile<T, pi::POLY, 4, 768, 40, 40>(frame_t, P, p, st, s);
             default: break;
         }
     }
-#define CALL_FT(HC, K, NT, ...) launch_fwd_tile<T, HC, K, NT, ##__VA_ARGS__>(frame_t, P, p, st)
+#define CALL_FT(HC, K, NT, ...) launch_fwd_tile<T, HC, K, NT, ##__VA_ARGS__>(frame_t, P, p, st, s)
     PI_TILE_DISPATCH(CALL_FT);
 #undef CALL_FT
 }
@@ -1190,12 +1263,14 @@ bool tile_fuse_ok(const Problem& p)
 
 template <typename T>
 hipError_t adj_tile(const T* hframe_t, const T* gframe_t, T* aframe_t, unsigned inj_mask, T* g_h0, int steps_to_zero,
-                    double* partials, const T* P, const Problem& p, hipStream_t st)
+                    double* partials, const T* P, const Problem& p, hipStream_t st, const Samples& s = {},
+                    const pi::ObsTile* ob = nullptr)
 {
     if constexpr (sizeof(T) == 4) {
         const bool fused = tile_fuse_ok<T>(p);
-#define CALL_WIDE(NT, BY, BX, MOM) \
-    launch_adj_tile<T, pi::POLY, 4, NT, BY, MOM, BX>(hframe_t, gframe_t, aframe_t, inj_mask, g_h0, steps_to_zero, partials, P, p, st)
+#define CALL_WIDE(NT, BY, BX, MOM)                                                                                                  \
+    launch_adj_tile<T, pi::POLY, 4, NT, BY, MOM, BX>(hframe_t, gframe_t, aframe_t, inj_mask, g_h0, steps_to_zero, partials, P, p, st, \
+                                                     s, ob)
         switch (tile_wide_for<T>(p, true)) {
             case 1: return fused ? CALL_WIDE(640, 40, 32, true) : CALL_WIDE(640, 40, 32, false);
             case 2: return fused ? CALL_WIDE(768, 40, 40, true) : CALL_WIDE(768, 40, 40, false);
@@ -1205,9 +1280,9 @@ hipError_t adj_tile(const T* hframe_t, const T* gframe_t, T* aframe_t, unsigned 
     }
     if (tile_fuse_ok<T>(p))
         return launch_adj_tile<T, pi::POLY, 4, 512, TILE_B, true>(hframe_t, gframe_t, aframe_t, inj_mask, g_h0,
-                                                                  steps_to_zero, partials, P, p, st);
+                                                                  steps_to_zero, partials, P, p, st, s, ob);
 #define CALL_AT(HC, K, NT, ...) \
-    launch_adj_tile<T, HC, K, NT, ##__VA_ARGS__>(hframe_t, gframe_t, aframe_t, inj_mask, g_h0, steps_to_zero, partials, P, p, st)
+    launch_adj_tile<T, HC, K, NT, ##__VA_ARGS__>(hframe_t, gframe_t, aframe_t, inj_mask, g_h0, steps_to_zero, partials, P, p, st, s, ob)
     PI_TILE_DISPATCH(CALL_AT);
 #undef CALL_AT
 }
@@ -2616,9 +2691,12 @@ int batch_problem(int hc, int ndim, const int64_t* shape, int batch, Problem& p,
     return 0;
 }
 
-// Launchers below: ens_rows = -1 runs the batched flavour (one block P); ens_rows >= 0 the ensemble flavour of the same
-// shape (P [B][np], partial rows at sample * ens_rows; "ensembles" further down).  They differ in the kernel's trailing
-// arguments alone, so each launcher states its launch once, in `go`.
+// Every launcher takes the samples of its launch as a `Samples`: the batch size, and ens_rows = -1 for the batched flavour (one
+// block P) or >= 0 for the ensemble flavour of the same shape (P [B][np], partial rows at sample * ens_rows; "ensembles" further
+// down).  The flavours differ in the kernel's trailing arguments alone, so each launcher states its launch once, in `go`.  The
+// tile launchers and the gradient pass are the unbatched ones (launch_fwd_tile, launch_adj_tile, launch_wgrad) given a
+// `Samples`; the direct and the brick launchers below are sample launchers of their own (no RZ, grid cap, XCD window, fused put).
+// Below its argument checks every batched / ensemble entry point runs one body: sample_rollout_fwd, sample_rollout_bwd.
 
 // tile vs direct: the per-sample rules of tile_eligible, with the size limits of the "tile = 1" rule applied to the points of
 // the whole batch (the tile kernels pay while the launches are latency-bound: 100^2 x 64 still is)
@@ -2630,105 +2708,8 @@ bool batch_tile(const Problem& p, int batch, std::initializer_list<const void*> 
     return true;
 }
 
-template <typename T, int HC, int K, int NT, int BY = TILE_B, int BX = TILE_B>
-hipError_t launch_fwd_tile_b(T* frame_t, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows = -1)
-{
-    using TL = pi::Tile<K, BX, BY>;
-    const pi::TileGeom g = make_tile_geom(p, BY, BX);
-    const unsigned grid = (unsigned)(((p.n0 + BY - 1) / BY) * g.tiles_x);
-    const size_t lds = (size_t)4 * TL::PLANE * sizeof(T) + 32 /* lds_pad0/1 */ + (size_t)p.opt.lds_pad;
-    auto go = [&](auto* k, auto... tail) {
-        if (hipError_t e = allow_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(NT), lds, st, frame_t, (long)batch * 2 * p.n, (long)(2 * p.n), P, g,
-                           tail...);
-        return hipGetLastError();
-    };
-    // the target type picks the trailing pack (`int np`); `long` is the sample stride in the middle of the list
-    void (*ens)(T*, long, long, const T*, pi::TileGeom, int) = pi::pi_fwd2d_tile_kernel<T, HC, K, BX, BY, NT, long>;
-    return ens_rows >= 0 ? go(ens, pi::nparams(p.hc)) : go(pi::pi_fwd2d_tile_kernel<T, HC, K, BX, BY, NT, long>);
-}
-
-template <typename T, int HC, int K, int NT, int BY = TILE_B, bool MOM = false, int BX = TILE_B>
-hipError_t launch_adj_tile_b(const T* hframe_t, const T* gframe_t, T* aframe_t, unsigned inj_mask, T* g_h0, int steps_to_zero,
-                             double* partials, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows = -1,
-                             const pi::ObsTile* ob = nullptr)
-{
-    using TL = pi::Tile<K, BX, BY>;
-    const pi::TileGeom g = make_tile_geom(p, BY, BX);
-    const unsigned grid = (unsigned)(((p.n0 + BY - 1) / BY) * g.tiles_x);
-    size_t lds = (size_t)4 * TL::PLANE * sizeof(T) + 32 /* lds_pad0/1 */;
-    if (MOM && sizeof(T) == 4) {                // as launch_adj_tile
-        const size_t tail = (size_t)(2 * (NT / pi::WAVE) + 20 + 20 * (NT / pi::WAVE)) * sizeof(double) +
-                            (size_t)20 * (NT + 16) * sizeof(T);
-        if (tail > lds) lds = tail;
-    }
-    if (MOM && sizeof(T) == 8)
-        lds = pi::tile_state_bytes<T, K, BX, BY>() + (size_t)20 * NT * sizeof(double);
-    lds += (size_t)p.opt.lds_pad;
-    auto go = [&](auto* k, auto... tail) {
-        if (hipError_t e = allow_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(NT), lds, st, hframe_t, gframe_t, aframe_t, (long)batch * 2 * p.n,
-                           (long)(2 * p.n), inj_mask, g_h0, steps_to_zero, partials, pi::nparams(p.hc), P, g, tail...);
-        return hipGetLastError();
-    };
-    // as launch_fwd_tile_b: the target type picks the trailing pack (`int rows`)
-    void (*ens)(const T*, const T*, T*, long, long, unsigned, T*, int, double*, int, const T*, pi::TileGeom, int) =
-        pi::pi_adj2d_tile_kernel<T, HC, K, BX, BY, NT, MOM, long>;
-    if (ob) {                                   // sparse-observation flavours: the lattice behind the other trailing arguments
-        static_assert(K <= 8, "ObsTile::coff");
-        void (*bo)(const T*, const T*, T*, long, long, unsigned, T*, int, double*, int, const T*, pi::TileGeom, pi::ObsTile) =
-            pi::pi_adj2d_tile_kernel<T, HC, K, BX, BY, NT, MOM, long>;
-        void (*eo)(const T*, const T*, T*, long, long, unsigned, T*, int, double*, int, const T*, pi::TileGeom, int, pi::ObsTile) =
-            pi::pi_adj2d_tile_kernel<T, HC, K, BX, BY, NT, MOM, long>;
-        return ens_rows >= 0 ? go(eo, ens_rows, *ob) : go(bo, *ob);
-    }
-    return ens_rows >= 0 ? go(ens, ens_rows) : go(pi::pi_adj2d_tile_kernel<T, HC, K, BX, BY, NT, MOM, long>);
-}
-
-// the tile variant fwd_tile / adj_tile pick for one sample, on all samples
-template <typename T>
-hipError_t fwd_tile_b(T* frame_t, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows = -1)
-{
-    if constexpr (sizeof(T) == 4) {
-        switch (tile_wide_for<T>(p, false)) {
-            case 1: return launch_fwd_tile_b<T, pi::POLY, 4, 640, 40, 32>(frame_t, P, p, batch, st, ens_rows);
-            case 2: return launch_fwd_tile_b<T, pi::POLY, 4, 768, 40, 40>(frame_t, P, p, batch, st, ens_rows);
-            default: break;
-        }
-    }
-#define CALL_FTB(HC, K, NT, ...) launch_fwd_tile_b<T, HC, K, NT, ##__VA_ARGS__>(frame_t, P, p, batch, st, ens_rows)
-    PI_TILE_DISPATCH(CALL_FTB);
-#undef CALL_FTB
-}
-
-template <typename T>
-hipError_t adj_tile_b(const T* hframe_t, const T* gframe_t, T* aframe_t, unsigned inj_mask, T* g_h0, int steps_to_zero,
-                      double* partials, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows = -1,
-                      const pi::ObsTile* ob = nullptr)
-{
-    if constexpr (sizeof(T) == 4) {
-        const bool fused = tile_fuse_ok<T>(p);
-#define CALL_WIDE_B(NT, BY, BX, MOM) launch_adj_tile_b<T, pi::POLY, 4, NT, BY, MOM, BX>(hframe_t, gframe_t, aframe_t, inj_mask, \
-                                                                                      g_h0, steps_to_zero, partials, P, p, batch, st, \
-                                                                                      ens_rows, ob)
-        switch (tile_wide_for<T>(p, true)) {
-            case 1: return fused ? CALL_WIDE_B(640, 40, 32, true) : CALL_WIDE_B(640, 40, 32, false);
-            case 2: return fused ? CALL_WIDE_B(768, 40, 40, true) : CALL_WIDE_B(768, 40, 40, false);
-            default: break;
-        }
-#undef CALL_WIDE_B
-    }
-    if (tile_fuse_ok<T>(p))
-        return launch_adj_tile_b<T, pi::POLY, 4, 512, TILE_B, true>(hframe_t, gframe_t, aframe_t, inj_mask, g_h0, steps_to_zero,
-                                                                    partials, P, p, batch, st, ens_rows, ob);
-#define CALL_ATB(HC, K, NT, ...) launch_adj_tile_b<T, HC, K, NT, ##__VA_ARGS__>(hframe_t, gframe_t, aframe_t, inj_mask, g_h0, \
-                                                                               steps_to_zero, partials, P, p, batch, st, ens_rows, ob)
-    PI_TILE_DISPATCH(CALL_ATB);
-#undef CALL_ATB
-}
-
 template <typename T, int NDIM, int HC, int VEC>
-hipError_t launch_fwd_b(const T* h, T* out, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows = -1)
+hipError_t launch_fwd_b(const T* h, T* out, const T* P, const Problem& p, hipStream_t st, const Samples& s)
 {
     Geom g = make_geom(p);
     const int block = direct_block(p, g, VEC);
@@ -2737,16 +2718,16 @@ hipError_t launch_fwd_b(const T* h, T* out, const T* P, const Problem& p, int ba
         return (hipError_t)PERCNN_PI_ETOOLARGE;
     g.xwin = 0;
     auto go = [&](auto* k, auto... tail) {
-        hipLaunchKernelGGL(k, dim3(g.nblk, (unsigned)batch), dim3(block), 0, st, h, out, P, g, p.hc, (long)(2 * p.n), tail...);
+        hipLaunchKernelGGL(k, dim3(g.nblk, (unsigned)s.batch), dim3(block), 0, st, h, out, P, g, p.hc, (long)(2 * p.n), tail...);
         return hipGetLastError();
     };
-    return ens_rows >= 0 ? go(pi::pi_fwd_kernel<T, NDIM, HC, VEC, 1, long, int>, pi::nparams(p.hc))
-                         : go(pi::pi_fwd_kernel<T, NDIM, HC, VEC, 1, long>);
+    return s.ens() ? go(pi::pi_fwd_kernel<T, NDIM, HC, VEC, 1, long, int>, pi::nparams(p.hc))
+                   : go(pi::pi_fwd_kernel<T, NDIM, HC, VEC, 1, long>);
 }
 
 template <typename T, int NDIM, int HC, int VEC, bool WGRAD>
-hipError_t launch_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* partials, const T* P, const Problem& p, int batch,
-                        hipStream_t st, unsigned* rows_out, int ens_rows = -1, const pi::ObsLat* ol = nullptr)
+hipError_t launch_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* partials, const T* P, const Problem& p,
+                        hipStream_t st, const Samples& s, unsigned* rows_out, const pi::ObsLat* ol = nullptr)
 {
     Geom g = make_geom(p);
     const int block = direct_block(p, g, VEC);
@@ -2759,19 +2740,19 @@ hipError_t launch_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* par
                        ((WGRAD && HC == pi::POLY) ? (size_t)20 * (block + 8) * sizeof(T) : 0);
     auto go = [&](auto* k, auto... tail) {
         if (hipError_t e = allow_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(block), lds, st, h, G, inj, Gp, partials, P, g, p.hc, (long)(2 * p.n),
+        hipLaunchKernelGGL(k, dim3(grid, (unsigned)s.batch), dim3(block), lds, st, h, G, inj, Gp, partials, P, g, p.hc, (long)(2 * p.n),
                            tail...);
         return hipGetLastError();
     };
-    if (ens_rows >= 0) {
-        if (grid > (unsigned)ens_rows) return (hipError_t)PERCNN_PI_ETOOLARGE;   // ens_rows bounds every launch (ens_rows_for)
-        if (ol) return go(pi::pi_bwd_kernel<T, NDIM, HC, VEC, WGRAD, 1, long, int, pi::ObsLat>, ens_rows, *ol);
-        return go(pi::pi_bwd_kernel<T, NDIM, HC, VEC, WGRAD, 1, long, int>, ens_rows);
+    if (s.ens()) {
+        if (grid > (unsigned)s.ens_rows) return (hipError_t)PERCNN_PI_ETOOLARGE;   // ens_rows bounds every launch (ens_rows_for)
+        if (ol) return go(pi::pi_bwd_kernel<T, NDIM, HC, VEC, WGRAD, 1, long, int, pi::ObsLat>, s.ens_rows, *ol);
+        return go(pi::pi_bwd_kernel<T, NDIM, HC, VEC, WGRAD, 1, long, int>, s.ens_rows);
     }
     // (ol: the sparse-observation flavours, `inj` = the compact target frame)
     const hipError_t e = ol ? go(pi::pi_bwd_kernel<T, NDIM, HC, VEC, WGRAD, 1, long, pi::ObsLat>, *ol)
                             : go(pi::pi_bwd_kernel<T, NDIM, HC, VEC, WGRAD, 1, long>);
-    if (e == hipSuccess && rows_out) *rows_out = grid * (unsigned)batch;
+    if (e == hipSuccess && rows_out) *rows_out = grid * (unsigned)s.batch;
     return e;
 }
 
@@ -2823,7 +2804,7 @@ unsigned batch_brick_bwd_grid(const Problem& p, int vec, int rz, int batch)
 }
 
 template <typename T, int HC, int RZ>
-hipError_t launch_brick_fwd_b(const T* h, T* out, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows = -1)
+hipError_t launch_brick_fwd_b(const T* h, T* out, const T* P, const Problem& p, hipStream_t st, const Samples& s)
 {
     constexpr int VEC = 16 / (int)sizeof(T);
     const pi::BrickGeom b = make_brick_geom(p, VEC, RZ, pi::BRICK_NT, false);
@@ -2831,18 +2812,18 @@ hipError_t launch_brick_fwd_b(const T* h, T* out, const T* P, const Problem& p, 
     const size_t lds = (size_t)2 * RZ * pi::BRICK_WB + (size_t)p.opt.lds_pad;
     auto go = [&](auto* k, auto... tail) {
         if (hipError_t e = allow_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(b.nblk, (unsigned)batch), dim3(pi::BRICK_NT), lds, st, h, out, P, b, p.hc, pi::PeerPutFused{},
+        hipLaunchKernelGGL(k, dim3(b.nblk, (unsigned)s.batch), dim3(pi::BRICK_NT), lds, st, h, out, P, b, p.hc, pi::PeerPutFused{},
                            (long)(2 * p.n), tail...);
         return hipGetLastError();
     };
-    return ens_rows >= 0 ? go(pi::pi_fwd3d_brick_kernel<T, HC, RZ, pi::BRICK_NT, long, int>, pi::nparams(p.hc))
-                         : go(pi::pi_fwd3d_brick_kernel<T, HC, RZ, pi::BRICK_NT, long>);
+    return s.ens() ? go(pi::pi_fwd3d_brick_kernel<T, HC, RZ, pi::BRICK_NT, long, int>, pi::nparams(p.hc))
+                   : go(pi::pi_fwd3d_brick_kernel<T, HC, RZ, pi::BRICK_NT, long>);
 }
 
 template <typename T>
-hipError_t brick_fwd_b(int rz, const T* h, T* out, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows)
+hipError_t brick_fwd_b(int rz, const T* h, T* out, const T* P, const Problem& p, hipStream_t st, const Samples& s)
 {
-#define CALL_BFB(HC, RZ) launch_brick_fwd_b<T, HC, RZ>(h, out, P, p, batch, st, ens_rows)
+#define CALL_BFB(HC, RZ) launch_brick_fwd_b<T, HC, RZ>(h, out, P, p, st, s)
     switch (p.hc) {
         case 0:  return rz == 2 ? CALL_BFB(pi::POLY, 2) : CALL_BFB(pi::POLY, 1);
         case 2:  return CALL_BFB(2, 1);
@@ -2854,41 +2835,41 @@ hipError_t brick_fwd_b(int rz, const T* h, T* out, const T* P, const Problem& p,
 }
 
 template <typename T, int HC, int RZ, bool MOM>
-hipError_t launch_brick_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* partials, const T* P, const Problem& p, int batch,
-                              hipStream_t st, unsigned* rows_out, int ens_rows = -1)
+hipError_t launch_brick_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* partials, const T* P, const Problem& p,
+                              hipStream_t st, const Samples& s, unsigned* rows_out)
 {
     constexpr int VEC = 16 / (int)sizeof(T), NT = pi::BRICK_NT;
     const pi::BrickGeom b = make_brick_geom(p, VEC, RZ, NT, true);
     if (b.n0 <= 0) return hipSuccess;
-    unsigned grid = batch_brick_bwd_grid(p, VEC, RZ, batch);
-    if (ens_rows >= 0 && grid > (unsigned)ens_rows) grid = (unsigned)ens_rows;   // (ens_rows_for counts this launch: no-op)
+    unsigned grid = batch_brick_bwd_grid(p, VEC, RZ, s.batch);
+    if (s.ens() && grid > (unsigned)s.ens_rows) grid = (unsigned)s.ens_rows;   // (ens_rows_for counts this launch: no-op)
     if (!grid) return (hipError_t)PERCNN_PI_ETOOLARGE;
     const size_t head = (size_t)(NT / pi::WAVE) * 2 * sizeof(double);
     const size_t windows = (size_t)2 * RZ * pi::BRICK_WB, scratch = MOM ? (size_t)(32 + 20 * (NT + 8)) * sizeof(T) : 0;
     const size_t lds = head + (windows > scratch ? windows : scratch) + (size_t)p.opt.lds_pad;
     auto go = [&](auto* k, auto... tail) {
         if (hipError_t e = allow_lds(k, lds)) return e;
-        hipLaunchKernelGGL(k, dim3(grid, (unsigned)batch), dim3(NT), lds, st, h, G, inj, Gp, partials, P, b, p.hc, pi::NoPut{},
+        hipLaunchKernelGGL(k, dim3(grid, (unsigned)s.batch), dim3(NT), lds, st, h, G, inj, Gp, partials, P, b, p.hc, pi::NoPut{},
                            (long)(2 * p.n), tail...);
         return hipGetLastError();
     };
     auto flavour = [&](auto loss) {
         constexpr int LOSS = decltype(loss)::value;
-        return ens_rows >= 0 ? go(pi::pi_adj3d_brick_kernel<T, HC, RZ, MOM, LOSS, NT, false, long, int>, ens_rows)
-                             : go(pi::pi_adj3d_brick_kernel<T, HC, RZ, MOM, LOSS, NT, false, long>);
+        return s.ens() ? go(pi::pi_adj3d_brick_kernel<T, HC, RZ, MOM, LOSS, NT, false, long, int>, s.ens_rows)
+                       : go(pi::pi_adj3d_brick_kernel<T, HC, RZ, MOM, LOSS, NT, false, long>);
     };
     const hipError_t e = p.loss.mode == 1 ? flavour(std::integral_constant<int, 1>{})
                        : p.loss.mode == 2 ? flavour(std::integral_constant<int, 2>{})
                                           : flavour(std::integral_constant<int, 0>{});
-    if (e == hipSuccess && rows_out) *rows_out = grid * (unsigned)batch;
+    if (e == hipSuccess && rows_out) *rows_out = grid * (unsigned)s.batch;
     return e;
 }
 
 template <typename T>
 hipError_t brick_bwd_b(int rz, bool mom, const T* h, const T* G, const T* inj, T* Gp, double* partials, const T* P, const Problem& p,
-                       int batch, hipStream_t st, unsigned* rows_out, int ens_rows)
+                       hipStream_t st, const Samples& s, unsigned* rows_out)
 {
-#define CALL_BBB(HC, RZ, MOM) launch_brick_bwd_b<T, HC, RZ, MOM>(h, G, inj, Gp, partials, P, p, batch, st, rows_out, ens_rows)
+#define CALL_BBB(HC, RZ, MOM) launch_brick_bwd_b<T, HC, RZ, MOM>(h, G, inj, Gp, partials, P, p, st, s, rows_out)
     if (p.hc == 0) {
         if (mom) return rz == 2 ? CALL_BBB(pi::POLY, 2, true) : CALL_BBB(pi::POLY, 1, true);
         return rz == 2 ? CALL_BBB(pi::POLY, 2, false) : CALL_BBB(pi::POLY, 1, false);
@@ -2903,24 +2884,24 @@ hipError_t brick_bwd_b(int rz, bool mom, const T* h, const T* G, const T* inj, T
 }
 
 template <typename T>
-hipError_t step_fwd_b(const T* h, T* out, const T* P, const Problem& p, int batch, hipStream_t st, int ens_rows = -1)
+hipError_t step_fwd_b(const T* h, T* out, const T* P, const Problem& p, hipStream_t st, const Samples& s)
 {
     const int vec = pick_vec<T>(p, {h, out});
-    if (const int brz = batch_brick_rz<T>(p, vec, batch, false, false, false)) return brick_fwd_b<T>(brz, h, out, P, p, batch, st, ens_rows);
-#define CALL_FWDB(NDIM, HC, VEC) launch_fwd_b<T, NDIM, HC, VEC>(h, out, P, p, batch, st, ens_rows)
+    if (const int brz = batch_brick_rz<T>(p, vec, s.batch, false, false, false)) return brick_fwd_b<T>(brz, h, out, P, p, st, s);
+#define CALL_FWDB(NDIM, HC, VEC) launch_fwd_b<T, NDIM, HC, VEC>(h, out, P, p, st, s)
     PI_DISPATCH(CALL_FWDB);
 #undef CALL_FWDB
 }
 
 template <typename T, bool WGRAD>
-hipError_t step_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* partials, const T* P, const Problem& p, int batch,
-                      hipStream_t st, unsigned* rows_out, int ens_rows = -1, const pi::ObsLat* ol = nullptr)
+hipError_t step_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* partials, const T* P, const Problem& p, hipStream_t st,
+                      const Samples& s, unsigned* rows_out, const pi::ObsLat* ol = nullptr)
 {
     // (the compact target of the sparse-observation flavours is read element-wise: its alignment does not pick the lanes)
     const int vec = pick_vec<T>(p, {h, G, ol ? nullptr : inj, Gp});
-    if (const int brz = batch_brick_rz<T>(p, vec, batch, true, WGRAD, ol != nullptr))
-        return brick_bwd_b<T>(brz, WGRAD, h, G, inj, Gp, partials, P, p, batch, st, rows_out, ens_rows);
-#define CALL_BWDB(NDIM, HC, VEC) launch_bwd_b<T, NDIM, HC, VEC, WGRAD>(h, G, inj, Gp, partials, P, p, batch, st, rows_out, ens_rows, ol)
+    if (const int brz = batch_brick_rz<T>(p, vec, s.batch, true, WGRAD, ol != nullptr))
+        return brick_bwd_b<T>(brz, WGRAD, h, G, inj, Gp, partials, P, p, st, s, rows_out);
+#define CALL_BWDB(NDIM, HC, VEC) launch_bwd_b<T, NDIM, HC, VEC, WGRAD>(h, G, inj, Gp, partials, P, p, st, s, rows_out, ol)
     PI_DISPATCH(CALL_BWDB);
 #undef CALL_BWDB
 }
@@ -2945,7 +2926,7 @@ int batch_step_fwd_impl(const T* h, T* out, const T* P, int hc, int ndim, const 
     Problem p;
     if (int rc = batch_problem(hc, ndim, shape, batch, p, options)) return rc;
     if (!h || !out || !P || h == out) return PERCNN_PI_EINVAL;
-    return (int)step_fwd_b<T>(h, out, P, p, batch, static_cast<hipStream_t>(stream));
+    return (int)step_fwd_b<T>(h, out, P, p, static_cast<hipStream_t>(stream), Samples{batch, -1, true});
 }
 
 template <typename T>
@@ -2966,8 +2947,24 @@ int batch_step_bwd_impl(const T* h, const T* g_out, const T* g_inj, T* g_in, dou
     w.partials_bytes = batch_partials_bytes(p, batch);
     if (hipError_t e = hipMemsetAsync(w.partials, 0, w.partials_bytes, st)) return (int)e;
     unsigned rows = 0;
-    if (hipError_t e = step_bwd_b<T, true>(h, g_out, g_inj, g_in, w.partials, P, p, batch, st, &rows)) return (int)e;
+    if (hipError_t e = step_bwd_b<T, true>(h, g_out, g_inj, g_in, w.partials, P, p, st, Samples{batch, -1, true}, &rows)) return (int)e;
     return (int)finish_grads(w, rows, hc, param_grad, st);
+}
+
+// the forward loop of both flavours: tile launches of K steps while they fit, the rest step by step
+template <typename T>
+int sample_rollout_fwd(T* traj, const T* P, const Problem& p, int T_steps, hipStream_t st, const Samples& s)
+{
+    const size_t frame = (size_t)s.batch * 2 * p.n;        // frame t of all samples: [B][2][*S]
+    int t = 0;
+    if (batch_tile<T>(p, s.batch, {traj}, false)) {
+        const int K = (p.opt.tile_k == 8 && p.hc != 0) ? 4 : p.opt.tile_k;
+        for (; t + K <= T_steps; t += K)
+            if (hipError_t e = fwd_tile<T>(traj + (size_t)t * frame, P, p, st, s)) return (int)e;
+    }
+    for (; t < T_steps; ++t)
+        if (hipError_t e = step_fwd_b<T>(traj + (size_t)t * frame, traj + (size_t)(t + 1) * frame, P, p, st, s)) return (int)e;
+    return 0;
 }
 
 template <typename T>
@@ -2978,17 +2975,7 @@ int batch_rollout_fwd_impl(T* traj, const T* P, int hc, int ndim, const int64_t*
     Problem p;
     if (int rc = batch_problem(hc, ndim, shape, batch, p, options)) return rc;
     if (!traj || !P || T_steps < 0) return PERCNN_PI_EINVAL;
-    auto st = static_cast<hipStream_t>(stream);
-    const size_t frame = (size_t)batch * 2 * p.n;          // frame t of all samples: [B][2][*S]
-    int t = 0;
-    if (batch_tile<T>(p, batch, {traj}, false)) {
-        const int K = (p.opt.tile_k == 8 && p.hc != 0) ? 4 : p.opt.tile_k;
-        for (; t + K <= T_steps; t += K)
-            if (hipError_t e = fwd_tile_b<T>(traj + (size_t)t * frame, P, p, batch, st)) return (int)e;
-    }
-    for (; t < T_steps; ++t)
-        if (hipError_t e = step_fwd_b<T>(traj + (size_t)t * frame, traj + (size_t)(t + 1) * frame, P, p, batch, st)) return (int)e;
-    return 0;
+    return sample_rollout_fwd<T>(traj, P, p, T_steps, static_cast<hipStream_t>(stream), Samples{batch, -1, true});
 }
 
 // loss form of the batched / ensemble sweeps (pi::LossInj; `dev` holds one factor per sample): frame [B][2][*S] of the loss
@@ -3075,6 +3062,12 @@ int sweep_loss_form(const pi::LossInj* loss, const void* traj, const void*& g_tr
     return 0;
 }
 
+// the sweep of both flavours, below their argument checks (defined under "ensembles", next to the ensemble flavour's row rule)
+template <typename T>
+int sample_rollout_bwd(const T* traj, const T* g_traj, const unsigned char* mask, T* g_h0, double* param_grad, void* ws, const T* P,
+                       const Problem& p, int T_steps, hipStream_t st, const pi::LossInj* loss, const ObsHost* oh, const T* target_c,
+                       Samples s);
+
 template <typename T>
 int batch_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* mask, T* g_h0, double* param_grad, void* ws,
                            size_t ws_bytes, const T* P, int hc, int ndim, const int64_t* shape, int batch, int T_steps,
@@ -3082,7 +3075,7 @@ int batch_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* 
                            const T* target_c = nullptr)
 {
     // obs_strides (with loss, mode 2, and g_traj = traj): the sparse-observation loss form, target_c its compact target or nullptr.
-    // It runs the launches below for one sample too: the unbatched sweep may dispatch a resident kernel, which has no such form
+    // It runs the sample launches for one sample too: the unbatched sweep may dispatch a resident kernel, which has no such form
     const bool obs = loss && obs_strides;
     if (batch == 1 && !obs)
         return rollout_bwd_impl<T>(traj, g_traj, mask, g_h0, param_grad, ws, ws_bytes, P, hc, ndim, shape, T_steps, stream, options,
@@ -3106,97 +3099,20 @@ int batch_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* 
     }
     if (!ws || ws_bytes < batch_rollout_workspace_bytes(p, batch, T_steps, sizeof(T)) || (reinterpret_cast<uintptr_t>(ws) % 16))
         return PERCNN_PI_EWORKSPACE;
-    auto st = static_cast<hipStream_t>(stream);
-    const size_t sample = (size_t)2 * p.n;
-    const size_t frame = (size_t)batch * sample;
-    const size_t frame_bytes = frame * sizeof(T);
-    T* adj = static_cast<T*>(ws);                          // adjoint trajectory [T+1][B][2][*S]
-    Workspace w;
-    w.partials = reinterpret_cast<double*>(static_cast<unsigned char*>(ws) + align_up((size_t)(T_steps + 1) * frame_bytes, 256));
-    w.partials_bytes = batch_partials_bytes(p, batch);
-    auto has = [&](int t) { return !mask || mask[t]; };
-    int t_top = T_steps;
-    while (t_top > 0 && !has(t_top)) --t_top;
-    // dL/dh of one frame that no later step injects (the top frame): a copy, or -- loss form -- a_b * (h - target)
-    // (sparse observations: target_c + cframe(t) is frame t's compact target)
-    auto ctarget = [&](int t) -> const T* { return target_c ? target_c + oh.cframe[(size_t)t] : nullptr; };
-    auto top_frame = [&](int t, T* dst) -> hipError_t {
-        if (!loss) return hipMemcpyAsync(dst, g_traj + (size_t)t * frame, frame_bytes, hipMemcpyDeviceToDevice, st);
-        if (obs) return obs_grad_frame_b<T>(traj + (size_t)t * frame, ctarget(t), dst, p, batch, oh.lat, st);
-        return loss_grad_frame_b<T>(traj + (size_t)t * frame, p.loss.mode == 2 ? g_traj + (size_t)t * frame : nullptr, dst, p, batch, st);
-    };
-    if (t_top == 0) {
-        if (has(0)) return (int)top_frame(0, g_h0);
-        return (int)hipMemsetAsync(g_h0, 0, frame_bytes, st);
-    }
-    if (hipError_t e = hipMemsetAsync(w.partials, 0, w.partials_bytes, st)) return (int)e;
-    const bool tile = batch_tile<T>(p, batch, {traj, g_traj, g_h0, adj}, true);
-    const bool fuse = tile ? tile_fuse_ok<T>(p)
-                           : (!p.opt.skip_wgrad && (p.opt.fuse_wgrad == 1 || (p.opt.fuse_wgrad == 2 && hc == 0)));
-    // (the direct sweep with fused sums reads the top frame's dL/dtraj where it lies, as rollout_bwd_impl does; in loss form
-    // there is no such frame to read)
-    const T* top_in_place = (!tile && fuse && !loss) ? g_traj + (size_t)t_top * frame : nullptr;
-    if (!top_in_place)
-        if (hipError_t e = top_frame(t_top, adj + (size_t)t_top * frame)) return (int)e;
-    unsigned rows = 0;
-    int t_cur = t_top;
-    if (tile) {
-        const int K = (p.opt.tile_k == 8 && p.hc != 0) ? 4 : p.opt.tile_k;
-        rows = (unsigned)tile_count<T>(p, true) * (unsigned)batch;
-        for (; t_cur - K >= 0; t_cur -= K) {
-            unsigned m = 0;
-            for (int q = 0; q < K; ++q) if (has(t_cur - 1 - q)) m |= 1u << q;
-            pi::ObsTile ob{};
-            if (obs) ob = obs_tile(oh, m, t_cur, K);
-            if (hipError_t e = adj_tile_b<T>(traj + (size_t)t_cur * frame, g_traj + (size_t)t_cur * frame, adj + (size_t)t_cur * frame,
-                                             m, g_h0, t_cur == K ? K : 0, w.partials, P, p, batch, st, -1, obs ? &ob : nullptr))
-                return (int)e;
-        }
-    }
-    for (int t = t_cur; t >= 1; --t) {
-        T* dst = (t == 1) ? g_h0 : adj + (size_t)(t - 1) * frame;
-        const T* inj = has(t - 1) ? g_traj + (size_t)(t - 1) * frame : nullptr;
-        if (obs && inj && target_c) inj = ctarget(t - 1);   // (without a target the pointer only says "inside the loss")
-        const T* gin = (top_in_place && t == t_top) ? top_in_place : adj + (size_t)t * frame;
-        const pi::ObsLat* ol = obs ? &oh.lat : nullptr;
-        unsigned r2 = 0;
-        hipError_t e = fuse ? step_bwd_b<T, true>(traj + (size_t)(t - 1) * frame, gin, inj, dst, w.partials, P, p, batch, st, &r2, -1, ol)
-                            : step_bwd_b<T, false>(traj + (size_t)(t - 1) * frame, gin, inj, dst, w.partials, P, p, batch, st, &r2, -1, ol);
-        if (e) return (int)e;
-        if (r2 > rows) rows = r2;
-    }
-    if (p.opt.skip_wgrad || fuse) return (int)finish_grads(w, rows, hc, param_grad, st);
-    // time-parallel branch gradients over the flattened frame index f = t * B + b: state frame f pairs with adjoint frame f + B,
-    // i.e. the unbatched kernels' pair (f' - 1, f') with the adjoint base moved B - 1 samples up, over f' in (0, t_top * B]
-    const bool vec_ok = (p.n % pi::vec_width<T>::value == 0) && p.opt.vec != 1 && (reinterpret_cast<uintptr_t>(traj) % 16 == 0);
-    const T* adj_b = adj + (size_t)(batch - 1) * sample;
-    unsigned wrows = 0;
-    hipError_t e = vec_ok ? launch_wgrad<T, pi::vec_width<T>::value>(traj, adj_b, w.partials, P, p, 0, t_top * batch, &wrows, st)
-                          : launch_wgrad<T, 1>(traj, adj_b, w.partials, P, p, 0, t_top * batch, &wrows, st);
-    if (e) return (int)e;
-    return (int)finish_grads(w, rows > wrows ? rows : wrows, hc, param_grad, st);
+    return sample_rollout_bwd<T>(traj, g_traj, mask, g_h0, param_grad, ws, P, p, T_steps, static_cast<hipStream_t>(stream), loss,
+                                 obs ? &oh : nullptr, target_c, Samples{batch, -1, true});
 }
 
 
 // ---- ensembles: B independent trajectories, one parameter block per sample (include/percnn_pi.h "Ensembles") ---------------
-// The launches of the batched path with the kernels' ensemble flavour: workgroup (x, b) reads block P + b * np.  Every
-// partial gradient row of sample b lies in [b * rows, (b + 1) * rows) -- `rows` is one bound for every launch of a call
-// (ens_rows_for) -- and pi_reduce_partials_kernel<true> sums the rows of each sample alone, in a fixed order, into param_grad[b].
+// The launches of the batched path with the kernels' ensemble flavour (Samples::ens_rows >= 0): workgroup (x, b) reads block
+// P + b * np.  Every partial gradient row of sample b lies in [b * rows, (b + 1) * rows) -- `rows` = Samples::ens_rows is one bound
+// for every launch of a call (ens_rows_for) -- and pi_reduce_partials_kernel<true> sums the rows of each sample alone, in a fixed
+// order, into param_grad[b].
 int ens_problem(int hc, int ndim, const int64_t* shape, int batch, Problem& p, const char* options, bool launches = true)
 {
     if (hc == -1) return PERCNN_PI_EINVAL;                  // the advective block has no ensemble flavour
     return batch_problem(hc, ndim, shape, batch, p, options, launches);
-}
-
-// workgroups per sample of the ensemble gradient pass: launch_wgrad's count for the steps of the whole batch, split over the
-// samples (the same number of workgroups and chunks per lane as the batched pass over the flattened frame index)
-long ens_wgrad_blocks(const Problem& p, int batch, int t_top, int vec)
-{
-    const long total = (long)t_top * batch * (p.n / vec);
-    long nb = (total + 256L * 16 - 1) / (256L * 16);
-    if (nb > p.opt.wgrad_blocks) nb = p.opt.wgrad_blocks;
-    nb = (nb + batch - 1) / batch;
-    return nb < 1 ? 1 : nb;
 }
 
 // partial rows per sample: the most that any launch of the call writes for one sample -- the tile sweep one per tile, the direct
@@ -3225,44 +3141,96 @@ hipError_t ens_finish_grads(const double* partials, int rows, int batch, int hc,
     return hipGetLastError();
 }
 
-// time-parallel branch gradients of all samples, ONE launch per hidden-channel group (sample = grid z; launch_wgrad_pass)
-template <typename T, int JC, int NS, int VEC>
-hipError_t launch_wgrad_ens_pass(const T* traj, const T* adj, double* partials, const T* P, const Problem& p, int batch, int t_top,
-                                 int j0, unsigned nb, int rows, hipStream_t st)
+// The reverse sweep of both flavours, entered below the argument checks of batch_rollout_bwd_impl / ens_rollout_bwd_impl.  `ws`
+// holds the adjoint trajectory and the partial rows (batch_rollout_workspace_bytes); oh != nullptr: the sparse-observation loss
+// form, target_c its compact target or nullptr.  s.ens_rows >= 0 asks for the ensemble flavour; the row count is fixed here.
+// The flavours part in four places, marked (1) .. (4).
+template <typename T>
+int sample_rollout_bwd(const T* traj, const T* g_traj, const unsigned char* mask, T* g_h0, double* param_grad, void* ws, const T* P,
+                       const Problem& p, int T_steps, hipStream_t st, const pi::LossInj* loss, const ObsHost* oh, const T* target_c,
+                       Samples s)
 {
-    const int block = 256;
-    const size_t lds = (size_t)(block / pi::WAVE) * NS * (10 * JC + 1) * sizeof(T);
-    hipLaunchKernelGGL((pi::pi_wgrad_kernel<T, JC, NS, VEC, long, int>), dim3(nb, NS == 2 ? 1 : 2, (unsigned)batch), dim3(block), lds, st,
-                       traj, adj, partials, P, (long)p.n, (long)p.n, 0L, 0, t_top, p.hc, j0, (long)batch * 2 * p.n, rows);
-    return hipGetLastError();
-}
-
-// steps (0, t_top] of every sample: state frame t-1 and adjoint frame t of sample b at (t-1) * B + b and t * B + b (launch_wgrad)
-template <typename T, int VEC>
-hipError_t launch_wgrad_ens(const T* traj, const T* adj, double* partials, const T* P, const Problem& p, int batch, int t_top,
-                            int rows, hipStream_t st)
-{
-    const unsigned nb = (unsigned)ens_wgrad_blocks(p, batch, t_top, VEC);
-    if (p.hc == 0) {                                           // pre-contracted mode: coefficient moments
-        const size_t lds = (size_t)(256 / pi::WAVE) * 20 * sizeof(T);
-        hipLaunchKernelGGL((pi::pi_moments_kernel<T, VEC, long, int>), dim3(nb, (unsigned)batch), dim3(256), lds, st, traj, adj, partials,
-                           P, (long)p.n, (long)p.n, 0L, 0, t_top, (long)batch * 2 * p.n, rows);
-        return hipGetLastError();
+    const bool obs = oh != nullptr, ens = s.ens();
+    const int batch = s.batch, hc = p.hc;
+    const size_t sample = (size_t)2 * p.n;
+    const size_t frame = (size_t)batch * sample;
+    const size_t frame_bytes = frame * sizeof(T);
+    T* adj = static_cast<T*>(ws);                          // adjoint trajectory [T+1][B][2][*S]
+    Workspace w;
+    w.partials = reinterpret_cast<double*>(static_cast<unsigned char*>(ws) + align_up((size_t)(T_steps + 1) * frame_bytes, 256));
+    w.partials_bytes = batch_partials_bytes(p, batch);
+    auto has = [&](int t) { return !mask || mask[t]; };
+    int t_top = T_steps;
+    while (t_top > 0 && !has(t_top)) --t_top;
+    // dL/dh of one frame that no later step injects (the top frame): a copy, or -- loss form -- a_b * (h - target)
+    // (sparse observations: target_c + cframe(t) is frame t's compact target)
+    auto ctarget = [&](int t) -> const T* { return target_c ? target_c + oh->cframe[(size_t)t] : nullptr; };
+    auto top_frame = [&](int t, T* dst) -> hipError_t {
+        if (!loss) return hipMemcpyAsync(dst, g_traj + (size_t)t * frame, frame_bytes, hipMemcpyDeviceToDevice, st);
+        if (obs) return obs_grad_frame_b<T>(traj + (size_t)t * frame, ctarget(t), dst, p, batch, oh->lat, st);
+        return loss_grad_frame_b<T>(traj + (size_t)t * frame, p.loss.mode == 2 ? g_traj + (size_t)t * frame : nullptr, dst, p, batch, st);
+    };
+    if (t_top == 0) {
+        if (has(0)) return (int)top_frame(0, g_h0);
+        return (int)hipMemsetAsync(g_h0, 0, frame_bytes, st);
     }
-    if (p.hc == 2) return launch_wgrad_ens_pass<T, 2, 2, VEC>(traj, adj, partials, P, p, batch, t_top, 0, nb, rows, st);
-    if (p.hc == 4) return launch_wgrad_ens_pass<T, 4, 2, VEC>(traj, adj, partials, P, p, batch, t_top, 0, nb, rows, st);
-    const int jc = p.hc % 8 == 0 ? 8 : p.hc % 4 == 0 ? 4 : p.hc % 2 == 0 ? 2 : 1;
-    for (int j0 = 0; j0 < p.hc; j0 += jc) {
-        hipError_t e;
-        switch (jc) {
-            case 8:  e = launch_wgrad_ens_pass<T, 8, 1, VEC>(traj, adj, partials, P, p, batch, t_top, j0, nb, rows, st); break;
-            case 4:  e = launch_wgrad_ens_pass<T, 4, 1, VEC>(traj, adj, partials, P, p, batch, t_top, j0, nb, rows, st); break;
-            case 2:  e = launch_wgrad_ens_pass<T, 2, 1, VEC>(traj, adj, partials, P, p, batch, t_top, j0, nb, rows, st); break;
-            default: e = launch_wgrad_ens_pass<T, 1, 1, VEC>(traj, adj, partials, P, p, batch, t_top, j0, nb, rows, st); break;
+    const bool tile = batch_tile<T>(p, batch, {traj, g_traj, g_h0, adj}, true);
+    const bool fuse = tile ? tile_fuse_ok<T>(p)
+                           : (!p.opt.skip_wgrad && (p.opt.fuse_wgrad == 1 || (p.opt.fuse_wgrad == 2 && hc == 0)));
+    const bool pass = !p.opt.skip_wgrad && !fuse;          // time-parallel gradient pass after the sweep
+    // (1) the partial rows: batched -- all of them, the launches say how many they wrote (`rows`); ensemble -- ens_rows per sample
+    if (ens) s.ens_rows = ens_rows_for<T>(p, batch, tile, pass ? t_top : 0);
+    if (hipError_t e = hipMemsetAsync(w.partials, 0, ens ? (size_t)batch * s.ens_rows * pi::nparams(hc) * sizeof(double) : w.partials_bytes, st))
+        return (int)e;
+    // (the direct sweep with fused sums reads the top frame's dL/dtraj where it lies, as rollout_bwd_impl does; in loss form
+    // there is no such frame to read)
+    const T* top_in_place = (!tile && fuse && !loss) ? g_traj + (size_t)t_top * frame : nullptr;
+    if (!top_in_place)
+        if (hipError_t e = top_frame(t_top, adj + (size_t)t_top * frame)) return (int)e;
+    unsigned rows = 0;
+    int t_cur = t_top;
+    if (tile) {
+        const int K = (p.opt.tile_k == 8 && p.hc != 0) ? 4 : p.opt.tile_k;
+        rows = (unsigned)tile_count<T>(p, true) * (unsigned)batch;
+        for (; t_cur - K >= 0; t_cur -= K) {
+            unsigned m = 0;
+            for (int q = 0; q < K; ++q) if (has(t_cur - 1 - q)) m |= 1u << q;
+            pi::ObsTile ob{};
+            if (obs) ob = obs_tile(*oh, m, t_cur, K);
+            if (hipError_t e = adj_tile<T>(traj + (size_t)t_cur * frame, g_traj + (size_t)t_cur * frame, adj + (size_t)t_cur * frame,
+                                           m, g_h0, t_cur == K ? K : 0, w.partials, P, p, st, s, obs ? &ob : nullptr))
+                return (int)e;
         }
-        if (e) return e;
     }
-    return hipSuccess;
+    for (int t = t_cur; t >= 1; --t) {
+        T* dst = (t == 1) ? g_h0 : adj + (size_t)(t - 1) * frame;
+        const T* inj = has(t - 1) ? g_traj + (size_t)(t - 1) * frame : nullptr;
+        if (obs && inj && target_c) inj = ctarget(t - 1);   // (without a target the pointer only says "inside the loss")
+        const T* gin = (top_in_place && t == t_top) ? top_in_place : adj + (size_t)t * frame;
+        const pi::ObsLat* ol = obs ? &oh->lat : nullptr;
+        unsigned r2 = 0;                                    // (2) batched: rows tracked from the launches; ensemble: fixed above
+        unsigned* const track = ens ? nullptr : &r2;
+        hipError_t e = fuse ? step_bwd_b<T, true>(traj + (size_t)(t - 1) * frame, gin, inj, dst, w.partials, P, p, st, s, track, ol)
+                            : step_bwd_b<T, false>(traj + (size_t)(t - 1) * frame, gin, inj, dst, w.partials, P, p, st, s, track, ol);
+        if (e) return (int)e;
+        if (r2 > rows) rows = r2;
+    }
+    if (pass) {
+        // (3) time-parallel branch gradients.  Ensemble: per sample, on grid y / z (launch_wgrad).  Batched: over the flattened frame
+        // index f = t * B + b -- state frame f pairs with adjoint frame f + B, i.e. the unbatched kernels' pair (f' - 1, f') with the
+        // adjoint base moved B - 1 samples up, over f' in (0, t_top * B]
+        const bool vec_ok = (p.n % pi::vec_width<T>::value == 0) && p.opt.vec != 1 && (reinterpret_cast<uintptr_t>(traj) % 16 == 0);
+        const T* adj_w = ens ? adj : adj + (size_t)(batch - 1) * sample;
+        const int t_hi = ens ? t_top : t_top * batch;
+        unsigned wrows = 0;
+        hipError_t e = vec_ok ? launch_wgrad<T, pi::vec_width<T>::value>(traj, adj_w, w.partials, P, p, 0, t_hi, &wrows, st, s)
+                              : launch_wgrad<T, 1>(traj, adj_w, w.partials, P, p, 0, t_hi, &wrows, st, s);
+        if (e) return (int)e;
+        if (wrows > rows) rows = wrows;
+    }
+    // (4) one block of gradients, or one per sample
+    if (ens) return (int)ens_finish_grads(w.partials, s.ens_rows, batch, hc, param_grad, st);
+    return (int)finish_grads(w, rows, hc, param_grad, st);
 }
 
 template <typename T>
@@ -3273,7 +3241,7 @@ int ens_step_fwd_impl(const T* h, T* out, const T* P, int hc, int ndim, const in
     if (int rc = ens_problem(hc, ndim, shape, batch, p, options)) return rc;
     if (!h || !out || !P || h == out || P == out) return PERCNN_PI_EINVAL;
     if (batch == 1) return step_fwd_impl<T>(h, out, P, hc, ndim, shape, stream, false, 2, 0, options);
-    return (int)step_fwd_b<T>(h, out, P, p, batch, static_cast<hipStream_t>(stream), 0);
+    return (int)step_fwd_b<T>(h, out, P, p, static_cast<hipStream_t>(stream), Samples{batch, 0, true});
 }
 
 template <typename T>
@@ -3294,7 +3262,7 @@ int ens_step_bwd_impl(const T* h, const T* g_out, const T* g_inj, T* g_in, doubl
                                                  2 * align_up((size_t)batch * 2 * p.n * sizeof(T), 256));
     const int rows = ens_rows_for<T>(p, batch, false, 0);
     if (hipError_t e = hipMemsetAsync(partials, 0, (size_t)batch * rows * pi::nparams(hc) * sizeof(double), st)) return (int)e;
-    if (hipError_t e = step_bwd_b<T, true>(h, g_out, g_inj, g_in, partials, P, p, batch, st, nullptr, rows)) return (int)e;
+    if (hipError_t e = step_bwd_b<T, true>(h, g_out, g_inj, g_in, partials, P, p, st, Samples{batch, rows, true}, nullptr)) return (int)e;
     return (int)ens_finish_grads(partials, rows, batch, hc, param_grad, st);
 }
 
@@ -3306,17 +3274,7 @@ int ens_rollout_fwd_impl(T* traj, const T* P, int hc, int ndim, const int64_t* s
     if (int rc = ens_problem(hc, ndim, shape, batch, p, options)) return rc;
     if (!traj || !P || T_steps < 0 || P == traj) return PERCNN_PI_EINVAL;
     if (batch == 1) return rollout_fwd_impl<T>(traj, P, hc, ndim, shape, T_steps, stream, options);
-    auto st = static_cast<hipStream_t>(stream);
-    const size_t frame = (size_t)batch * 2 * p.n;          // frame t of all samples: [B][2][*S]
-    int t = 0;
-    if (batch_tile<T>(p, batch, {traj}, false)) {
-        const int K = (p.opt.tile_k == 8 && p.hc != 0) ? 4 : p.opt.tile_k;
-        for (; t + K <= T_steps; t += K)
-            if (hipError_t e = fwd_tile_b<T>(traj + (size_t)t * frame, P, p, batch, st, 0)) return (int)e;
-    }
-    for (; t < T_steps; ++t)
-        if (hipError_t e = step_fwd_b<T>(traj + (size_t)t * frame, traj + (size_t)(t + 1) * frame, P, p, batch, st, 0)) return (int)e;
-    return 0;
+    return sample_rollout_fwd<T>(traj, P, p, T_steps, static_cast<hipStream_t>(stream), Samples{batch, 0, true});
 }
 
 template <typename T>
@@ -3347,64 +3305,8 @@ int ens_rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* ma
                                    options, loss);
     if (!ws || ws_bytes < batch_rollout_workspace_bytes(p, batch, T_steps, sizeof(T)) || (reinterpret_cast<uintptr_t>(ws) % 16))
         return PERCNN_PI_EWORKSPACE;
-    auto st = static_cast<hipStream_t>(stream);
-    const size_t frame = (size_t)batch * 2 * p.n;
-    const size_t frame_bytes = frame * sizeof(T);
-    T* adj = static_cast<T*>(ws);                          // adjoint trajectory [T+1][B][2][*S]
-    double* partials = reinterpret_cast<double*>(static_cast<unsigned char*>(ws) + align_up((size_t)(T_steps + 1) * frame_bytes, 256));
-    auto has = [&](int t) { return !mask || mask[t]; };
-    int t_top = T_steps;
-    while (t_top > 0 && !has(t_top)) --t_top;
-    auto ctarget = [&](int t) -> const T* { return target_c ? target_c + oh.cframe[(size_t)t] : nullptr; };
-    auto top_frame = [&](int t, T* dst) -> hipError_t {     // as in batch_rollout_bwd_impl
-        if (!loss) return hipMemcpyAsync(dst, g_traj + (size_t)t * frame, frame_bytes, hipMemcpyDeviceToDevice, st);
-        if (obs) return obs_grad_frame_b<T>(traj + (size_t)t * frame, ctarget(t), dst, p, batch, oh.lat, st);
-        return loss_grad_frame_b<T>(traj + (size_t)t * frame, p.loss.mode == 2 ? g_traj + (size_t)t * frame : nullptr, dst, p, batch, st);
-    };
-    if (t_top == 0) {
-        if (has(0)) return (int)top_frame(0, g_h0);
-        return (int)hipMemsetAsync(g_h0, 0, frame_bytes, st);
-    }
-    const bool tile = batch_tile<T>(p, batch, {traj, g_traj, g_h0, adj}, true);
-    const bool fuse = tile ? tile_fuse_ok<T>(p)
-                           : (!p.opt.skip_wgrad && (p.opt.fuse_wgrad == 1 || (p.opt.fuse_wgrad == 2 && hc == 0)));
-    const bool pass = !p.opt.skip_wgrad && !fuse;          // time-parallel gradient pass after the sweep
-    const int rows = ens_rows_for<T>(p, batch, tile, pass ? t_top : 0);
-    if (hipError_t e = hipMemsetAsync(partials, 0, (size_t)batch * rows * pi::nparams(hc) * sizeof(double), st)) return (int)e;
-    // (the direct sweep with fused sums reads the top frame's dL/dtraj where it lies, as rollout_bwd_impl does; not in loss form)
-    const T* top_in_place = (!tile && fuse && !loss) ? g_traj + (size_t)t_top * frame : nullptr;
-    if (!top_in_place)
-        if (hipError_t e = top_frame(t_top, adj + (size_t)t_top * frame)) return (int)e;
-    int t_cur = t_top;
-    if (tile) {
-        const int K = (p.opt.tile_k == 8 && p.hc != 0) ? 4 : p.opt.tile_k;
-        for (; t_cur - K >= 0; t_cur -= K) {
-            unsigned m = 0;
-            for (int q = 0; q < K; ++q) if (has(t_cur - 1 - q)) m |= 1u << q;
-            pi::ObsTile ob{};
-            if (obs) ob = obs_tile(oh, m, t_cur, K);
-            if (hipError_t e = adj_tile_b<T>(traj + (size_t)t_cur * frame, g_traj + (size_t)t_cur * frame, adj + (size_t)t_cur * frame,
-                                             m, g_h0, t_cur == K ? K : 0, partials, P, p, batch, st, rows, obs ? &ob : nullptr))
-                return (int)e;
-        }
-    }
-    for (int t = t_cur; t >= 1; --t) {
-        T* dst = (t == 1) ? g_h0 : adj + (size_t)(t - 1) * frame;
-        const T* inj = has(t - 1) ? g_traj + (size_t)(t - 1) * frame : nullptr;
-        if (obs && inj && target_c) inj = ctarget(t - 1);
-        const T* gin = (top_in_place && t == t_top) ? top_in_place : adj + (size_t)t * frame;
-        const pi::ObsLat* ol = obs ? &oh.lat : nullptr;
-        hipError_t e = fuse ? step_bwd_b<T, true>(traj + (size_t)(t - 1) * frame, gin, inj, dst, partials, P, p, batch, st, nullptr, rows, ol)
-                            : step_bwd_b<T, false>(traj + (size_t)(t - 1) * frame, gin, inj, dst, partials, P, p, batch, st, nullptr, rows, ol);
-        if (e) return (int)e;
-    }
-    if (pass) {
-        const bool vec_ok = (p.n % pi::vec_width<T>::value == 0) && p.opt.vec != 1 && (reinterpret_cast<uintptr_t>(traj) % 16 == 0);
-        hipError_t e = vec_ok ? launch_wgrad_ens<T, pi::vec_width<T>::value>(traj, adj, partials, P, p, batch, t_top, rows, st)
-                              : launch_wgrad_ens<T, 1>(traj, adj, partials, P, p, batch, t_top, rows, st);
-        if (e) return (int)e;
-    }
-    return (int)ens_finish_grads(partials, rows, batch, hc, param_grad, st);
+    return sample_rollout_bwd<T>(traj, g_traj, mask, g_h0, param_grad, ws, P, p, T_steps, static_cast<hipStream_t>(stream), loss,
+                                 obs ? &oh : nullptr, target_c, Samples{batch, 0, true});
 }
 
 
@@ -3991,23 +3893,20 @@ unsigned batch_sqerr_slots(int batch) { return (unsigned)std::max(8, 1024 / batc
 
 // out[b] = scale * sum over the frames with mask[f] != 0 of sum_x (traj[f][b] - target[f][b])^2, traj / target [nframes][B][2][*S]:
 // per run of selected frames one launch of grid (nb, B) that adds to the slots of each sample alone (launches of one stream are
-// ordered and nb is a function of the arguments: bit-identical from run to run), then one wave per sample sums its slots
+// ordered and nb is a function of the arguments: bit-identical from run to run), then one wave per sample sums its slots.
+// oh != nullptr: the sparse-observation form -- the sum runs over the lattice points alone and `target` is compact in space and
+// time, [n][B][2][*Sc].  All strides 1: the lattice is the grid and the run goes through the dense kernel with its 16-byte lanes,
+// so the result is the dense form's bit for bit.  ws: batch * batch_sqerr_slots(batch) doubles.
 template <typename T>
-int batch_sqerr_impl(const T* traj, const T* target, const unsigned char* mask, int nframes, int ndim, const int64_t* shape,
-                     int batch, double scale, T* out, void* ws, size_t ws_bytes, void* stream)
+int sample_sqerr(const T* traj, const T* target, const unsigned char* mask, int nframes, const Problem& p, int batch, const ObsHost* oh,
+                 double scale, T* out, void* ws, hipStream_t st)
 {
-    if (batch < 1 || batch > MAX_BATCH) return PERCNN_PI_EINVAL;
-    if (batch == 1) return sqerr_impl<T>(traj, target, mask, nframes, ndim, shape, scale, out, ws, ws_bytes, stream);
-    Problem p;
-    if (int rc = batch_problem(0, ndim, shape, batch, p, nullptr, false)) return rc;
-    if (!traj || !out || nframes < 0 || out == traj || out == target) return PERCNN_PI_EINVAL;
     const unsigned slots = batch_sqerr_slots(batch);
-    if (!ws || ws_bytes < (size_t)batch * slots * sizeof(double) || reinterpret_cast<uintptr_t>(ws) % 8) return PERCNN_PI_EWORKSPACE;
-    auto st = static_cast<hipStream_t>(stream);
-    const long sample = 2 * p.n, frame = (long)batch * sample;
+    const long sample = 2 * p.n, frame = (long)batch * sample, cframe = oh ? (long)batch * 2 * oh->lat.cs : 0;
     double* partials = static_cast<double*>(ws);
     if (hipError_t e = hipMemsetAsync(partials, 0, (size_t)batch * slots * sizeof(double), st)) return (int)e;
-    const bool v16 = sample % pi::vec_width<T>::value == 0 && (sample * sizeof(T)) % 16 == 0 &&
+    const bool dense = !oh || oh->lat.cs == p.n;
+    const bool v16 = dense && sample % pi::vec_width<T>::value == 0 && (sample * sizeof(T)) % 16 == 0 &&
                      reinterpret_cast<uintptr_t>(traj) % 16 == 0 && (!target || reinterpret_cast<uintptr_t>(target) % 16 == 0);
     unsigned used = 1;                                     // slots of a sample that any launch wrote
     int f = 0;
@@ -4017,63 +3916,15 @@ int batch_sqerr_impl(const T* traj, const T* target, const unsigned char* mask, 
         while (g < nframes && (!mask || mask[g])) ++g;
         if (g > f) {
             const T* tr = traj + (size_t)f * frame;
-            const T* tg = target ? target + (size_t)f * frame : nullptr;
+            const T* tg = !target ? nullptr : oh ? target + oh->cframe[(size_t)f] : target + (size_t)f * frame;
             // a workgroup per 1024 chunks of the sample's part of the run (four per lane), at most the sample's slots
-            const long chunks = (long)(g - f) * (sample / (v16 ? pi::vec_width<T>::value : 1));
-            const unsigned nb = (unsigned)std::min<long>(slots, (chunks + 1023) / 1024);
-            if (nb > used) used = nb;
-            if (v16) hipLaunchKernelGGL((pi::pi_sqerr_kernel<T, pi::vec_width<T>::value, long, int, int>), dim3(nb, (unsigned)batch), dim3(256),
-                                        0, st, tr, tg, sample, partials, frame, g - f, (int)slots);
-            else     hipLaunchKernelGGL((pi::pi_sqerr_kernel<T, 1, long, int, int>), dim3(nb, (unsigned)batch), dim3(256), 0, st, tr, tg,
-                                        sample, partials, frame, g - f, (int)slots);
-            if (hipError_t e = hipGetLastError()) return (int)e;
-        }
-        f = g;
-    }
-    hipLaunchKernelGGL((pi::pi_sqerr_finish_kernel<T, int>), dim3((unsigned)batch), dim3(64), 0, st, partials, (int)used, scale, out,
-                       (int)slots);
-    return (int)hipGetLastError();
-}
-
-// the sparse-observation form of batch_sqerr_impl: out[b] = scale * sum over the selected frames and the lattice points of
-// (traj - target_c)^2, target_c [n][B][2][*Sc] compact in space and time.  Same slots, launch order and finishing pass, for one
-// sample too.  All strides 1: the lattice is the grid and the run goes through the dense kernel with its 16-byte lanes, so the
-// result is batch_sqerr_impl's bit for bit.
-template <typename T>
-int batch_obs_sqerr_impl(const T* traj, const T* target_c, const unsigned char* mask, int nframes, int ndim, const int64_t* shape,
-                         const int* strides, int batch, double scale, T* out, void* ws, size_t ws_bytes, void* stream)
-{
-    if (batch < 1 || batch > MAX_BATCH) return PERCNN_PI_EINVAL;
-    Problem p;
-    if (int rc = batch_problem(0, ndim, shape, batch, p, nullptr, false)) return rc;
-    if (!traj || !out || nframes < 0 || out == traj || out == target_c) return PERCNN_PI_EINVAL;
-    ObsHost oh;
-    if (int rc = make_obs(p, batch, strides, target_c, mask, nframes, oh)) return rc;
-    const unsigned slots = batch_sqerr_slots(batch);
-    if (!ws || ws_bytes < (size_t)batch * slots * sizeof(double) || reinterpret_cast<uintptr_t>(ws) % 8) return PERCNN_PI_EWORKSPACE;
-    auto st = static_cast<hipStream_t>(stream);
-    const long sample = 2 * p.n, frame = (long)batch * sample, cframe = (long)batch * 2 * oh.lat.cs;
-    double* partials = static_cast<double*>(ws);
-    if (hipError_t e = hipMemsetAsync(partials, 0, (size_t)batch * slots * sizeof(double), st)) return (int)e;
-    const bool dense = oh.lat.cs == p.n;
-    const bool v16 = dense && sample % pi::vec_width<T>::value == 0 && (sample * sizeof(T)) % 16 == 0 &&
-                     reinterpret_cast<uintptr_t>(traj) % 16 == 0 && (!target_c || reinterpret_cast<uintptr_t>(target_c) % 16 == 0);
-    unsigned used = 1;
-    int f = 0;
-    while (f < nframes) {
-        while (f < nframes && mask && !mask[f]) ++f;
-        int g = f;
-        while (g < nframes && (!mask || mask[g])) ++g;
-        if (g > f) {
-            const T* tr = traj + (size_t)f * frame;
-            const T* tg = target_c ? target_c + oh.cframe[(size_t)f] : nullptr;
-            const long chunks = (long)(g - f) * (dense ? sample / (v16 ? pi::vec_width<T>::value : 1) : 2 * oh.lat.cs);
+            const long chunks = (long)(g - f) * (dense ? sample / (v16 ? pi::vec_width<T>::value : 1) : 2 * oh->lat.cs);
             const unsigned nb = (unsigned)std::min<long>(slots, (chunks + 1023) / 1024);
             if (nb > used) used = nb;
             const dim3 grid(nb, (unsigned)batch);
             if (!dense)
                 hipLaunchKernelGGL((pi::pi_sqerr_kernel<T, 1, long, int, int, long, int, int, pi::ObsLat>), grid, dim3(256), 0, st, tr, tg,
-                                   sample, partials, frame, g - f, (int)slots, cframe, (int)(p.ndim == 3 ? p.n1 : p.n0), (int)p.W, oh.lat);
+                                   sample, partials, frame, g - f, (int)slots, cframe, (int)(p.ndim == 3 ? p.n1 : p.n0), (int)p.W, oh->lat);
             else if (v16)
                 hipLaunchKernelGGL((pi::pi_sqerr_kernel<T, pi::vec_width<T>::value, long, int, int>), grid, dim3(256), 0, st, tr, tg,
                                    sample, partials, frame, g - f, (int)slots);
@@ -4087,6 +3938,37 @@ int batch_obs_sqerr_impl(const T* traj, const T* target_c, const unsigned char* 
     hipLaunchKernelGGL((pi::pi_sqerr_finish_kernel<T, int>), dim3((unsigned)batch), dim3(64), 0, st, partials, (int)used, scale, out,
                        (int)slots);
     return (int)hipGetLastError();
+}
+
+// the dense loss value per sample; one sample is the unbatched pass
+template <typename T>
+int batch_sqerr_impl(const T* traj, const T* target, const unsigned char* mask, int nframes, int ndim, const int64_t* shape,
+                     int batch, double scale, T* out, void* ws, size_t ws_bytes, void* stream)
+{
+    if (batch < 1 || batch > MAX_BATCH) return PERCNN_PI_EINVAL;
+    if (batch == 1) return sqerr_impl<T>(traj, target, mask, nframes, ndim, shape, scale, out, ws, ws_bytes, stream);
+    Problem p;
+    if (int rc = batch_problem(0, ndim, shape, batch, p, nullptr, false)) return rc;
+    if (!traj || !out || nframes < 0 || out == traj || out == target) return PERCNN_PI_EINVAL;
+    if (!ws || ws_bytes < (size_t)batch * batch_sqerr_slots(batch) * sizeof(double) || reinterpret_cast<uintptr_t>(ws) % 8)
+        return PERCNN_PI_EWORKSPACE;
+    return sample_sqerr<T>(traj, target, mask, nframes, p, batch, nullptr, scale, out, ws, static_cast<hipStream_t>(stream));
+}
+
+// the sparse-observation loss value per sample: the same slots, launch order and finishing pass, for one sample too
+template <typename T>
+int batch_obs_sqerr_impl(const T* traj, const T* target_c, const unsigned char* mask, int nframes, int ndim, const int64_t* shape,
+                         const int* strides, int batch, double scale, T* out, void* ws, size_t ws_bytes, void* stream)
+{
+    if (batch < 1 || batch > MAX_BATCH) return PERCNN_PI_EINVAL;
+    Problem p;
+    if (int rc = batch_problem(0, ndim, shape, batch, p, nullptr, false)) return rc;
+    if (!traj || !out || nframes < 0 || out == traj || out == target_c) return PERCNN_PI_EINVAL;
+    ObsHost oh;
+    if (int rc = make_obs(p, batch, strides, target_c, mask, nframes, oh)) return rc;
+    if (!ws || ws_bytes < (size_t)batch * batch_sqerr_slots(batch) * sizeof(double) || reinterpret_cast<uintptr_t>(ws) % 8)
+        return PERCNN_PI_EWORKSPACE;
+    return sample_sqerr<T>(traj, target_c, mask, nframes, p, batch, &oh, scale, out, ws, static_cast<hipStream_t>(stream));
 }
 }  // namespace
 
