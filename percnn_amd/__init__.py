@@ -6,11 +6,11 @@ update, their adjoint, and the T-step rollout -- as hand-written HIP kernels beh
 (``include/percnn_pi.h``), with drop-in ``RCNNCell`` / ``RCNN`` modules on top.
 
 Layout:  ``csrc/`` HIP kernels + the C-ABI translation units (pi_abi.hip: base block, slabs, physics residual;
-pi_s1_abi.hip: Stage-1 block on the matrix cores; pi_up3d_abi.hip: 3D IC-generator contraction; pi_disc_abi.hip: Stage-2 library moments) ->
+pi_s1_abi.hip: Stage-1 block on the matrix cores; pi_up3d_abi.hip: 3D IC-generator contraction; pi_disc_abi.hip: Stage-2 library moments; pi_lib_abi.hip: library cell) ->
 ``libpercnn_pi.so``;  ``_lib`` ctypes binding + build;  ``ops`` the registered ``torch.ops.percnn.*`` operators;
 ``functional`` raw calls + autograd front-end;  ``modules`` the reference's
 module interface;  ``stage1`` the Stage-1 cell;  ``slab`` multi-GPU slab decomposition;  ``physics`` physics-residual
-loss;  ``discovery`` Stage-2 library moments + STRidge;  ``synthetic`` initial states for benchmarks / tests.
+loss;  ``discovery`` Stage-2 library moments + STRidge;  ``library_cell`` Stage-3 cell over that library;  ``synthetic`` initial states for benchmarks / tests.
 """
 from ._lib import build, lib, set_option, LIB_PATH  # noqa: F401
 from .functional import (pi_step, pi_rollout, pack_params, contract_block, param_count, rollout_fwd_, rollout_bwd,  # noqa: F401
@@ -24,5 +24,7 @@ from . import slab, synthetic, physics, stage1, discovery  # noqa: F401
 from .stage1 import Stage1Cell  # noqa: F401
 from .physics import physics_loss_batched  # noqa: F401
 from .discovery import LIBRARY_TERMS, LibraryMoments, row_class, library_moments, stridge, train_stridge, discover  # noqa: F401
+from . import library_cell  # noqa: F401
+from .library_cell import LibraryCell  # noqa: F401
 
 __version__ = "0.1.0"

@@ -22,6 +22,7 @@ SOURCES = {
     "pi_s1_abi.hip": ["pi_s1.h", "pi_device.h", "pi_host.h", os.path.join(_INC, "percnn_pi.h"), os.path.join(_INC, "percnn_pi_stage1.h")],
     "pi_up3d_abi.hip": ["pi_up3d.h", "pi_device.h", os.path.join(_INC, "percnn_pi.h")],
     "pi_disc_abi.hip": ["pi_disc.h", os.path.join(_INC, "percnn_pi.h"), os.path.join(_INC, "percnn_pi_discovery.h")],
+    "pi_lib_abi.hip": ["pi_lib.h", os.path.join(_INC, "percnn_pi.h"), os.path.join(_INC, "percnn_pi_library_cell.h")],
 }
 
 # the PyTorch operator library + eager fast path (csrc/torch_ext.cpp: TORCH_LIBRARY(percnn) operators with C++ autograd,
@@ -79,6 +80,8 @@ EXPORTS = [
     "percnn_pi_s1_rollout_bwd_workspace_bytes", "percnn_pi_s1_rollout_bwd_f32", "percnn_pi_s1_set_option",
     "percnn_pi_conv3d_k5c8_f32", "percnn_pi_conv3d_k5c8_wgrad_workspace_bytes", "percnn_pi_conv3d_k5c8_wgrad_f32",
     "percnn_pi_library_moments_workspace_bytes", "percnn_pi_library_moments_f32", "percnn_pi_library_moments_f64",
+    "percnn_pi_lib_step_fwd_f64", "percnn_pi_lib_rollout_fwd_f64", "percnn_pi_lib_rollout_bwd_workspace_bytes",
+    "percnn_pi_lib_rollout_bwd_f64",
 ]
 
 
@@ -326,6 +329,12 @@ def lib() -> ctypes.CDLL:
         f = getattr(L, f"percnn_pi_library_moments_{suf}")
         f.restype = ci
         f.argtypes = [vp, i64, i64, i64p, ci, ci, cd, cd, ci, ctypes.c_uint32, u64, u64, vp, vp, vp, vp, vp, sz, vp]
+    L.percnn_pi_lib_step_fwd_f64.restype, L.percnn_pi_lib_step_fwd_f64.argtypes = ci, [vp, vp, vp, i64p, cd, cd, vp]
+    L.percnn_pi_lib_rollout_fwd_f64.restype, L.percnn_pi_lib_rollout_fwd_f64.argtypes = ci, [vp, vp, i64p, ci, cd, cd, vp]
+    L.percnn_pi_lib_rollout_bwd_workspace_bytes.restype = sz
+    L.percnn_pi_lib_rollout_bwd_workspace_bytes.argtypes = [i64p, ci]
+    L.percnn_pi_lib_rollout_bwd_f64.restype = ci
+    L.percnn_pi_lib_rollout_bwd_f64.argtypes = [vp, vp, ctypes.c_char_p, vp, vp, vp, sz, vp, i64p, ci, cd, cd, vp]
     # process-wide tuning defaults from the environment ("key=value,..."; the keys of percnn_pi_set_option) -- what a launcher
     # uses to A/B an option in worker processes it does not construct itself
     spec = os.environ.get("PERCNN_PI_OPTIONS", "")

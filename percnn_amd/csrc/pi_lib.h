@@ -1,0 +1,286 @@
+// Stage-3 rollouts of any equation over the Stage-2 candidate library (include/percnn_pi_library_cell.h).
+//
+//   next_s = h_s + dt * sum_{k<7} psi_k * q_{s,k},     q_{s,k} = sum_{m<10} C[s][m][k] * phi_m
+//   phi = [1, u, v, u^2, uv, v^2, u^3, u^2 v, u v^2, v^3]        psi = [1, u_x, u_y, v_x, v_y, lap_u, lap_v]
+// with the stencil expressions of disc::point_fields (pi_disc.h), so the library that discovers an equation and the cell
+// that integrates it evaluate the same numbers.  float64, periodic, one launch per step and per adjoint step.
+//
+// step_kernel     one point per lane: the radius-2 star of both species (18 loads), psi, phi, both updates in the pinned
+//                 order (plain multiplies and adds).  C is read with wave-uniform addresses (scalar loads); a column k whose ten
+//                 coefficients of a species are all zero is skipped by a wave-uniform branch.  Which columns those are comes
+//                 from one vote of the wave over the 140 entries (nonzero_mask): testing them one scalar load after the other
+//                 cost 4 us per step pair on the sparse Burgers equation, more than the skipped arithmetic saves.
+// adjoint_kernel  one 16 x 16 tile per workgroup, one point per lane.  With G the incoming adjoint state, a_s = dt G_s and
+//                 w_k = sum_s a_s q_{s,k}, the outgoing state is
+//                   G_s + inject_s + sum_{s',k} a_s' psi_k dq_{s',k}/dh_s  - D0 w_{s_x} - D1 w_{s_y} + Lap w_{lap_s}
+//                 q depends on the point's own (u, v) only, so w is evaluated ONCE per point of the tile plus its 2-wide star
+//                 halo into LDS (384 evaluations for 256 points) and the transposed stencils read it from there.
+//                 The same launch accumulates gC[s][m][k] += sum_p a_s phi_m psi_k with v_mfma_f64_16x16x4_f64: rows (s, m)
+//                 = 20 padded to two 16-row tiles, columns k = 7 padded to 16, K = 4 points per instruction.  Each lane
+//                 stages phi, a and psi of its point in LDS; lane l then feeds row / column l & 15 for the point l >> 4 of a
+//                 group of 4 (the operand map at the top of pi_disc.h; C/D: D[(lane >> 4) + 4 reg][lane & 15]).  Lanes
+//                 outside the grid stage zeros for a and psi, padding rows and columns feed zeros.
+// Partial sums: one row of 140 doubles per workgroup, each workgroup adds only to its own row, launch after launch in stream
+// order; finish_kernel sums the rows in a fixed order.  No floating-point atomics: the same call twice gives the same bits.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+namespace pi {
+namespace lib {
+
+constexpr int NA = 10, NB = 7, NCOEF = 2 * NA * NB;
+constexpr int NT = 256, NWAVES = NT / 64;
+constexpr int TS = 16, HALO = 2, LW = TS + 2 * HALO;   // adjoint tile, its LDS extent with the star halo
+constexpr int STG = 19;                                 // staged doubles per point: phi[10], a_u, a_v, psi[7]
+constexpr int FIN_NT = 192;
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+struct Geom {
+    int H, W;
+    long plane;
+    double dt, inv_12dx, inv_dx2;
+};
+
+__host__ __device__ inline int cidx(int s, int m, int k) { return (s * NA + m) * NB + k; }
+
+__device__ inline int wrapi(int v, int n)
+{
+    v %= n;
+    return v < 0 ? v + n : v;
+}
+
+// phi in the pinned operation order
+__device__ inline void monomials(double u, double v, double* phi)
+{
+    const double u2 = u * u, uv = u * v, v2 = v * v;
+    phi[0] = 1.0; phi[1] = u; phi[2] = v; phi[3] = u2; phi[4] = uv; phi[5] = v2;
+    phi[6] = u2 * u; phi[7] = u2 * v; phi[8] = u * v2; phi[9] = v2 * v;
+}
+
+// which of the 140 coefficients are non-zero, as three wave-uniform 64-bit words: lane l looks at entries l, 64 + l, 128 + l
+// and the wave votes (one round of loads instead of a chain of 140 dependent scalar loads).  Needs all 64 lanes of the wave.
+struct NonZero {
+    unsigned long long w[3];
+};
+
+__device__ inline NonZero nonzero_mask(const double* __restrict__ C)
+{
+    const int lane = threadIdx.x & 63;
+    const bool tail = lane < NCOEF - 128;
+    NonZero z;
+    z.w[0] = __ballot(C[lane] != 0.0);
+    z.w[1] = __ballot(C[64 + lane] != 0.0);
+    z.w[2] = __ballot(tail && C[tail ? 128 + lane : 0] != 0.0);
+    return z;
+}
+
+// wave-uniform: does column k of species s carry any coefficient?  (s, k compile-time: the three masks fold to constants)
+__device__ inline bool column_live(const NonZero& z, int s, int k)
+{
+    unsigned long long m[3] = {0, 0, 0};
+#pragma unroll
+    for (int a = 0; a < NA; ++a) m[cidx(s, a, k) >> 6] |= 1ULL << (cidx(s, a, k) & 63);
+    return ((z.w[0] & m[0]) | (z.w[1] & m[1]) | (z.w[2] & m[2])) != 0;
+}
+
+__device__ inline double column_q(const double* __restrict__ C, int s, int k, const double* phi)
+{
+    double q = C[cidx(s, 0, k)] * phi[0];
+#pragma unroll
+    for (int m = 1; m < NA; ++m) q = q + C[cidx(s, m, k)] * phi[m];
+    return q;
+}
+
+// one species at the point (y, x): value, first derivatives along axis 0 / 1, Laplacian -- disc::point_fields' expressions
+__device__ inline void point_fields(const double* __restrict__ p, const Geom& g, int y, int x, int ym2, int ym1, int yp1, int yp2,
+                                    int xm2, int xm1, int xp1, int xp2, double& ce, double& d0, double& d1, double& lap)
+{
+    const long W = g.W, row = (long)y * W;
+    ce = p[row + x];
+    const double a2 = p[ym2 * W + x], a1 = p[ym1 * W + x];
+    const double b1 = p[yp1 * W + x], b2 = p[yp2 * W + x];
+    const double l2 = p[row + xm2], l1 = p[row + xm1];
+    const double r1 = p[row + xp1], r2 = p[row + xp2];
+    d0 = ((a2 - b2) + 8.0 * (b1 - a1)) * g.inv_12dx;
+    d1 = ((l2 - r2) + 8.0 * (r1 - l1)) * g.inv_12dx;
+    lap = ((-1.0 / 12.0) * ((a2 + b2) + (l2 + r2)) + (4.0 / 3.0) * ((a1 + b1) + (l1 + r1)) - 5.0 * ce) * g.inv_dx2;
+}
+
+// psi of the point (y, x), 0 <= y < H, 0 <= x < W
+__device__ inline void library_fields(const double* __restrict__ h, const Geom& g, int y, int x, double& u, double& v, double* psi)
+{
+    const int H = g.H, W = g.W;
+    int ym2 = y - 2, ym1 = y - 1, yp1 = y + 1, yp2 = y + 2, xm2 = x - 2, xm1 = x - 1, xp1 = x + 1, xp2 = x + 2;
+    ym2 += ym2 < 0 ? H : 0; ym1 += ym1 < 0 ? H : 0; yp1 -= yp1 >= H ? H : 0; yp2 -= yp2 >= H ? H : 0;
+    xm2 += xm2 < 0 ? W : 0; xm1 += xm1 < 0 ? W : 0; xp1 -= xp1 >= W ? W : 0; xp2 -= xp2 >= W ? W : 0;
+    psi[0] = 1.0;
+    point_fields(h, g, y, x, ym2, ym1, yp1, yp2, xm2, xm1, xp1, xp2, u, psi[1], psi[2], psi[5]);
+    point_fields(h + g.plane, g, y, x, ym2, ym1, yp1, yp2, xm2, xm1, xp1, xp2, v, psi[3], psi[4], psi[6]);
+}
+
+__global__ __launch_bounds__(NT) void step_kernel(const double* __restrict__ h, double* __restrict__ out,
+                                                  const double* __restrict__ C, Geom g)
+{
+    const NonZero nz = nonzero_mask(C);
+    const long idx = (long)blockIdx.x * NT + threadIdx.x;
+    if (idx >= g.plane) return;
+    const int y = (int)(idx / g.W), x = (int)(idx - (long)y * g.W);
+    double u, v, psi[NB], phi[NA];
+    library_fields(h, g, y, x, u, v, psi);
+    monomials(u, v, phi);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        double rhs = 0.0;
+#pragma unroll
+        for (int k = 0; k < NB; ++k)
+            if (column_live(nz, s, k)) rhs = rhs + psi[k] * column_q(C, s, k, phi);
+        const double inc = g.dt * rhs;
+        out[s * g.plane + idx] = (s == 0 ? u : v) + inc;
+    }
+}
+
+// w_k = sum_s a_s q_{s,k}, k = 1 .. 6, of the grid point (gy, gx) into LDS slot `slot`; returns the point's values
+__device__ inline void eval_w(const double* __restrict__ h, const double* __restrict__ G, const double* __restrict__ C,
+                              const Geom& g, const bool* live, int gy, int gx, double (*wl)[LW * LW], int slot, double& u,
+                              double& v, double& gu, double& gv, double* phi)
+{
+    const long o = (long)gy * g.W + gx;
+    u = h[o]; v = h[g.plane + o];
+    gu = G[o]; gv = G[g.plane + o];
+    const double au = g.dt * gu, av = g.dt * gv;
+    monomials(u, v, phi);
+#pragma unroll
+    for (int k = 1; k < NB; ++k)
+        if (live[k]) wl[k - 1][slot] = au * column_q(C, 0, k, phi) + av * column_q(C, 1, k, phi);
+}
+
+// grid (ceil(W / 16), ceil(H / 16)); inject may be NULL (the frame carries no gradient); rows: [blocks][140], added to
+__global__ __launch_bounds__(NT) void adjoint_kernel(const double* __restrict__ h, const double* __restrict__ G,
+                                                     const double* __restrict__ inject, double* __restrict__ out,
+                                                     const double* __restrict__ C, double* __restrict__ rows, Geom g)
+{
+    __shared__ double wl[NB - 1][LW * LW];
+    __shared__ double stg[NWAVES][64 * STG];
+    __shared__ double red[NCOEF];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lx = tid & (TS - 1), ly = tid >> 4;
+    const int ty0 = blockIdx.y * TS, tx0 = blockIdx.x * TS;
+
+    const NonZero nz = nonzero_mask(C);
+    bool live[NB];                                                  // wave-uniform: column k carries a coefficient
+#pragma unroll
+    for (int k = 0; k < NB; ++k) live[k] = column_live(nz, 0, k) || column_live(nz, 1, k);
+
+    // w at the tile's points (lanes outside the grid evaluate the wrapped point: it is the halo of a lane inside) ...
+    const bool inside = ty0 + ly < g.H && tx0 + lx < g.W;
+    const int gy = wrapi(ty0 + ly, g.H), gx = wrapi(tx0 + lx, g.W);
+    const int slot = (ly + HALO) * LW + lx + HALO;
+    double u, v, gu, gv, phi[NA];
+    eval_w(h, G, C, g, live, gy, gx, wl, slot, u, v, gu, gv, phi);
+    // ... and at the 4 x 32 points of the star halo
+    if (tid < 128) {
+        const int strip = tid >> 5, j = tid & 31;
+        int py, px;
+        if (strip < 2) { py = (j >> 4) + (strip ? TS + HALO : 0); px = (j & 15) + HALO; }
+        else           { py = (j & 15) + HALO; px = (j >> 4) + (strip == 3 ? TS + HALO : 0); }
+        double u_, v_, gu_, gv_, phi_[NA];
+        eval_w(h, G, C, g, live, wrapi(ty0 + py - HALO, g.H), wrapi(tx0 + px - HALO, g.W), wl, py * LW + px, u_, v_, gu_, gv_,
+               phi_);
+    }
+    __syncthreads();
+
+    double psi[NB], uc, vc;
+    library_fields(h, g, gy, gx, uc, vc, psi);
+    const double au = g.dt * gu, av = g.dt * gv;
+    // pointwise part: sum_k psi_k sum_m (a_u C[u][m][k] + a_v C[v][m][k]) dphi_m/dh_s
+    const double du_phi[NA] = {0.0, 1.0, 0.0, 2.0 * u, v, 0.0, 3.0 * phi[3], 2.0 * phi[4], phi[5], 0.0};
+    const double dv_phi[NA] = {0.0, 0.0, 1.0, 0.0, u, 2.0 * v, 0.0, phi[3], 2.0 * phi[4], 3.0 * phi[5]};
+    double ou = gu, ov = gv;
+    if (inject) {
+        const long o = (long)gy * g.W + gx;
+        ou += inject[o]; ov += inject[g.plane + o];
+    }
+#pragma unroll
+    for (int k = 0; k < NB; ++k)
+        if (live[k]) {
+            double su = 0.0, sv = 0.0;
+#pragma unroll
+            for (int m = 1; m < NA; ++m) {
+                const double r = au * C[cidx(0, m, k)] + av * C[cidx(1, m, k)];
+                su += r * du_phi[m]; sv += r * dv_phi[m];
+            }
+            ou += psi[k] * su; ov += psi[k] * sv;
+        }
+    // transposed stencils on w: D0^T = -D0, D1^T = -D1, Lap^T = Lap
+    auto d0 = [&](const double* f) {
+        return ((f[slot - 2 * LW] - f[slot + 2 * LW]) + 8.0 * (f[slot + LW] - f[slot - LW])) * g.inv_12dx;
+    };
+    auto d1 = [&](const double* f) { return ((f[slot - 2] - f[slot + 2]) + 8.0 * (f[slot + 1] - f[slot - 1])) * g.inv_12dx; };
+    auto lap = [&](const double* f) {
+        return ((-1.0 / 12.0) * ((f[slot - 2 * LW] + f[slot + 2 * LW]) + (f[slot - 2] + f[slot + 2])) +
+                (4.0 / 3.0) * ((f[slot - LW] + f[slot + LW]) + (f[slot - 1] + f[slot + 1])) - 5.0 * f[slot]) * g.inv_dx2;
+    };
+    if (live[1]) ou -= d0(wl[0]);
+    if (live[2]) ou -= d1(wl[1]);
+    if (live[5]) ou += lap(wl[4]);
+    if (live[3]) ov -= d0(wl[2]);
+    if (live[4]) ov -= d1(wl[3]);
+    if (live[6]) ov += lap(wl[5]);
+    if (inside) {
+        const long o = (long)gy * g.W + gx;
+        out[o] = ou; out[g.plane + o] = ov;
+    }
+
+    // coefficient gradients: stage this lane's point, then 16 groups of 4 points through the matrix cores
+    double* mine = &stg[wave][lane * STG];
+#pragma unroll
+    for (int m = 0; m < NA; ++m) mine[m] = phi[m];
+    mine[NA] = inside ? au : 0.0;
+    mine[NA + 1] = inside ? av : 0.0;
+#pragma unroll
+    for (int k = 0; k < NB; ++k) mine[NA + 2 + k] = inside ? psi[k] : 0.0;
+    __syncthreads();
+    const int r = lane & 15, kq = lane >> 4;
+    const int s0 = r >= NA ? 1 : 0, m0 = r - NA * s0;               // row r of tile 0; row 16 + r of tile 1 is (v, 6 + r)
+    d4 acc0 = d4{0.0, 0.0, 0.0, 0.0}, acc1 = d4{0.0, 0.0, 0.0, 0.0};
+    for (int grp = 0; grp < 16; ++grp) {
+        const double* P = &stg[wave][(grp * 4 + kq) * STG];
+        const double a0 = P[NA + s0] * P[m0];
+        const double a1 = r < 2 * NA - 16 ? P[NA + 1] * P[r + 16 - NA] : 0.0;
+        const double b = r < NB ? P[NA + 2 + r] : 0.0;
+        acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b, acc1, 0, 0, 0);
+    }
+    // the workgroup's waves in a fixed order: wave 0 stores, waves 1.. add
+    for (int w = 0; w < NWAVES; ++w) {
+        if (wave == w && r < NB) {
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                double* e = &red[(kq + 4 * reg) * NB + r];
+                *e = (w == 0 ? 0.0 : *e) + acc0[reg];
+            }
+            double* e = &red[(16 + kq) * NB + r];
+            *e = (w == 0 ? 0.0 : *e) + acc1[0];
+        }
+        __syncthreads();
+    }
+    if (tid < NCOEF) {
+        double* row = rows + ((long)blockIdx.y * gridDim.x + blockIdx.x) * NCOEF;
+        row[tid] = row[tid] + red[tid];
+    }
+}
+
+// one workgroup: sums the `nrows` partial rows in row order
+__global__ __launch_bounds__(FIN_NT) void finish_kernel(const double* __restrict__ rows, int nrows, double* __restrict__ gC)
+{
+    const int e = threadIdx.x;
+    if (e >= NCOEF) return;
+    double s = 0.0;
+    for (int r = 0; r < nrows; ++r) s += rows[(long)r * NCOEF + e];
+    gC[e] = s;
+}
+
+}  // namespace lib
+}  // namespace pi

@@ -1,0 +1,172 @@
+"""Library cell: one Stage-3 fine-tuning iteration (rollout forward + backward) of the Burgers equation on three routes.
+
+Workload: 100^2, float64, 200 explicit Euler steps, the reference's Stage-3 Burgers parameters, loss = mean(traj^2).
+  (a) library_cell    ``LibraryCell.from_cell(Stage3BurgersCell())``: csrc/pi_lib.h, one launch per step and per adjoint step
+  (b) stage3_burgers  ``Stage3BurgersCell`` on the advective kernels (csrc/pi_adv.h): this one equation's hand-written path
+  (c) stock_torch     the same step on stock tensor operations (rolls for the stencils, the equation's six terms only) with
+                      stock autograd: what a user whose Stage-2 run returned any OTHER equation had before the library cell
+  (d) library_cell_dense  (a) with 140 random coefficients on the same state: no column is skipped
+The routes are compared before anything is timed.  Timed with HIP events over a region of at least --seconds after warm-up;
+the routes alternate --repeats times and every time is kept.  The spread of a route is (max - min) / min of its own repeats.
+
+    python tools/library_cell_bench.py [--seconds 1.0] [--repeats 5] [--out profiles/library_cell.json]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import percnn_amd as pa  # noqa: E402
+from percnn_amd import _lib  # noqa: E402
+
+H = W = 100
+STEPS = 200
+
+
+def timed(fn, seconds):
+    """microseconds per call of fn, over a region of >= `seconds` (HIP events)"""
+    fn()
+    torch.cuda.synchronize()
+    n = 1
+    while True:
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(n):
+            fn()
+        b.record()
+        b.synchronize()
+        elapsed = a.elapsed_time(b) / 1e3
+        if elapsed >= seconds:
+            return 1e6 * elapsed / n
+        n = max(n + 1, int(n * 1.2 * seconds / max(elapsed, 1e-4)))
+
+
+def stock_rollout(h0, terms, dx, dt, steps):
+    """terms: per species a list of (coefficient tensor, monomial index, factor index); -> [steps+1,2,H,W]"""
+    def d1(f, ax):
+        return ((torch.roll(f, 2, ax) - torch.roll(f, -2, ax)) + 8.0 * (torch.roll(f, -1, ax) - torch.roll(f, 1, ax))) * (1.0 / (12.0 * dx))
+
+    def lap(f):
+        return ((-1.0 / 12.0) * ((torch.roll(f, 2, 0) + torch.roll(f, -2, 0)) + (torch.roll(f, 2, 1) + torch.roll(f, -2, 1)))
+                + (4.0 / 3.0) * ((torch.roll(f, 1, 0) + torch.roll(f, -1, 0)) + (torch.roll(f, 1, 1) + torch.roll(f, -1, 1)))
+                - 5.0 * f) * (1.0 / (dx * dx))
+
+    mono = [lambda u, v: None, lambda u, v: u, lambda u, v: v, lambda u, v: u * u, lambda u, v: u * v, lambda u, v: v * v,
+            lambda u, v: u * u * u, lambda u, v: u * u * v, lambda u, v: u * v * v, lambda u, v: v * v * v]
+    fact = [lambda u, v: None, lambda u, v: d1(u, 0), lambda u, v: d1(u, 1), lambda u, v: d1(v, 0), lambda u, v: d1(v, 1),
+            lambda u, v: lap(u), lambda u, v: lap(v)]
+    frames = [h0[0]]
+    for _ in range(steps):
+        u, v = frames[-1][0], frames[-1][1]
+        nxt = []
+        for s, h in enumerate((u, v)):
+            rhs = 0.0
+            for c, m, k in terms[s]:
+                a, b = mono[m](u, v), fact[k](u, v)
+                t = c if a is None and b is None else (c * b if a is None else (c * a if b is None else c * a * b))
+                rhs = rhs + t
+            nxt.append(h + dt * rhs)
+        frames.append(torch.stack(nxt))
+    return torch.stack(frames)
+
+
+def resource_usage():
+    """registers / scratch / LDS of the library cell's kernels, from a compile of its translation unit (no GPU work)"""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cmd = [hipcc] + _lib.HIPCC_FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c", "-o", os.devnull,
+                                       os.path.join(_lib.CSRC, "pi_lib_abi.hip")]
+    try:
+        err = subprocess.run(cmd, cwd=_lib.CSRC, capture_output=True, text=True, check=True).stderr
+    except (OSError, subprocess.CalledProcessError) as e:
+        return {"error": str(e)}
+    out, cur = {}, None
+    for line in err.splitlines():
+        if "Function Name:" in line:
+            name = line.split("Function Name:")[1].split()[0]
+            cur = out.setdefault(next((k for k in ("step_kernel", "adjoint_kernel", "finish_kernel") if k in name), name), {})
+        elif cur is not None:
+            for key in ("VGPRs:", "AGPRs:", "TotalSGPRs:", "ScratchSize [bytes/lane]:", "LDS Size [bytes/block]:", "Occupancy [waves/SIMD]:"):
+                if " " + key in line:
+                    cur[key.rstrip(":")] = int(line.split(key)[1].split()[0])
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--seconds", type=float, default=1.0)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "library_cell.json"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("library_cell_bench.py measures on a HIP device; none found")
+    dev = torch.device("cuda:0")
+    stage3 = pa.Stage3BurgersCell().to(dev)
+    dx, dt = stage3.dx, stage3.dt
+    cell = pa.LibraryCell.from_cell(stage3)
+    rng = np.random.default_rng(0)
+    dense = pa.LibraryCell(0.1 * rng.standard_normal((2, 10, 7)) * np.array([1, 1, 1, 1, 1, 1e-4, 1e-4]), dx, dt,
+                           support="dense").to(dev)            # diffusion-like columns scaled to dx^2: the rollout stays bounded
+    ys = torch.arange(H, dtype=torch.float64) / H
+    yy, xx = torch.meshgrid(ys, ys, indexing="ij")
+    tp = 2 * np.pi
+    u = torch.sin(tp * xx) * torch.cos(tp * yy) + 0.3 * torch.cos(2 * tp * xx + 0.5)
+    v = torch.cos(tp * xx) * torch.sin(tp * yy) - 0.2 * torch.sin(tp * (xx + 2 * yy))
+    h0 = torch.stack((u, v))[None].to(dev).requires_grad_(True)
+    rcnn = pa.RCNN(stage3, step=STEPS, effective_step=list(range(STEPS)), init_state=h0)
+    names = list(pa.Stage3BurgersCell.INIT)
+    where = {"nu_u": (0, 0, 5), "C1_u": (0, 1, 1), "C2_u": (0, 2, 2), "nu_v": (1, 0, 6), "C1_v": (1, 1, 3), "C2_v": (1, 2, 4)}
+    terms = [[(getattr(stage3, n), where[n][1], where[n][2]) for n in names if where[n][0] == s] for s in (0, 1)]
+
+    def grads_of(traj, params):
+        return torch.autograd.grad((traj ** 2).mean(), params + [h0])
+
+    routes = {"library_cell": lambda: grads_of(cell.rollout(h0, STEPS), [cell.coef]),
+              "stage3_burgers": lambda: grads_of(rcnn.trajectory(), [getattr(stage3, n) for n in names]),
+              "stock_torch": lambda: grads_of(stock_rollout(h0, terms, dx, dt, STEPS), [getattr(stage3, n) for n in names]),
+              "library_cell_dense": lambda: grads_of(dense.rollout(h0, STEPS), [dense.coef])}
+
+    # same results first: the six scalar gradients and dL/dh0 of the three Burgers routes
+    ga, gb, gc = routes["library_cell"](), routes["stage3_burgers"](), routes["stock_torch"]()
+    a6 = torch.stack([ga[0][where[n]] for n in names])
+    diff = {"library_cell_vs_stage3_burgers": float(((a6 - torch.stack(gb[:6])).abs() / torch.stack(gb[:6]).abs()).max()),
+            "library_cell_vs_stock_torch": float(((a6 - torch.stack(gc[:6])).abs() / torch.stack(gc[:6]).abs()).max()),
+            "dLdh0_vs_stage3_burgers_rel_l2": float((ga[1] - gb[6]).norm() / gb[6].norm()),
+            "dLdh0_vs_stock_torch_rel_l2": float((ga[1] - gc[6]).norm() / gc[6].norm())}
+    dense_finite = bool(torch.isfinite(routes["library_cell_dense"]()[0]).all())
+    del ga, gb, gc
+
+    times = {k: [] for k in routes}
+    for _ in range(args.repeats):
+        for key, fn in routes.items():
+            times[key].append(round(timed(fn, args.seconds) / STEPS, 3))
+    spread = {k: round((max(v) - min(v)) / min(v), 4) for k, v in times.items()}
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    out = {"metric": "microseconds per step, rollout forward + backward (one fine-tuning iteration / steps)",
+           "workload": {"shape": [H, W], "dtype": "float64", "steps": STEPS, "equation": "Burgers (Stage3BurgersCell.INIT)",
+                        "loss": "mean(traj^2)"},
+           "device": torch.cuda.get_device_name(0), "seconds_per_region": args.seconds,
+           "us_per_step": times, "median": med, "spread": spread,
+           "library_cell_median_below_stock_torch_min": med["library_cell"] < min(times["stock_torch"]),
+           "ratio_library_cell_over_stock_torch": round(med["library_cell"] / med["stock_torch"], 4),
+           "ratio_library_cell_over_stage3_burgers": round(med["library_cell"] / med["stage3_burgers"], 4),
+           "ratio_dense_over_library_cell": round(med["library_cell_dense"] / med["library_cell"], 4),
+           "max_relative_difference_between_routes": diff, "dense_gradient_finite": dense_finite,
+           "kernel_resources": resource_usage()}
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+    if not out["library_cell_median_below_stock_torch_min"]:
+        sys.exit("library_cell_bench.py: the library cell's median is not below the stock route's minimum")
+
+
+if __name__ == "__main__":
+    main()
