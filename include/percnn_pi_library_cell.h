@@ -15,6 +15,18 @@
  * q summed over m = 0..9 in order; rhs summed over k = 0..6 in order; inc = dt*rhs; next = h + inc; plain multiplies and adds.
  * A column k whose ten coefficients are all zero is skipped (the same bits for finite inputs, up to the sign of a zero).
  *
+ * The reference's Stage-3 cells also define a classical Runge-Kutta step (forward_rk4).  With f(y) the right-hand side above
+ * (rhs, evaluated exactly as the Euler step evaluates it, skipped columns included), the percnn_pi_lib_rk4_* entry points take
+ * one such step per launch in this fixed order:
+ *   k1 = f(h)         y2 = h + (k1*dt)/2.0
+ *   k2 = f(y2)        y3 = h + (k2*dt)/2.0
+ *   k3 = f(y3)        y4 = h + k3*dt
+ *   k4 = f(y4)        s  = ((k1 + 2.0*k2) + 2.0*k3) + k4
+ *   next = h + (dt*s)/6.0                                     plain multiplies and adds, one true division by 6.0
+ * Their backward walks the stages from 4 down to 1 with kappa_i = dL/dk_i and ybar_i = J(y_i)^T kappa_i:
+ *   kappa4 = dt/6 lambda,  kappa3 = dt/3 lambda + dt ybar4,  kappa2 = dt/3 lambda + dt/2 ybar3,  kappa1 = dt/6 lambda + dt/2 ybar2
+ *   lambda_out = lambda + inject + ybar1 + ybar2 + ybar3 + ybar4,      gC[s][m][k] += sum_i sum_p kappa_{i,s} phi_m(y_i) psi_k(y_i)
+ *
  * float64, planar [2][H][W] states, dx = dy.  coef: DEVICE array double[2][10][7].
  * Two calls on the same input give the same bits (no floating-point atomics).
  *
@@ -53,6 +65,19 @@ size_t percnn_pi_lib_rollout_bwd_workspace_bytes(const int64_t* shape, int T_ste
 int percnn_pi_lib_rollout_bwd_f64(const double* traj, const double* g_traj, const unsigned char* frame_mask, double* g_h0,
                                   double* g_coef, void* workspace, size_t workspace_bytes, const double* coef,
                                   const int64_t* shape, int T_steps, double dx, double dt, void* stream);
+
+/* The same four calls with the Runge-Kutta step: argument lists, refusals and frame_mask as above.  The forward calls need no
+ * workspace.  The backward recomputes y2, y3, y4 of a step in one launch and runs one launch per stage; its workspace holds two
+ * adjoint states (lambda), the three stage states, two ybar states and one row of 140 partial sums per 16 x 16 tile:
+ *   (7 * 2 * H * W + ceil(H / 16) * ceil(W / 16) * 140) * sizeof(double) */
+int percnn_pi_lib_rk4_step_fwd_f64(const double* h, double* h_next, const double* coef, const int64_t* shape, double dx, double dt,
+                                   void* stream);
+int percnn_pi_lib_rk4_rollout_fwd_f64(double* traj, const double* coef, const int64_t* shape, int T_steps, double dx, double dt,
+                                      void* stream);
+size_t percnn_pi_lib_rk4_rollout_bwd_workspace_bytes(const int64_t* shape, int T_steps);
+int percnn_pi_lib_rk4_rollout_bwd_f64(const double* traj, const double* g_traj, const unsigned char* frame_mask, double* g_h0,
+                                      double* g_coef, void* workspace, size_t workspace_bytes, const double* coef,
+                                      const int64_t* shape, int T_steps, double dx, double dt, void* stream);
 
 #ifdef __cplusplus
 }

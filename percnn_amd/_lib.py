@@ -82,6 +82,8 @@ EXPORTS = [
     "percnn_pi_library_moments_workspace_bytes", "percnn_pi_library_moments_f32", "percnn_pi_library_moments_f64",
     "percnn_pi_lib_step_fwd_f64", "percnn_pi_lib_rollout_fwd_f64", "percnn_pi_lib_rollout_bwd_workspace_bytes",
     "percnn_pi_lib_rollout_bwd_f64",
+    "percnn_pi_lib_rk4_step_fwd_f64", "percnn_pi_lib_rk4_rollout_fwd_f64", "percnn_pi_lib_rk4_rollout_bwd_workspace_bytes",
+    "percnn_pi_lib_rk4_rollout_bwd_f64",
 ]
 
 
@@ -329,12 +331,15 @@ def lib() -> ctypes.CDLL:
         f = getattr(L, f"percnn_pi_library_moments_{suf}")
         f.restype = ci
         f.argtypes = [vp, i64, i64, i64p, ci, ci, cd, cd, ci, ctypes.c_uint32, u64, u64, vp, vp, vp, vp, vp, sz, vp]
-    L.percnn_pi_lib_step_fwd_f64.restype, L.percnn_pi_lib_step_fwd_f64.argtypes = ci, [vp, vp, vp, i64p, cd, cd, vp]
-    L.percnn_pi_lib_rollout_fwd_f64.restype, L.percnn_pi_lib_rollout_fwd_f64.argtypes = ci, [vp, vp, i64p, ci, cd, cd, vp]
-    L.percnn_pi_lib_rollout_bwd_workspace_bytes.restype = sz
-    L.percnn_pi_lib_rollout_bwd_workspace_bytes.argtypes = [i64p, ci]
-    L.percnn_pi_lib_rollout_bwd_f64.restype = ci
-    L.percnn_pi_lib_rollout_bwd_f64.argtypes = [vp, vp, ctypes.c_char_p, vp, vp, vp, sz, vp, i64p, ci, cd, cd, vp]
+    for pre in ("percnn_pi_lib_", "percnn_pi_lib_rk4_"):      # the Euler step and the Runge-Kutta step: the same signatures
+        f = getattr(L, pre + "step_fwd_f64")
+        f.restype, f.argtypes = ci, [vp, vp, vp, i64p, cd, cd, vp]
+        f = getattr(L, pre + "rollout_fwd_f64")
+        f.restype, f.argtypes = ci, [vp, vp, i64p, ci, cd, cd, vp]
+        f = getattr(L, pre + "rollout_bwd_workspace_bytes")
+        f.restype, f.argtypes = sz, [i64p, ci]
+        f = getattr(L, pre + "rollout_bwd_f64")
+        f.restype, f.argtypes = ci, [vp, vp, ctypes.c_char_p, vp, vp, vp, sz, vp, i64p, ci, cd, cd, vp]
     # process-wide tuning defaults from the environment ("key=value,..."; the keys of percnn_pi_set_option) -- what a launcher
     # uses to A/B an option in worker processes it does not construct itself
     spec = os.environ.get("PERCNN_PI_OPTIONS", "")

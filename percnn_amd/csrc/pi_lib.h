@@ -20,6 +20,18 @@
 //                 stages phi, a and psi of its point in LDS; lane l then feeds row / column l & 15 for the point l >> 4 of a
 //                 group of 4 (the operand map at the top of pi_disc.h; C/D: D[(lane >> 4) + 4 reg][lane & 15]).  Lanes
 //                 outside the grid stage zeros for a and psi, padding rows and columns feed zeros.
+// rk4_kernel      one classical Runge-Kutta step per launch, no workspace (the order of include/percnn_pi_library_cell.h).  A
+//                 workgroup owns an FT x FT tile (FT = 8 or 16: rk4_tile) and loads it with an 8-wide wrapped halo into LDS,
+//                 then evaluates k1 on tile + 6, k2 on tile + 4, k3 on tile + 2 and k4 on the tile: four right-hand sides, one
+//                 launch boundary.  The stage
+//                 states ping-pong between two LDS windows next to the window of h; k1 .. k4 of the tile's own points stay in
+//                 registers for s.  A point's value is the same expression whichever tile evaluates it, so the redundant halo
+//                 work changes no bit.  Window extents are no multiple of the workgroup, so lanes loop over window points;
+//                 every lane reaches every barrier.  <STAGES>: writes y2, y3, y4 of the tile's points instead of the next
+//                 state (what the backward recomputes per step; k4 is not needed for that).
+// rk4_stage_kernel  adjoint_kernel's body for one Runge-Kutta stage: kappa = a lambda + b ybar_{i+1} pointwise (halo points
+//                 included) takes the place of dt G, the stage state y_i that of h; writes ybar_i = J(y_i)^T kappa and adds it to
+//                 the running sum that becomes the step's outgoing adjoint.
 // Partial sums: one row of 140 doubles per workgroup, each workgroup adds only to its own row, launch after launch in stream
 // order; finish_kernel sums the rows in a fixed order.  No floating-point atomics: the same call twice gives the same bits.
 #pragma once
@@ -34,6 +46,17 @@ constexpr int NT = 256, NWAVES = NT / 64;
 constexpr int TS = 16, HALO = 2, LW = TS + 2 * HALO;   // adjoint tile, its LDS extent with the star halo
 constexpr int STG = 19;                                 // staged doubles per point: phi[10], a_u, a_v, psi[7]
 constexpr int FIN_NT = 192;
+constexpr int FH = 8;                                   // halo of the forward Runge-Kutta tile: four radius-2 stages
+// The Runge-Kutta tile is FT x FT, FT = 8 or 16 (rk4_tile): a launch of a 100^2 step is bounded by its slowest workgroup, not by
+// arithmetic, and a workgroup's time is its serial right-hand sides per lane -- 5 on the 8-wide tile (169 workgroups at 100^2,
+// 3.4 x redundant evaluations), 10 on the 16-wide one (49 workgroups, 2.0 x).  The small tile while every workgroup still gets a
+// compute unit of its own (256 on MI355X), the 16-wide tile beyond.
+constexpr int RK4_SMALL_TILE_BLOCKS = 256;
+
+__host__ __device__ inline int rk4_tile(int H, int W)
+{
+    return (long)((H + 7) / 8) * ((W + 7) / 8) <= RK4_SMALL_TILE_BLOCKS ? 8 : 16;
+}
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -93,6 +116,15 @@ __device__ inline double column_q(const double* __restrict__ C, int s, int k, co
     return q;
 }
 
+// the pinned stencil expressions on the star a2 a1 [ce] b1 b2 (axis 0), l2 l1 [ce] r1 r2 (axis 1)
+__device__ inline void star_fields(const Geom& g, double ce, double a2, double a1, double b1, double b2, double l2, double l1,
+                                   double r1, double r2, double& d0, double& d1, double& lap)
+{
+    d0 = ((a2 - b2) + 8.0 * (b1 - a1)) * g.inv_12dx;
+    d1 = ((l2 - r2) + 8.0 * (r1 - l1)) * g.inv_12dx;
+    lap = ((-1.0 / 12.0) * ((a2 + b2) + (l2 + r2)) + (4.0 / 3.0) * ((a1 + b1) + (l1 + r1)) - 5.0 * ce) * g.inv_dx2;
+}
+
 // one species at the point (y, x): value, first derivatives along axis 0 / 1, Laplacian -- disc::point_fields' expressions
 __device__ inline void point_fields(const double* __restrict__ p, const Geom& g, int y, int x, int ym2, int ym1, int yp1, int yp2,
                                     int xm2, int xm1, int xp1, int xp2, double& ce, double& d0, double& d1, double& lap)
@@ -103,9 +135,7 @@ __device__ inline void point_fields(const double* __restrict__ p, const Geom& g,
     const double b1 = p[yp1 * W + x], b2 = p[yp2 * W + x];
     const double l2 = p[row + xm2], l1 = p[row + xm1];
     const double r1 = p[row + xp1], r2 = p[row + xp2];
-    d0 = ((a2 - b2) + 8.0 * (b1 - a1)) * g.inv_12dx;
-    d1 = ((l2 - r2) + 8.0 * (r1 - l1)) * g.inv_12dx;
-    lap = ((-1.0 / 12.0) * ((a2 + b2) + (l2 + r2)) + (4.0 / 3.0) * ((a1 + b1) + (l1 + r1)) - 5.0 * ce) * g.inv_dx2;
+    star_fields(g, ce, a2, a1, b1, b2, l2, l1, r1, r2, d0, d1, lap);
 }
 
 // psi of the point (y, x), 0 <= y < H, 0 <= x < W
@@ -120,6 +150,17 @@ __device__ inline void library_fields(const double* __restrict__ h, const Geom& 
     point_fields(h + g.plane, g, y, x, ym2, ym1, yp1, yp2, xm2, xm1, xp1, xp2, v, psi[3], psi[4], psi[6]);
 }
 
+// the right-hand side of species s in the pinned order: live columns k = 0 .. 6 in turn, q summed over m = 0 .. 9
+template <int S>
+__device__ inline double rhs_of(const double* __restrict__ C, const NonZero& nz, const double* phi, const double* psi)
+{
+    double rhs = 0.0;
+#pragma unroll
+    for (int k = 0; k < NB; ++k)
+        if (column_live(nz, S, k)) rhs = rhs + psi[k] * column_q(C, S, k, phi);
+    return rhs;
+}
+
 __global__ __launch_bounds__(NT) void step_kernel(const double* __restrict__ h, double* __restrict__ out,
                                                   const double* __restrict__ C, Geom g)
 {
@@ -130,36 +171,172 @@ __global__ __launch_bounds__(NT) void step_kernel(const double* __restrict__ h, 
     double u, v, psi[NB], phi[NA];
     library_fields(h, g, y, x, u, v, psi);
     monomials(u, v, phi);
+    const double inc_u = g.dt * rhs_of<0>(C, nz, phi, psi), inc_v = g.dt * rhs_of<1>(C, nz, phi, psi);
+    out[idx] = u + inc_u;
+    out[g.plane + idx] = v + inc_v;
+}
+
+// ---- one Runge-Kutta step per launch -------------------------------------------------------------------------------------------
+// f(y) at slot c of an LDS window y [2][FW * FW]: point_fields' expressions on LDS neighbours
+template <int FW>
+__device__ inline void rhs_window(const double* y, int c, const double* __restrict__ C, const NonZero& nz, const Geom& g, double& ku,
+                                  double& kv)
+{
+    double psi[NB], phi[NA];
+    psi[0] = 1.0;
+    const double *pu = y + c, *pv = y + FW * FW + c;
+    star_fields(g, pu[0], pu[-2 * FW], pu[-FW], pu[FW], pu[2 * FW], pu[-2], pu[-1], pu[1], pu[2], psi[1], psi[2], psi[5]);
+    star_fields(g, pv[0], pv[-2 * FW], pv[-FW], pv[FW], pv[2 * FW], pv[-2], pv[-1], pv[1], pv[2], psi[3], psi[4], psi[6]);
+    monomials(pu[0], pv[0], phi);
+    ku = rhs_of<0>(C, nz, phi, psi);
+    kv = rhs_of<1>(C, nz, phi, psi);
+}
+
+// window slot of point i of the region tile + M: the tile's FT^2 points first (point i of the tile is i of every region, so it
+// stays on one lane through the stages), then the ring of width M: two bands of M rows over the region's FT + 2M columns, then
+// FT rows of 2M columns.  0 <= i < (FT + 2M)^2
+template <int FT, int M>
+__device__ inline int region_slot(int i)
+{
+    constexpr int R = FT + 2 * M, FW = FT + 2 * FH;
+    if (i < FT * FT) return (i / FT + FH) * FW + i % FT + FH;
+    if constexpr (M > 0) {
+        i -= FT * FT;
+        int row, col;
+        if (i < 2 * M * R) {
+            row = i / R; col = i - row * R;
+            row += row >= M ? FT : 0;
+        } else {
+            const int j = i - 2 * M * R;
+            row = j / (2 * M); col = j - row * (2 * M);
+            row += M; col += col >= M ? FT : 0;
+        }
+        return (row + FH - M) * FW + col + FH - M;
+    }
+    return 0;
+}
+
+// k = f(y) on the region tile + M and, for M > 0, the next stage state h + (k dt) / DIV there.  Lanes loop over the region's
+// points; k of a lane's tile points (the leading KPL rounds) is returned in ku, kv
+template <int FT, int M, int DIV>
+__device__ inline void rk4_stage(const double* y, const double* hb, double* nb, const double* __restrict__ C, const NonZero& nz,
+                                 const Geom& g, double* ku, double* kv)
+{
+    constexpr int FW = FT + 2 * FH, FWIN = FW * FW, NPTS = (FT + 2 * M) * (FT + 2 * M), KPL = (FT * FT + NT - 1) / NT;
+    auto point = [&](int i, double& ru, double& rv) {
+        const int c = region_slot<FT, M>(i);
+        rhs_window<FW>(y, c, C, nz, g, ru, rv);
+        if constexpr (M > 0) {
+            nb[c] = hb[c] + (ru * g.dt) / (double)DIV;
+            nb[FWIN + c] = hb[FWIN + c] + (rv * g.dt) / (double)DIV;
+        }
+    };
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        double rhs = 0.0;
-#pragma unroll
-        for (int k = 0; k < NB; ++k)
-            if (column_live(nz, s, k)) rhs = rhs + psi[k] * column_q(C, s, k, phi);
-        const double inc = g.dt * rhs;
-        out[s * g.plane + idx] = (s == 0 ? u : v) + inc;
+    for (int j = 0; j < KPL; ++j)
+        if ((int)threadIdx.x + j * NT < NPTS) point(threadIdx.x + j * NT, ku[j], kv[j]);
+    for (int i = threadIdx.x + KPL * NT; i < NPTS; i += NT) {
+        double ru, rv;
+        point(i, ru, rv);
     }
 }
 
-// w_k = sum_s a_s q_{s,k}, k = 1 .. 6, of the grid point (gy, gx) into LDS slot `slot`; returns the point's values
-__device__ inline void eval_w(const double* __restrict__ h, const double* __restrict__ G, const double* __restrict__ C,
-                              const Geom& g, const bool* live, int gy, int gx, double (*wl)[LW * LW], int slot, double& u,
-                              double& v, double& gu, double& gv, double* phi)
+// grid (ceil(W / FT), ceil(H / FT)).  out: the next state [2][H][W]; STAGES: y2, y3, y4 as [3][2][H][W]
+template <int FT, bool STAGES>
+__global__ __launch_bounds__(NT) void rk4_kernel(const double* __restrict__ h, double* __restrict__ out,
+                                                 const double* __restrict__ C, Geom g)
+{
+    constexpr int FW = FT + 2 * FH, FWIN = FW * FW, KPL = (FT * FT + NT - 1) / NT;
+    __shared__ double hb[2 * FWIN], pb[2 * FWIN], qb[2 * FWIN];
+    const int tid = threadIdx.x;
+    const int ty0 = blockIdx.y * FT, tx0 = blockIdx.x * FT;
+    const NonZero nz = nonzero_mask(C);
+    // the halo may wrap the grid more than once: a true modulo
+    for (int i = tid; i < FWIN; i += NT) {
+        const int wy = i / FW, wx = i - wy * FW;
+        const long o = (long)wrapi(ty0 - FH + wy, g.H) * g.W + wrapi(tx0 - FH + wx, g.W);
+        hb[i] = h[o];
+        hb[FWIN + i] = h[g.plane + o];
+    }
+    __syncthreads();
+    // where this lane's tile points live (-1: none, or outside the grid -- such a lane evaluates wrapped points and stores nothing)
+    int slot[KPL];
+    long at[KPL];
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) {
+        const int p = tid + j * NT, ly = p / FT, lx = p % FT;
+        slot[j] = p < FT * FT ? (ly + FH) * FW + lx + FH : 0;
+        at[j] = p < FT * FT && ty0 + ly < g.H && tx0 + lx < g.W ? (long)(ty0 + ly) * g.W + tx0 + lx : -1;
+    }
+    auto store_stage = [&](const double* yb, int i) {
+        if (!STAGES) return;
+#pragma unroll
+        for (int j = 0; j < KPL; ++j)
+            if (at[j] >= 0) {
+                out[(2 * i) * g.plane + at[j]] = yb[slot[j]];
+                out[(2 * i + 1) * g.plane + at[j]] = yb[FWIN + slot[j]];
+            }
+    };
+    double ku[KPL] = {}, kv[KPL] = {}, su[KPL], sv[KPL];
+    rk4_stage<FT, 6, 2>(hb, hb, pb, C, nz, g, ku, kv);               // k1, y2
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) { su[j] = ku[j]; sv[j] = kv[j]; }
+    __syncthreads();
+    store_stage(pb, 0);
+    rk4_stage<FT, 4, 2>(pb, hb, qb, C, nz, g, ku, kv);               // k2, y3
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) { su[j] = su[j] + 2.0 * ku[j]; sv[j] = sv[j] + 2.0 * kv[j]; }
+    __syncthreads();
+    store_stage(qb, 1);
+    rk4_stage<FT, 2, 1>(qb, hb, pb, C, nz, g, ku, kv);               // k3, y4 (the reads of y2 ended at the barrier above)
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) { su[j] = su[j] + 2.0 * ku[j]; sv[j] = sv[j] + 2.0 * kv[j]; }
+    __syncthreads();
+    store_stage(pb, 2);
+    if (STAGES) return;                                             // no barrier follows
+    rk4_stage<FT, 0, 1>(pb, hb, nullptr, C, nz, g, ku, kv);          // k4
+#pragma unroll
+    for (int j = 0; j < KPL; ++j)
+        if (at[j] >= 0) {
+            out[at[j]] = hb[slot[j]] + (g.dt * (su[j] + ku[j])) / 6.0;
+            out[g.plane + at[j]] = hb[FWIN + slot[j]] + (g.dt * (sv[j] + kv[j])) / 6.0;
+        }
+}
+
+// what multiplies the right-hand side's Jacobian at a point: dt G for the Euler step (prev NULL, a = dt), and for a Runge-Kutta
+// stage kappa_i = a lambda + b ybar_{i+1}
+struct Kappa {
+    const double* lam;
+    const double* prev;
+    double a, b;
+    __device__ void at(long o, long plane, double& ku, double& kv) const
+    {
+        ku = a * lam[o]; kv = a * lam[plane + o];
+        if (prev) { ku = ku + b * prev[o]; kv = kv + b * prev[plane + o]; }
+    }
+};
+
+// w_k = sum_s a_s q_{s,k}, k = 1 .. 6, of the grid point (gy, gx) into LDS slot `slot`; returns the point's values and a = kappa
+__device__ inline void eval_w(const double* __restrict__ h, const Kappa& kap, const double* __restrict__ C, const Geom& g,
+                              const bool* live, int gy, int gx, double (*wl)[LW * LW], int slot, double& u, double& v, double& au,
+                              double& av, double* phi)
 {
     const long o = (long)gy * g.W + gx;
     u = h[o]; v = h[g.plane + o];
-    gu = G[o]; gv = G[g.plane + o];
-    const double au = g.dt * gu, av = g.dt * gv;
+    kap.at(o, g.plane, au, av);
     monomials(u, v, phi);
 #pragma unroll
     for (int k = 1; k < NB; ++k)
         if (live[k]) wl[k - 1][slot] = au * column_q(C, 0, k, phi) + av * column_q(C, 1, k, phi);
 }
 
-// grid (ceil(W / 16), ceil(H / 16)); inject may be NULL (the frame carries no gradient); rows: [blocks][140], added to
-__global__ __launch_bounds__(NT) void adjoint_kernel(const double* __restrict__ h, const double* __restrict__ G,
-                                                     const double* __restrict__ inject, double* __restrict__ out,
-                                                     const double* __restrict__ C, double* __restrict__ rows, Geom g)
+// One 16 x 16 tile of J(h)^T kappa and of the coefficient-gradient row, for the Euler adjoint step and for a Runge-Kutta stage.
+//   Euler (STAGE false): out = lam + inject + J(h)^T kappa, summed onto lam + inject term by term.
+//   STAGE:               ybar (may be NULL) = J(h)^T kappa summed from zero;  out = (acc + inject) + ybar.  out may be acc
+//                        (each lane reads and writes its own point only); it is never lam or prev, which are read with a halo.
+template <bool STAGE>
+__device__ inline void adjoint_body(const double* __restrict__ h, const Kappa kap, const double* __restrict__ inject,
+                                    const double* acc, double* __restrict__ ybar, double* out, const double* __restrict__ C,
+                                    double* __restrict__ rows, const Geom& g)
 {
     __shared__ double wl[NB - 1][LW * LW];
     __shared__ double stg[NWAVES][64 * STG];
@@ -177,30 +354,30 @@ __global__ __launch_bounds__(NT) void adjoint_kernel(const double* __restrict__ 
     const bool inside = ty0 + ly < g.H && tx0 + lx < g.W;
     const int gy = wrapi(ty0 + ly, g.H), gx = wrapi(tx0 + lx, g.W);
     const int slot = (ly + HALO) * LW + lx + HALO;
-    double u, v, gu, gv, phi[NA];
-    eval_w(h, G, C, g, live, gy, gx, wl, slot, u, v, gu, gv, phi);
+    double u, v, au, av, phi[NA];
+    eval_w(h, kap, C, g, live, gy, gx, wl, slot, u, v, au, av, phi);
     // ... and at the 4 x 32 points of the star halo
     if (tid < 128) {
         const int strip = tid >> 5, j = tid & 31;
         int py, px;
         if (strip < 2) { py = (j >> 4) + (strip ? TS + HALO : 0); px = (j & 15) + HALO; }
         else           { py = (j & 15) + HALO; px = (j >> 4) + (strip == 3 ? TS + HALO : 0); }
-        double u_, v_, gu_, gv_, phi_[NA];
-        eval_w(h, G, C, g, live, wrapi(ty0 + py - HALO, g.H), wrapi(tx0 + px - HALO, g.W), wl, py * LW + px, u_, v_, gu_, gv_,
+        double u_, v_, au_, av_, phi_[NA];
+        eval_w(h, kap, C, g, live, wrapi(ty0 + py - HALO, g.H), wrapi(tx0 + px - HALO, g.W), wl, py * LW + px, u_, v_, au_, av_,
                phi_);
     }
     __syncthreads();
 
     double psi[NB], uc, vc;
     library_fields(h, g, gy, gx, uc, vc, psi);
-    const double au = g.dt * gu, av = g.dt * gv;
     // pointwise part: sum_k psi_k sum_m (a_u C[u][m][k] + a_v C[v][m][k]) dphi_m/dh_s
     const double du_phi[NA] = {0.0, 1.0, 0.0, 2.0 * u, v, 0.0, 3.0 * phi[3], 2.0 * phi[4], phi[5], 0.0};
     const double dv_phi[NA] = {0.0, 0.0, 1.0, 0.0, u, 2.0 * v, 0.0, phi[3], 2.0 * phi[4], 3.0 * phi[5]};
-    double ou = gu, ov = gv;
-    if (inject) {
-        const long o = (long)gy * g.W + gx;
-        ou += inject[o]; ov += inject[g.plane + o];
+    const long o = (long)gy * g.W + gx;
+    double ou = 0.0, ov = 0.0;
+    if (!STAGE) {
+        ou = kap.lam[o]; ov = kap.lam[g.plane + o];
+        if (inject) { ou += inject[o]; ov += inject[g.plane + o]; }
     }
 #pragma unroll
     for (int k = 0; k < NB; ++k)
@@ -229,7 +406,12 @@ __global__ __launch_bounds__(NT) void adjoint_kernel(const double* __restrict__ 
     if (live[4]) ov -= d1(wl[3]);
     if (live[6]) ov += lap(wl[5]);
     if (inside) {
-        const long o = (long)gy * g.W + gx;
+        if (STAGE) {
+            if (ybar) { ybar[o] = ou; ybar[g.plane + o] = ov; }
+            double bu = acc[o], bv = acc[g.plane + o];
+            if (inject) { bu += inject[o]; bv += inject[g.plane + o]; }
+            ou = bu + ou; ov = bv + ov;
+        }
         out[o] = ou; out[g.plane + o] = ov;
     }
 
@@ -270,6 +452,25 @@ __global__ __launch_bounds__(NT) void adjoint_kernel(const double* __restrict__ 
         double* row = rows + ((long)blockIdx.y * gridDim.x + blockIdx.x) * NCOEF;
         row[tid] = row[tid] + red[tid];
     }
+}
+
+// grid (ceil(W / 16), ceil(H / 16)); inject may be NULL (the frame carries no gradient); rows: [blocks][140], added to
+__global__ __launch_bounds__(NT) void adjoint_kernel(const double* __restrict__ h, const double* __restrict__ G,
+                                                     const double* __restrict__ inject, double* __restrict__ out,
+                                                     const double* __restrict__ C, double* __restrict__ rows, Geom g)
+{
+    adjoint_body<false>(h, Kappa{G, nullptr, g.dt, 0.0}, inject, nullptr, nullptr, out, C, rows, g);
+}
+
+// one Runge-Kutta stage of the adjoint, same grid: y the stage state, kappa = a lam + b prev (prev NULL: a lam);
+// ybar (may be NULL) = J(y)^T kappa;  out = (acc + inject) + ybar, out may be acc.  g.dt is not used: a and b carry it
+__global__ __launch_bounds__(NT) void rk4_stage_kernel(const double* __restrict__ y, const double* __restrict__ lam,
+                                                       const double* __restrict__ prev, double a, double b,
+                                                       const double* __restrict__ inject, const double* acc,
+                                                       double* __restrict__ ybar, double* out, const double* __restrict__ C,
+                                                       double* __restrict__ rows, Geom g)
+{
+    adjoint_body<true>(y, Kappa{lam, prev, a, b}, inject, acc, ybar, out, C, rows, g);
 }
 
 // one workgroup: sums the `nrows` partial rows in row order

@@ -10,6 +10,9 @@ so ``pa.discover(traj, dx, dt)`` -> ``LibraryCell.from_equations(eqs, dx, dt)`` 
 for whatever came out.  One fused launch per step and per adjoint step (``csrc/pi_lib.h``, ``include/percnn_pi_library_cell.h``);
 the 140 coefficient gradients are contractions on the float64 matrix cores.  float64, one [1,2,H,W] periodic state, dx = dy.
 No CPU path: CPU tensors raise.
+
+``integrator="rk4"`` takes the classical Runge-Kutta step of the reference cells' ``forward_rk4`` instead of the explicit Euler
+step: four right-hand sides in one launch forward, one recompute launch and one launch per stage backward.
 """
 from __future__ import annotations
 
@@ -24,6 +27,14 @@ from .discovery import LIBRARY_TERMS, _A, _B
 from .functional import _stream, _assemble_frame_grads, Frame
 
 NCOEF = 140                              # PERCNN_PI_LIB_COEFS
+INTEGRATORS = ("euler", "rk4")
+
+
+def _entry(integrator: str, name: str):
+    """the C entry point ``name`` of the step ``integrator`` takes"""
+    if integrator not in INTEGRATORS:
+        raise ValueError(f"LibraryCell: integrator must be one of {INTEGRATORS}, got {integrator!r}")
+    return getattr(_lib.lib(), f"percnn_pi_lib_{'rk4_' if integrator == 'rk4' else ''}{name}")
 
 
 def _check_state(t: torch.Tensor, name: str, lead) -> None:
@@ -48,37 +59,41 @@ def _check_coef(C: torch.Tensor) -> None:
         raise ValueError(f"LibraryCell: coef must be contiguous float64 [2,10,7], got {C.dtype} {tuple(C.shape)}")
 
 
-def step_fwd(h: torch.Tensor, C: torch.Tensor, dx: float, dt: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def step_fwd(h: torch.Tensor, C: torch.Tensor, dx: float, dt: float, out: Optional[torch.Tensor] = None,
+             integrator: str = "euler") -> torch.Tensor:
     """h: [1,2,H,W] -> the next state"""
+    fn = _entry(integrator, "step_fwd_f64")
     _check_state(h, "h", 1)
     _check_coef(C)
     out = torch.empty_like(h) if out is None else out
     with torch.cuda.device(h.device):
-        _lib.check(_lib.lib().percnn_pi_lib_step_fwd_f64(h.data_ptr(), out.data_ptr(), C.data_ptr(), _lib.shape_arg(h.shape[2:]),
-                                                        float(dx), float(dt), _stream()), "lib_step_fwd")
+        _lib.check(fn(h.data_ptr(), out.data_ptr(), C.data_ptr(), _lib.shape_arg(h.shape[2:]), float(dx), float(dt), _stream()),
+                   "lib_step_fwd")
     return out
 
 
-def rollout_fwd_(traj: torch.Tensor, C: torch.Tensor, dx: float, dt: float) -> torch.Tensor:
+def rollout_fwd_(traj: torch.Tensor, C: torch.Tensor, dx: float, dt: float, integrator: str = "euler") -> torch.Tensor:
     """In place: traj[0] holds the initial state, frames 1..T are written.  traj: [T+1,2,H,W]."""
+    fn = _entry(integrator, "rollout_fwd_f64")
     _check_state(traj, "traj", None)
     _check_coef(C)
     with torch.cuda.device(traj.device):
-        _lib.check(_lib.lib().percnn_pi_lib_rollout_fwd_f64(traj.data_ptr(), C.data_ptr(), _lib.shape_arg(traj.shape[2:]),
-                                                           traj.shape[0] - 1, float(dx), float(dt), _stream()), "lib_rollout_fwd")
+        _lib.check(fn(traj.data_ptr(), C.data_ptr(), _lib.shape_arg(traj.shape[2:]), traj.shape[0] - 1, float(dx), float(dt),
+                      _stream()), "lib_rollout_fwd")
     return traj
 
 
-def rollout_bwd(traj: torch.Tensor, g_traj: torch.Tensor, C: torch.Tensor, dx: float, dt: float, frame_mask=None):
+def rollout_bwd(traj: torch.Tensor, g_traj: torch.Tensor, C: torch.Tensor, dx: float, dt: float, frame_mask=None,
+                integrator: str = "euler"):
     """-> (dL/dh0 [2,H,W], dL/dC [2,10,7]: all 140 entries, whatever the support)"""
+    ws_bytes, fn = _entry(integrator, "rollout_bwd_workspace_bytes"), _entry(integrator, "rollout_bwd_f64")
     _check_state(traj, "traj", None)
     _check_state(g_traj, "g_traj", traj.shape[0])
     if g_traj.shape != traj.shape:
         raise ValueError(f"LibraryCell: g_traj must have the trajectory's shape {tuple(traj.shape)}, got {tuple(g_traj.shape)}")
     _check_coef(C)
     T, shape = traj.shape[0] - 1, traj.shape[2:]
-    L = _lib.lib()
-    ws = torch.empty(L.percnn_pi_lib_rollout_bwd_workspace_bytes(_lib.shape_arg(shape), T), dtype=torch.uint8, device=traj.device)
+    ws = torch.empty(ws_bytes(_lib.shape_arg(shape), T), dtype=torch.uint8, device=traj.device)
     mask = None
     if frame_mask is not None:
         assert len(frame_mask) == T + 1
@@ -86,9 +101,8 @@ def rollout_bwd(traj: torch.Tensor, g_traj: torch.Tensor, C: torch.Tensor, dx: f
     g_h0 = torch.empty_like(traj[0])
     gC = torch.empty((2, 10, 7), dtype=torch.float64, device=traj.device)
     with torch.cuda.device(traj.device):
-        _lib.check(L.percnn_pi_lib_rollout_bwd_f64(traj.data_ptr(), g_traj.data_ptr(), mask, g_h0.data_ptr(), gC.data_ptr(),
-                                                  ws.data_ptr(), ws.numel(), C.data_ptr(), _lib.shape_arg(shape), T, float(dx),
-                                                  float(dt), _stream()), "lib_rollout_bwd")
+        _lib.check(fn(traj.data_ptr(), g_traj.data_ptr(), mask, g_h0.data_ptr(), gC.data_ptr(), ws.data_ptr(), ws.numel(),
+                      C.data_ptr(), _lib.shape_arg(shape), T, float(dx), float(dt), _stream()), "lib_rollout_bwd")
         ws.record_stream(torch.cuda.current_stream())
     return g_h0, gC
 
@@ -98,14 +112,14 @@ class LibraryRolloutFramesFunction(torch.autograd.Function):
     ONE trajectory buffer and outputs of ONE autograd node; the trajectory itself rides along as the last output."""
 
     @staticmethod
-    def forward(ctx, h0, C, dx, dt, steps, frames):
+    def forward(ctx, h0, C, dx, dt, steps, frames, integrator="euler"):
         _check_state(h0, "h0", 1)
         C = C.contiguous()
         traj = torch.empty((steps + 1,) + tuple(h0.shape[1:]), dtype=torch.float64, device=h0.device)
         traj[0].copy_(h0[0])
-        rollout_fwd_(traj, C, dx, dt)
+        rollout_fwd_(traj, C, dx, dt, integrator=integrator)
         ctx.save_for_backward(traj, C)
-        ctx.dx, ctx.dt = dx, dt
+        ctx.dx, ctx.dt, ctx.integrator = dx, dt, integrator
         ctx.frames = tuple(int(k) for k in frames)
         ctx.set_materialize_grads(False)
         views = traj.unsqueeze(1).unbind(0)
@@ -121,7 +135,7 @@ class LibraryRolloutFramesFunction(torch.autograd.Function):
         traj, C = ctx.saved_tensors
         g_stacked, grads = grads[-1], grads[:-1]
         if g_stacked is None and all(g is None for g in grads):
-            return None, None, None, None, None, None
+            return None, None, None, None, None, None, None
         if g_stacked is not None and all(g is None for g in grads):
             g_traj, mask = g_stacked.contiguous(), None
         elif g_stacked is None:
@@ -131,8 +145,8 @@ class LibraryRolloutFramesFunction(torch.autograd.Function):
             for k, g in zip(ctx.frames, grads):
                 if g is not None:
                     g_traj[k].add_(g[0])
-        g_h0, gC = rollout_bwd(traj, g_traj, C, ctx.dx, ctx.dt, frame_mask=mask)
-        return g_h0[None], gC.reshape(C.shape), None, None, None, None
+        g_h0, gC = rollout_bwd(traj, g_traj, C, ctx.dx, ctx.dt, frame_mask=mask, integrator=ctx.integrator)
+        return g_h0[None], gC.reshape(C.shape), None, None, None, None, None
 
 
 def _term_index(term: str) -> int:
@@ -147,10 +161,15 @@ class LibraryCell(nn.Module):
     """Physics-based cell over the whole candidate library (module docstring).  ``coefficients``: a [2,10,7] array
     (``C[s][m][k]`` = coefficient of ``LIBRARY_TERMS[7m + k]`` in the equation of species s, physical units -- what
     ``discover()`` returns) .  ``support``: None = the entries that are non-zero now stay trainable, the others stay zero;
-    ``"dense"`` = all 140 train; or a [2,10,7] mask.  ``cell(h) -> (ch, ch)`` like the other cells."""
+    ``"dense"`` = all 140 train; or a [2,10,7] mask.  ``integrator``: ``"euler"`` (the step the reference trains with) or
+    ``"rk4"`` (its ``forward_rk4``) -- the step ``cell(h)``, ``rollout`` and ``rollout_frames`` take.
+    ``cell(h) -> (ch, ch)`` like the other cells."""
 
-    def __init__(self, coefficients, dx: float, dt: float, support=None):
+    def __init__(self, coefficients, dx: float, dt: float, support=None, integrator: str = "euler"):
         super().__init__()
+        if integrator not in INTEGRATORS:
+            raise ValueError(f"LibraryCell: integrator must be one of {INTEGRATORS}, got {integrator!r}")
+        self.integrator = integrator
         C = torch.as_tensor(np.asarray(coefficients.detach().cpu() if isinstance(coefficients, torch.Tensor) else coefficients,
                                        dtype=np.float64))
         if tuple(C.shape) != (2, 10, 7):
@@ -175,7 +194,7 @@ class LibraryCell(nn.Module):
 
     # ---- equations in, equations out ----------------------------------------------------------------------------------
     @classmethod
-    def from_equations(cls, eqs: dict, dx: float, dt: float, support=None) -> "LibraryCell":
+    def from_equations(cls, eqs: dict, dx: float, dt: float, support=None, integrator: str = "euler") -> "LibraryCell":
         """``eqs``: one dict as ``discover()`` returns it, ``{"u": {term: coefficient}, "v": {...}}``"""
         if not isinstance(eqs, dict) or set(eqs) - {"u", "v"}:
             raise ValueError(f"LibraryCell.from_equations: eqs must be {{'u': {{term: c}}, 'v': {{term: c}}}} (one sample of "
@@ -184,7 +203,7 @@ class LibraryCell(nn.Module):
         for s, sp in enumerate("uv"):
             for term, c in eqs.get(sp, {}).items():
                 C[s, _term_index(term)] = float(c)
-        return cls(C.reshape(2, 10, 7), dx, dt, support=support)
+        return cls(C.reshape(2, 10, 7), dx, dt, support=support, integrator=integrator)
 
     def equations(self) -> dict:
         """the current parameters as ``discover()`` would return them (entries off the support or equal to zero left out)"""
@@ -192,7 +211,7 @@ class LibraryCell(nn.Module):
         return {sp: {t: float(c) for t, c in zip(LIBRARY_TERMS, C[s]) if c != 0} for s, sp in enumerate("uv")}
 
     @classmethod
-    def from_cell(cls, cell) -> "LibraryCell":
+    def from_cell(cls, cell, integrator: str = "euler") -> "LibraryCell":
         """a ``Stage3BurgersCell`` or ``Stage3LambdaOmegaCell`` as the library cell of the same equation"""
         from .modules import Stage3BurgersCell, Stage3LambdaOmegaCell
         p = lambda n: float(getattr(cell, n).detach())
@@ -212,7 +231,7 @@ class LibraryCell(nn.Module):
         for s, sp in enumerate("uv"):
             for term, c in eqs[sp].items():
                 C[s, _term_index(term)], sup[s, _term_index(term)] = c, 1.0
-        out = cls(C.reshape(2, 10, 7), cell.dx, cell.dt, support=sup.reshape(2, 10, 7))
+        out = cls(C.reshape(2, 10, 7), cell.dx, cell.dt, support=sup.reshape(2, 10, 7), integrator=integrator)
         return out.to(next(cell.parameters()).device)
 
     # ---- the cell ---------------------------------------------------------------------------------------------------------
@@ -222,16 +241,22 @@ class LibraryCell(nn.Module):
 
     def rollout(self, h0: torch.Tensor, steps: int) -> torch.Tensor:
         """-> [steps+1,2,H,W], frame 0 = h0"""
-        return LibraryRolloutFramesFunction.apply(h0, self.param_block(), self.dx, self.dt, int(steps), ())[-1]
+        return LibraryRolloutFramesFunction.apply(h0, self.param_block(), self.dx, self.dt, int(steps), (), self.integrator)[-1]
 
     def rollout_frames(self, h0: torch.Tensor, steps: int, frames: Sequence[int], with_stacked: bool = False):
         """hook used by ``percnn_amd.RCNN``: the requested frames as outputs of one autograd node (with_stacked: plus, last, the
         [steps+1,2,H,W] trajectory they are views of)"""
-        out = LibraryRolloutFramesFunction.apply(h0, self.param_block(), self.dx, self.dt, int(steps), tuple(frames))
+        out = LibraryRolloutFramesFunction.apply(h0, self.param_block(), self.dx, self.dt, int(steps), tuple(frames),
+                                                 self.integrator)
         return out if with_stacked else out[:-1]
 
     def forward(self, h: torch.Tensor):
         ch = self.rollout(h, 1)[1:2]
+        return ch, ch
+
+    def forward_rk4(self, h: torch.Tensor):
+        """One fused, differentiable Runge-Kutta step whatever ``self.integrator`` is (the reference method's name)"""
+        ch = LibraryRolloutFramesFunction.apply(h, self.param_block(), self.dx, self.dt, 1, (), "rk4")[-1][1:2]
         return ch, ch
 
     def f_rhs(self, u, v):

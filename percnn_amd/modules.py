@@ -490,8 +490,9 @@ class Stage3LambdaOmegaCell(nn.Module):
 
     def forward_rk4(self, h):
         """One classical Runge-Kutta step with ``f_rhs`` (reference: ``forward_rk4``, lo3:154-201 -- defined there, never called).
-        Offered for completeness on stock tensor operations (differentiable through stock autograd, any device); the fused
-        kernels implement the explicit Euler ``forward`` the reference trains with."""
+        Stock tensor operations here (differentiable through stock autograd, any device); this cell's fused kernels implement
+        the explicit Euler ``forward`` the reference trains with.  The fused Runge-Kutta step, forward and backward, is
+        ``LibraryCell.from_cell(cell, integrator="rk4")``."""
         dt = self.dt
         u0, v0 = h[:, 0:1], h[:, 1:2]
         ku, kv = self.f_rhs(u0, v0)
@@ -588,8 +589,9 @@ class Stage3BurgersCell(nn.Module):
 
     def forward_rk4(self, h):
         """One classical Runge-Kutta step with ``f_rhs`` (reference: ``forward_rk4``, bur3:159-206 -- defined there, never called).
-        Offered for completeness on stock tensor operations (differentiable through stock autograd, any device); the fused
-        kernels implement the explicit Euler ``forward`` the reference trains with."""
+        Stock tensor operations here (differentiable through stock autograd, any device); this cell's fused kernels implement
+        the explicit Euler ``forward`` the reference trains with.  The fused Runge-Kutta step, forward and backward, is
+        ``LibraryCell.from_cell(cell, integrator="rk4")``."""
         dt = self.dt
         u0, v0 = h[:, 0:1], h[:, 1:2]
         ku, kv = self.f_rhs(u0, v0)

@@ -10,10 +10,18 @@ The routes are compared before anything is timed.  Timed with HIP events over a 
 the routes alternate --repeats times and every time is kept.  The spread of a route is (max - min) / min of its own repeats.
 
     python tools/library_cell_bench.py [--seconds 1.0] [--repeats 5] [--out profiles/library_cell.json]
+
+``--integrator rk4``: the same workload with the classical Runge-Kutta step, 200 steps, on two routes
+  (e) library_cell_rk4  ``LibraryCell.from_cell(Stage3BurgersCell(), integrator="rk4")``: one fused launch per step forward, one
+                        recompute launch and four stage launches per step backward
+  (f) stock_torch_rk4   a ``Stage3BurgersCell.forward_rk4`` loop with stock autograd
+next to (a), whose Euler step times four is the yardstick.  Forward only (no tape) and forward + backward of every route; the
+result goes to profiles/library_cell_rk4.json.
 """
 import argparse
 import json
 import os
+import re
 import subprocess
 import sys
 
@@ -90,7 +98,11 @@ def resource_usage():
     for line in err.splitlines():
         if "Function Name:" in line:
             name = line.split("Function Name:")[1].split()[0]
-            cur = out.setdefault(next((k for k in ("step_kernel", "adjoint_kernel", "finish_kernel") if k in name), name), {})
+            m = re.search(r"rk4_kernelILi(\d+)ELb([01])E", name)      # rk4_kernel<FT, STAGES>
+            if m:
+                name = f"rk4_kernel<{m.group(1)}, {'stages' if m.group(2) == '1' else 'step'}>"
+            cur = out.setdefault(next((k for k in ("step_kernel", "adjoint_kernel", "finish_kernel", "rk4_stage_kernel") if k in name),
+                                      name), {})
         elif cur is not None:
             for key in ("VGPRs:", "AGPRs:", "TotalSGPRs:", "ScratchSize [bytes/lane]:", "LDS Size [bytes/block]:", "Occupancy [waves/SIMD]:"):
                 if " " + key in line:
@@ -98,27 +110,107 @@ def resource_usage():
     return out
 
 
+def burgers_state(dev):
+    ys = torch.arange(H, dtype=torch.float64) / H
+    yy, xx = torch.meshgrid(ys, ys, indexing="ij")
+    tp = 2 * np.pi
+    u = torch.sin(tp * xx) * torch.cos(tp * yy) + 0.3 * torch.cos(2 * tp * xx + 0.5)
+    v = torch.cos(tp * xx) * torch.sin(tp * yy) - 0.2 * torch.sin(tp * (xx + 2 * yy))
+    return torch.stack((u, v))[None].to(dev).requires_grad_(True)
+
+
+def main_rk4(args, dev):
+    stage3 = pa.Stage3BurgersCell().to(dev)
+    euler = pa.LibraryCell.from_cell(stage3)
+    cell = pa.LibraryCell.from_cell(stage3, integrator="rk4")
+    h0 = burgers_state(dev)
+    names = list(pa.Stage3BurgersCell.INIT)
+    where = {"nu_u": (0, 0, 5), "C1_u": (0, 1, 1), "C2_u": (0, 2, 2), "nu_v": (1, 0, 6), "C1_v": (1, 1, 3), "C2_v": (1, 2, 4)}
+
+    def stock(h):
+        frames = [h]
+        for _ in range(STEPS):
+            frames.append(stage3.forward_rk4(frames[-1])[0])
+        return torch.cat(frames, 0)
+
+    def fwd_only(fn):
+        def run():
+            with torch.no_grad():
+                return fn()
+        return run
+
+    def grads_of(traj, params):
+        return torch.autograd.grad((traj ** 2).mean(), params + [h0])
+
+    forward = {"library_cell": lambda: euler.rollout(h0, STEPS), "library_cell_rk4": lambda: cell.rollout(h0, STEPS),
+               "stock_torch_rk4": lambda: stock(h0)}
+    params = {"library_cell": [euler.coef], "library_cell_rk4": [cell.coef], "stock_torch_rk4": [getattr(stage3, n) for n in names]}
+    routes = {}
+    for key, fn in forward.items():
+        routes[key + "/fwd"] = fwd_only(fn)
+        routes[key + "/fwd_bwd"] = (lambda fn=fn, key=key: grads_of(fn(), params[key]))
+
+    # same results first: the trajectory, the six scalar gradients and dL/dh0 of the two Runge-Kutta routes
+    ta, tb = routes["library_cell_rk4/fwd"](), routes["stock_torch_rk4/fwd"]()
+    ga, gb = routes["library_cell_rk4/fwd_bwd"](), routes["stock_torch_rk4/fwd_bwd"]()
+    a6 = torch.stack([ga[0][where[n]] for n in names])
+    diff = {"trajectory_rel_l2": float((ta - tb).norm() / tb.norm()),
+            "six_gradients_max_relative": float(((a6 - torch.stack(gb[:6])).abs() / torch.stack(gb[:6]).abs()).max()),
+            "dLdh0_rel_l2": float((ga[1] - gb[6]).norm() / gb[6].norm()),
+            "rk4_vs_euler_trajectory_rel_l2": float((ta - routes["library_cell/fwd"]()).norm() / ta.norm())}
+    if not (diff["trajectory_rel_l2"] < 1e-12 and diff["six_gradients_max_relative"] < 1e-9 and diff["dLdh0_rel_l2"] < 1e-11):
+        sys.exit(f"library_cell_bench.py: the Runge-Kutta routes disagree: {diff}")
+    del ta, tb, ga, gb
+
+    times = {k: [] for k in routes}
+    for _ in range(args.repeats):
+        for key, fn in routes.items():
+            times[key].append(round(timed(fn, args.seconds) / STEPS, 3))
+    spread = {k: round((max(v) - min(v)) / min(v), 4) for k, v in times.items()}
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    out = {"metric": "microseconds per step: rollout forward only (no tape) and forward + backward (one fine-tuning iteration / steps)",
+           "workload": {"shape": [H, W], "dtype": "float64", "steps": STEPS, "equation": "Burgers (Stage3BurgersCell.INIT)",
+                        "loss": "mean(traj^2)", "step": "classical Runge-Kutta; library_cell: explicit Euler, the yardstick"},
+           "device": torch.cuda.get_device_name(0), "seconds_per_region": args.seconds, "library": os.path.basename(_lib.LIB_PATH),
+           "us_per_step": times, "median": med, "spread": spread,
+           "four_euler_steps": {"fwd": round(4 * med["library_cell/fwd"], 3), "fwd_bwd": round(4 * med["library_cell/fwd_bwd"], 3)},
+           "rk4_fwd_below_four_euler_fwd": med["library_cell_rk4/fwd"] < 4 * med["library_cell/fwd"],
+           "rk4_fwd_bwd_below_four_euler_fwd_bwd": med["library_cell_rk4/fwd_bwd"] < 4 * med["library_cell/fwd_bwd"],
+           "library_cell_rk4_median_below_stock_torch_rk4_min":
+               med["library_cell_rk4/fwd_bwd"] < min(times["stock_torch_rk4/fwd_bwd"]),
+           "ratio_library_cell_rk4_over_stock_torch_rk4": {k: round(med["library_cell_rk4/" + k] / med["stock_torch_rk4/" + k], 5)
+                                                           for k in ("fwd", "fwd_bwd")},
+           "max_relative_difference_between_routes": diff, "kernel_resources": resource_usage()}
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+    if not out["library_cell_rk4_median_below_stock_torch_rk4_min"]:
+        sys.exit("library_cell_bench.py: the Runge-Kutta library cell's median is not below the stock route's minimum")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "library_cell.json"))
+    ap.add_argument("--integrator", choices=("euler", "rk4"), default="euler")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "library_cell.json" if args.integrator == "euler" else "library_cell_rk4.json")
     if not torch.cuda.is_available():
         sys.exit("library_cell_bench.py measures on a HIP device; none found")
     dev = torch.device("cuda:0")
+    if args.integrator == "rk4":
+        return main_rk4(args, dev)
     stage3 = pa.Stage3BurgersCell().to(dev)
     dx, dt = stage3.dx, stage3.dt
     cell = pa.LibraryCell.from_cell(stage3)
     rng = np.random.default_rng(0)
     dense = pa.LibraryCell(0.1 * rng.standard_normal((2, 10, 7)) * np.array([1, 1, 1, 1, 1, 1e-4, 1e-4]), dx, dt,
                            support="dense").to(dev)            # diffusion-like columns scaled to dx^2: the rollout stays bounded
-    ys = torch.arange(H, dtype=torch.float64) / H
-    yy, xx = torch.meshgrid(ys, ys, indexing="ij")
-    tp = 2 * np.pi
-    u = torch.sin(tp * xx) * torch.cos(tp * yy) + 0.3 * torch.cos(2 * tp * xx + 0.5)
-    v = torch.cos(tp * xx) * torch.sin(tp * yy) - 0.2 * torch.sin(tp * (xx + 2 * yy))
-    h0 = torch.stack((u, v))[None].to(dev).requires_grad_(True)
+    h0 = burgers_state(dev)
     rcnn = pa.RCNN(stage3, step=STEPS, effective_step=list(range(STEPS)), init_state=h0)
     names = list(pa.Stage3BurgersCell.INIT)
     where = {"nu_u": (0, 0, 5), "C1_u": (0, 1, 1), "C2_u": (0, 2, 2), "nu_v": (1, 0, 6), "C1_v": (1, 1, 3), "C2_v": (1, 2, 4)}
