@@ -79,6 +79,33 @@ int percnn_pi_lib_rk4_rollout_bwd_f64(const double* traj, const double* g_traj, 
                                       double* g_coef, void* workspace, size_t workspace_bytes, const double* coef,
                                       const int64_t* shape, int T_steps, double dx, double dt, void* stream);
 
+/* Ensembles: B trajectories in the launches of one, sample b with member b's 140 coefficients.  The eight calls above with
+ * `int B` after `shape`; the members share dx, dt and the integrator.  Dense layouts:
+ *   h, h_next, g_h0   [B][2][H][W]
+ *   traj, g_traj      [T+1][B][2][H][W]   (frame-major, what percnn_pi_library_moments reads)
+ *   coef, g_coef      double[B][140]
+ * frame_mask stays one byte per frame.  The workspace is B times the single-trajectory workspace of the same integrator.
+ * Refusals in the order above, with PERCNN_PI_EINVAL for B < 1 or B > 65535 right after the shape check and the overlap checks
+ * on the B-fold extents.  Sample b's trajectory, g_h0[b] and g_coef[b] are bit for bit what the single-trajectory calls give for
+ * that sample alone: those calls are B = 1 of the same code. */
+int percnn_pi_lib_ensemble_step_fwd_f64(const double* h, double* h_next, const double* coef, const int64_t* shape, int B, double dx,
+                                        double dt, void* stream);
+int percnn_pi_lib_ensemble_rollout_fwd_f64(double* traj, const double* coef, const int64_t* shape, int B, int T_steps, double dx,
+                                           double dt, void* stream);
+size_t percnn_pi_lib_ensemble_rollout_bwd_workspace_bytes(const int64_t* shape, int B, int T_steps);
+int percnn_pi_lib_ensemble_rollout_bwd_f64(const double* traj, const double* g_traj, const unsigned char* frame_mask, double* g_h0,
+                                           double* g_coef, void* workspace, size_t workspace_bytes, const double* coef,
+                                           const int64_t* shape, int B, int T_steps, double dx, double dt, void* stream);
+int percnn_pi_lib_rk4_ensemble_step_fwd_f64(const double* h, double* h_next, const double* coef, const int64_t* shape, int B,
+                                            double dx, double dt, void* stream);
+int percnn_pi_lib_rk4_ensemble_rollout_fwd_f64(double* traj, const double* coef, const int64_t* shape, int B, int T_steps, double dx,
+                                               double dt, void* stream);
+size_t percnn_pi_lib_rk4_ensemble_rollout_bwd_workspace_bytes(const int64_t* shape, int B, int T_steps);
+int percnn_pi_lib_rk4_ensemble_rollout_bwd_f64(const double* traj, const double* g_traj, const unsigned char* frame_mask,
+                                               double* g_h0, double* g_coef, void* workspace, size_t workspace_bytes,
+                                               const double* coef, const int64_t* shape, int B, int T_steps, double dx, double dt,
+                                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,6 @@ from .stage1 import Stage1Cell  # noqa: F401
 from .physics import physics_loss_batched  # noqa: F401
 from .discovery import LIBRARY_TERMS, LibraryMoments, row_class, library_moments, stridge, train_stridge, discover  # noqa: F401
 from . import library_cell  # noqa: F401
-from .library_cell import LibraryCell  # noqa: F401
+from .library_cell import LibraryCell, LibraryEnsemble  # noqa: F401
 
 __version__ = "0.1.0"

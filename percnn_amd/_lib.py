@@ -84,6 +84,10 @@ EXPORTS = [
     "percnn_pi_lib_rollout_bwd_f64",
     "percnn_pi_lib_rk4_step_fwd_f64", "percnn_pi_lib_rk4_rollout_fwd_f64", "percnn_pi_lib_rk4_rollout_bwd_workspace_bytes",
     "percnn_pi_lib_rk4_rollout_bwd_f64",
+    "percnn_pi_lib_ensemble_step_fwd_f64", "percnn_pi_lib_ensemble_rollout_fwd_f64",
+    "percnn_pi_lib_ensemble_rollout_bwd_workspace_bytes", "percnn_pi_lib_ensemble_rollout_bwd_f64",
+    "percnn_pi_lib_rk4_ensemble_step_fwd_f64", "percnn_pi_lib_rk4_ensemble_rollout_fwd_f64",
+    "percnn_pi_lib_rk4_ensemble_rollout_bwd_workspace_bytes", "percnn_pi_lib_rk4_ensemble_rollout_bwd_f64",
 ]
 
 
@@ -340,6 +344,15 @@ def lib() -> ctypes.CDLL:
         f.restype, f.argtypes = sz, [i64p, ci]
         f = getattr(L, pre + "rollout_bwd_f64")
         f.restype, f.argtypes = ci, [vp, vp, ctypes.c_char_p, vp, vp, vp, sz, vp, i64p, ci, cd, cd, vp]
+        # B members per launch: the same signatures with `B` after `shape`
+        f = getattr(L, pre + "ensemble_step_fwd_f64")
+        f.restype, f.argtypes = ci, [vp, vp, vp, i64p, ci, cd, cd, vp]
+        f = getattr(L, pre + "ensemble_rollout_fwd_f64")
+        f.restype, f.argtypes = ci, [vp, vp, i64p, ci, ci, cd, cd, vp]
+        f = getattr(L, pre + "ensemble_rollout_bwd_workspace_bytes")
+        f.restype, f.argtypes = sz, [i64p, ci, ci]
+        f = getattr(L, pre + "ensemble_rollout_bwd_f64")
+        f.restype, f.argtypes = ci, [vp, vp, ctypes.c_char_p, vp, vp, vp, sz, vp, i64p, ci, ci, cd, cd, vp]
     # process-wide tuning defaults from the environment ("key=value,..."; the keys of percnn_pi_set_option) -- what a launcher
     # uses to A/B an option in worker processes it does not construct itself
     spec = os.environ.get("PERCNN_PI_OPTIONS", "")

@@ -34,6 +34,14 @@
 //                 the running sum that becomes the step's outgoing adjoint.
 // Partial sums: one row of 140 doubles per workgroup, each workgroup adds only to its own row, launch after launch in stream
 // order; finish_kernel sums the rows in a fixed order.  No floating-point atomics: the same call twice gives the same bits.
+//
+// Samples: every launch carries the sample index on blockIdx.z (B = gridDim.z members of an ensemble; one trajectory is B = 1 of
+// the same bodies).  Sample z reads and writes its own [2][H][W] slice of a dense [B][2][H][W] state (`sample`), member z's 140
+// coefficients (C + 140 z: blockIdx.z is uniform over the workgroup, so the coefficient reads stay scalar loads and nonzero_mask
+// / the column skip work per member) and its own nblocks rows of partial sums.  finish_kernel runs one workgroup per sample, so
+// sample z's results are the bits the B = 1 launch gives for that sample alone.  Every body exists twice, <SAMPLES> true for
+// B > 1 and false for B = 1, where the offsets are zero: these launches wait for their first load, and the offset arithmetic in
+// front of it cost the single-trajectory route 1 % (3.71 against 3.68 us per Euler step at 100^2); <false> is the code without it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -51,11 +59,24 @@ constexpr int FH = 8;                                   // halo of the forward R
 // arithmetic, and a workgroup's time is its serial right-hand sides per lane -- 5 on the 8-wide tile (169 workgroups at 100^2,
 // 3.4 x redundant evaluations), 10 on the 16-wide one (49 workgroups, 2.0 x).  The small tile while every workgroup still gets a
 // compute unit of its own (256 on MI355X), the 16-wide tile beyond.
+// An ensemble launch of B samples fills the chip, so its workgroups run in rounds of the resident ones -- LDS admits 5 workgroups
+// of the 8-wide tile per compute unit (1280 on MI355X) and 3 of the 16-wide one (768) -- and a round costs the serial right-hand
+// sides: the tile with fewer rounds x right-hand sides, the 16-wide one on a tie.  That is the faster tile at every measured
+// B x 100^2 (profiles/library_cell_ensemble.json), where counting B x tiles against the 256 of one trajectory chose the slower
+// one at B = 2, 4 and 16.  B = 1 is the rule above.
 constexpr int RK4_SMALL_TILE_BLOCKS = 256;
+constexpr int RK4_RESIDENT_8 = 1280, RK4_RESIDENT_16 = 768, RK4_SERIAL_8 = 5, RK4_SERIAL_16 = 10;
 
-__host__ __device__ inline int rk4_tile(int H, int W)
+__host__ __device__ inline int rk4_tile(int H, int W, int B = 1)
 {
-    return (long)((H + 7) / 8) * ((W + 7) / 8) <= RK4_SMALL_TILE_BLOCKS ? 8 : 16;
+#ifdef PERCNN_PI_LIB_RK4_TILE                               // measurement builds (tools/library_cell_bench.py): one tile everywhere
+    return PERCNN_PI_LIB_RK4_TILE;
+#endif
+    const long n8 = (long)B * ((H + 7) / 8) * ((W + 7) / 8), n16 = (long)B * ((H + 15) / 16) * ((W + 15) / 16);
+    if (B == 1) return n8 <= RK4_SMALL_TILE_BLOCKS ? 8 : 16;
+    const long cost8 = (n8 + RK4_RESIDENT_8 - 1) / RK4_RESIDENT_8 * RK4_SERIAL_8;
+    const long cost16 = (n16 + RK4_RESIDENT_16 - 1) / RK4_RESIDENT_16 * RK4_SERIAL_16;
+    return cost8 < cost16 ? 8 : 16;
 }
 
 typedef double d4 __attribute__((ext_vector_type(4)));
@@ -67,6 +88,29 @@ struct Geom {
 };
 
 __host__ __device__ inline int cidx(int s, int m, int k) { return (s * NA + m) * NB + k; }
+
+// this workgroup's sample (blockIdx.z) of a dense [B][2][H][W] state; sample_opt: of a pointer that may be NULL
+template <bool SAMPLES, class T>
+__device__ inline T* sample(T* p, const Geom& g)
+{
+    if constexpr (!SAMPLES) return p;
+    return p + (long)blockIdx.z * 2 * g.plane;
+}
+
+template <bool SAMPLES, class T>
+__device__ inline T* sample_opt(T* p, const Geom& g)
+{
+    if constexpr (!SAMPLES) return p;
+    return p ? p + (long)blockIdx.z * 2 * g.plane : nullptr;
+}
+
+// member z's coefficients of [B][140]
+template <bool SAMPLES>
+__device__ inline const double* sample_coef(const double* C)
+{
+    if constexpr (!SAMPLES) return C;
+    return C + blockIdx.z * NCOEF;
+}
 
 __device__ inline int wrapi(int v, int n)
 {
@@ -161,9 +205,11 @@ __device__ inline double rhs_of(const double* __restrict__ C, const NonZero& nz,
     return rhs;
 }
 
+template <bool SAMPLES>
 __global__ __launch_bounds__(NT) void step_kernel(const double* __restrict__ h, double* __restrict__ out,
                                                   const double* __restrict__ C, Geom g)
 {
+    C = sample_coef<SAMPLES>(C); h = sample<SAMPLES>(h, g); out = sample<SAMPLES>(out, g);
     const NonZero nz = nonzero_mask(C);
     const long idx = (long)blockIdx.x * NT + threadIdx.x;
     if (idx >= g.plane) return;
@@ -240,8 +286,8 @@ __device__ inline void rk4_stage(const double* y, const double* hb, double* nb, 
     }
 }
 
-// grid (ceil(W / FT), ceil(H / FT)).  out: the next state [2][H][W]; STAGES: y2, y3, y4 as [3][2][H][W]
-template <int FT, bool STAGES>
+// grid (ceil(W / FT), ceil(H / FT), B).  out: the next state [B][2][H][W]; STAGES: y2, y3, y4 as [3][B][2][H][W]
+template <int FT, bool STAGES, bool SAMPLES>
 __global__ __launch_bounds__(NT) void rk4_kernel(const double* __restrict__ h, double* __restrict__ out,
                                                  const double* __restrict__ C, Geom g)
 {
@@ -249,6 +295,8 @@ __global__ __launch_bounds__(NT) void rk4_kernel(const double* __restrict__ h, d
     __shared__ double hb[2 * FWIN], pb[2 * FWIN], qb[2 * FWIN];
     const int tid = threadIdx.x;
     const int ty0 = blockIdx.y * FT, tx0 = blockIdx.x * FT;
+    C = sample_coef<SAMPLES>(C); h = sample<SAMPLES>(h, g); out = sample<SAMPLES>(out, g);
+    const long planes = SAMPLES ? (long)gridDim.z * g.plane : g.plane;      // 2 planes: from y_i to y_{i+1} of the same sample
     const NonZero nz = nonzero_mask(C);
     // the halo may wrap the grid more than once: a true modulo
     for (int i = tid; i < FWIN; i += NT) {
@@ -272,8 +320,8 @@ __global__ __launch_bounds__(NT) void rk4_kernel(const double* __restrict__ h, d
 #pragma unroll
         for (int j = 0; j < KPL; ++j)
             if (at[j] >= 0) {
-                out[(2 * i) * g.plane + at[j]] = yb[slot[j]];
-                out[(2 * i + 1) * g.plane + at[j]] = yb[FWIN + slot[j]];
+                out[(2 * i) * planes + at[j]] = yb[slot[j]];
+                out[(SAMPLES ? (2 * i) * planes + g.plane : (2 * i + 1) * g.plane) + at[j]] = yb[FWIN + slot[j]];
             }
     };
     double ku[KPL] = {}, kv[KPL] = {}, su[KPL], sv[KPL];
@@ -454,33 +502,47 @@ __device__ inline void adjoint_body(const double* __restrict__ h, const Kappa ka
     }
 }
 
-// grid (ceil(W / 16), ceil(H / 16)); inject may be NULL (the frame carries no gradient); rows: [blocks][140], added to
+// the rows of partial sums of this workgroup's sample
+template <bool SAMPLES>
+__device__ inline double* sample_rows(double* rows)
+{
+    if constexpr (!SAMPLES) return rows;
+    return rows + (long)blockIdx.z * gridDim.y * gridDim.x * NCOEF;
+}
+
+// grid (ceil(W / 16), ceil(H / 16), B); inject may be NULL (the frame carries no gradient); rows: [B][blocks][140], added to
+template <bool SAMPLES>
 __global__ __launch_bounds__(NT) void adjoint_kernel(const double* __restrict__ h, const double* __restrict__ G,
                                                      const double* __restrict__ inject, double* __restrict__ out,
                                                      const double* __restrict__ C, double* __restrict__ rows, Geom g)
 {
-    adjoint_body<false>(h, Kappa{G, nullptr, g.dt, 0.0}, inject, nullptr, nullptr, out, C, rows, g);
+    adjoint_body<false>(sample<SAMPLES>(h, g), Kappa{sample<SAMPLES>(G, g), nullptr, g.dt, 0.0}, sample_opt<SAMPLES>(inject, g),
+                        nullptr, nullptr, sample<SAMPLES>(out, g), sample_coef<SAMPLES>(C), sample_rows<SAMPLES>(rows), g);
 }
 
 // one Runge-Kutta stage of the adjoint, same grid: y the stage state, kappa = a lam + b prev (prev NULL: a lam);
 // ybar (may be NULL) = J(y)^T kappa;  out = (acc + inject) + ybar, out may be acc.  g.dt is not used: a and b carry it
+template <bool SAMPLES>
 __global__ __launch_bounds__(NT) void rk4_stage_kernel(const double* __restrict__ y, const double* __restrict__ lam,
                                                        const double* __restrict__ prev, double a, double b,
                                                        const double* __restrict__ inject, const double* acc,
                                                        double* __restrict__ ybar, double* out, const double* __restrict__ C,
                                                        double* __restrict__ rows, Geom g)
 {
-    adjoint_body<true>(y, Kappa{lam, prev, a, b}, inject, acc, ybar, out, C, rows, g);
+    adjoint_body<true>(sample<SAMPLES>(y, g), Kappa{sample<SAMPLES>(lam, g), sample_opt<SAMPLES>(prev, g), a, b},
+                       sample_opt<SAMPLES>(inject, g), sample<SAMPLES>(acc, g), sample_opt<SAMPLES>(ybar, g), sample<SAMPLES>(out, g),
+                       sample_coef<SAMPLES>(C), sample_rows<SAMPLES>(rows), g);
 }
 
-// one workgroup: sums the `nrows` partial rows in row order
+// one workgroup per sample (grid (1, 1, B)): sums the sample's `nrows` partial rows in row order into gC [B][140]
 __global__ __launch_bounds__(FIN_NT) void finish_kernel(const double* __restrict__ rows, int nrows, double* __restrict__ gC)
 {
     const int e = threadIdx.x;
     if (e >= NCOEF) return;
+    rows += (long)blockIdx.z * nrows * NCOEF;
     double s = 0.0;
     for (int r = 0; r < nrows; ++r) s += rows[(long)r * NCOEF + e];
-    gC[e] = s;
+    gC[blockIdx.z * NCOEF + e] = s;
 }
 
 }  // namespace lib

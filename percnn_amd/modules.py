@@ -881,6 +881,19 @@ class RCNN(nn.Module):
                              f"got {None if h is None else tuple(h.shape)}")
         return True
 
+    def _library_ensemble(self, what: str) -> bool:
+        """a LibraryEnsemble: B trajectories of its own kernels, B == len(cells); forward() and trajectory() only"""
+        from .library_cell import LibraryEnsemble
+        if not isinstance(self.cell, LibraryEnsemble):
+            return False
+        if what not in ("RCNN.forward()", "RCNN.trajectory()"):
+            raise ValueError(f"{what}: LibraryEnsemble has no fused loss path; write the loss on forward() / trajectory()")
+        h = self.init_state
+        if h is None or h.dim() != 4 or h.shape[0] != len(self.cell):
+            raise ValueError(f"{what}: a LibraryEnsemble of {len(self.cell)} cells needs an initial state "
+                             f"[{len(self.cell)},2,H,W], got {None if h is None else tuple(h.shape)}")
+        return True
+
     def _check_batchable(self, what: str) -> None:
         if hasattr(self.cell, "rollout") or isinstance(self.cell, Stage3BurgersCell):
             raise ValueError(f"{what}: batched initial states (B > 1) need a cell on the Pi-block kernels; "
@@ -891,6 +904,8 @@ class RCNN(nn.Module):
         [B,2,*S]: [step+1, B, 2, *S]."""
         if hasattr(self, "UpconvBlock"):
             self.init_state = self.UpconvBlock(self.init_state_low)
+        if self._library_ensemble("RCNN.trajectory()"):
+            return self.cell.rollout(self.init_state, self.step)
         if self._ensemble("RCNN.trajectory()"):
             return F_pi.pi_rollout_ensemble(self.init_state, self._block(), self.step)
         if self._batched():
@@ -905,6 +920,7 @@ class RCNN(nn.Module):
         on (train_2drd.py:397, train_3drd.py:403) -- from ONE autograd node that never builds the dense dL/dtraj.
         Needs a dense ``effective_step``.  The full (detached) trajectory of the same rollout is kept in
         ``self.last_trajectory`` for validation-only consumers (the physics loss, train_2drd.py:405)."""
+        self._library_ensemble("RCNN.observe()")
         if self.effective_step != list(range(self.step)):
             raise ValueError("observe() indexes the dense output list: effective_step must be list(range(step))")
         if hasattr(self, "UpconvBlock"):
@@ -934,6 +950,7 @@ class RCNN(nn.Module):
           its result.
 
         The full (detached) trajectory is kept in ``self.last_trajectory``."""
+        self._library_ensemble("RCNN.loss_mse()")
         if self._batched() or isinstance(self.cell, CellEnsemble) or (
                 hasattr(self, "UpconvBlock") and self.init_state_low is not None and self.init_state_low.shape[0] > 1):
             raise ValueError("loss_mse() takes one trajectory: batched initial states (B > 1) go through forward() / trajectory()")
@@ -968,6 +985,7 @@ class RCNN(nn.Module):
         like ``traj[t_slice][:, :, :, ::s, ::s(, ::s)]`` (None: 0), and the loss lives on that sub-lattice of the selected
         frames (``pi_rollout_obs_sqerr_batched`` / ``pi_rollout_obs_sqerr_ensemble``); what ``loss_mse(space_stride > 1)``
         is for one trajectory, still one autograd node without a dL/dtraj."""
+        self._library_ensemble("RCNN.sample_losses()")
         if self.effective_step != list(range(self.step)):
             raise ValueError("sample_losses() indexes the dense output list: effective_step must be list(range(step))")
         if hasattr(self, "UpconvBlock"):
@@ -1000,6 +1018,7 @@ class RCNN(nn.Module):
         batched / ensemble rollout backward on the materialised dL/dtraj.  The detached trajectory is kept in
         ``self.last_trajectory``."""
         from . import physics
+        self._library_ensemble("RCNN.sample_physics_losses()")
         traj = self.trajectory()
         if traj.dim() == self.init_state.dim():             # one trajectory [step+1, 2, *S]
             traj = traj.unsqueeze(1)
@@ -1027,7 +1046,9 @@ class RCNN(nn.Module):
         if self.step >= 2:
             frames.append(self.step - 1)                    # second_last_state rides along as one more output
         stacked = None
-        if self._ensemble("RCNN.forward()"):               # B trajectories, B blocks: frames and stacked as batched
+        if self._library_ensemble("RCNN.forward()"):       # B library cells: frames [B,2,H,W], stacked [(step+1)*B,2,H,W]
+            outs = self.cell.rollout_frames(self.init_state, self.step, frames, with_stacked=True)
+        elif self._ensemble("RCNN.forward()"):             # B trajectories, B blocks: frames and stacked as batched
             outs = F_pi.pi_rollout_ensemble_frames(self.init_state, self._block(), self.step, frames, with_stacked=True)
         elif self._batched():                               # B trajectories: frames [B,2,*S], stacked [(step+1)*B,2,*S]
             self._check_batchable("RCNN.forward()")

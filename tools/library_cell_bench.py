@@ -17,6 +17,15 @@ the routes alternate --repeats times and every time is kept.  The spread of a ro
   (f) stock_torch_rk4   a ``Stage3BurgersCell.forward_rk4`` loop with stock autograd
 next to (a), whose Euler step times four is the yardstick.  Forward only (no tape) and forward + backward of every route; the
 result goes to profiles/library_cell_rk4.json.
+
+``--ensemble B[,B...]`` (e.g. ``1,2,4,8,16``): the same workload with one Burgers equation per member (the Stage-3 parameters
+scaled by 1 + b / 100, the state shifted by 7 b columns), both integrators, forward only and forward + backward, on two routes
+  (g) ensemble    ONE ``LibraryEnsemble`` rollout: B members in the launches of one (the sample index on blockIdx.z)
+  (h) sequential  B ``LibraryCell`` rollouts one after the other, what a user had before the ensemble
+compared bit for bit before anything is timed, alternating; microseconds per step of the whole ensemble.  Where B x tiles crosses
+``rk4_tile``'s 256 workgroups the Runge-Kutta forward launch switches to its 16-wide tile: route (g)'s Runge-Kutta timings are
+repeated in child processes on two builds with the tile pinned (``-DPERCNN_PI_LIB_RK4_TILE=8`` / ``=16``, built once into
+tools/scratch/; ``--rebuild-tiles`` builds them again).  The result goes to profiles/library_cell_ensemble.json.
 """
 import argparse
 import json
@@ -190,18 +199,161 @@ def main_rk4(args, dev):
         sys.exit("library_cell_bench.py: the Runge-Kutta library cell's median is not below the stock route's minimum")
 
 
+def tile_library(tile, rebuild=False):
+    """libpercnn_pi.so with the Runge-Kutta forward tile pinned: csrc/pi_lib_abi.hip compiled with -DPERCNN_PI_LIB_RK4_TILE,
+    linked with the committed build's other objects"""
+    scratch = os.path.join(ROOT, "tools", "scratch")
+    out = os.path.join(scratch, f"libpercnn_pi_rk4tile{tile}.so")
+    if os.path.exists(out) and not rebuild:
+        return out
+    os.makedirs(scratch, exist_ok=True)
+    _lib.build()                                            # the objects of the other translation units
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    obj = os.path.join(scratch, f"pi_lib_abi_rk4tile{tile}.o")
+    subprocess.check_call([hipcc] + _lib.HIPCC_FLAGS + [f"-DPERCNN_PI_LIB_RK4_TILE={tile}", "-c", "-o", obj,
+                                                         os.path.join(_lib.CSRC, "pi_lib_abi.hip")], cwd=_lib.CSRC)
+    objs = [os.path.join(_lib.CSRC, src.replace(".hip", ".o")) for src in _lib.SOURCES if src != "pi_lib_abi.hip"] + [obj]
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", out] + objs, cwd=_lib.CSRC)
+    return out
+
+
+def ensemble_routes(B, integrator, dev):
+    """{"fwd/ensemble", "fwd/sequential", "fwd_bwd/ensemble", "fwd_bwd/sequential"} of B Burgers members"""
+    cells = []
+    for b in range(B):
+        stage3 = pa.Stage3BurgersCell().to(dev)
+        with torch.no_grad():
+            for p in stage3.parameters():
+                p.mul_(1.0 + b / 100.0)
+        cells.append(pa.LibraryCell.from_cell(stage3, integrator=integrator))
+    ens = pa.LibraryEnsemble(cells)
+    base = burgers_state(dev).detach()
+    h0 = torch.cat([torch.roll(base, 7 * b, -1) for b in range(B)]).requires_grad_(True)
+    singles = [h0.detach()[b:b + 1].clone().requires_grad_(True) for b in range(B)]
+    coefs = [c.coef for c in cells]
+
+    def ensemble():
+        return ens.rollout(h0, STEPS)
+
+    def sequential():
+        return [c.rollout(h, STEPS) for c, h in zip(cells, singles)]
+
+    def no_grad(fn):
+        def run():
+            with torch.no_grad():
+                return fn()
+        return run
+
+    def ensemble_grads():
+        t = ensemble()
+        return torch.autograd.grad((t ** 2).sum() / t.numel(), coefs + [h0])
+
+    def sequential_grads():
+        # the ensemble's loss: the mean over all B trajectories
+        return [torch.autograd.grad((t ** 2).sum() / (B * t.numel()), [c.coef, h]) for t, c, h in zip(sequential(), cells, singles)]
+
+    routes = {"fwd/ensemble": no_grad(ensemble), "fwd/sequential": no_grad(sequential), "fwd_bwd/ensemble": ensemble_grads,
+              "fwd_bwd/sequential": sequential_grads}
+    # the same bits first: trajectories, coefficient gradients, dL/dh0
+    te, ts = routes["fwd/ensemble"](), routes["fwd/sequential"]()
+    ge, gs = ensemble_grads(), sequential_grads()
+    same = all(torch.equal(te[:, b], ts[b]) and torch.equal(ge[b], gs[b][0]) and torch.equal(ge[B][b:b + 1], gs[b][1])
+               for b in range(B))
+    if not same:
+        sys.exit(f"library_cell_bench.py: the ensemble and the sequential route differ at B = {B}, {integrator}")
+    return routes
+
+
+def time_routes(routes, args):
+    """{route: [microseconds per step of the whole ensemble, one per repeat]}, the routes alternating"""
+    times = {k: [] for k in routes}
+    for _ in range(args.repeats):
+        for key, fn in routes.items():
+            times[key].append(round(timed(fn, args.seconds) / STEPS, 3))
+    return times
+
+
+def summary(times):
+    return {"us_per_step": times, "median": {k: float(np.median(v)) for k, v in times.items()},
+            "spread": {k: round((max(v) - min(v)) / min(v), 4) for k, v in times.items()}}
+
+
+def main_ensemble_child(args, dev):
+    """route (g) with the Runge-Kutta step only, on the library PERCNN_PI_LIB names: one JSON line"""
+    out = {}
+    for B in args.ensemble:
+        routes = ensemble_routes(B, "rk4", dev)
+        out[str(B)] = summary(time_routes({k: v for k, v in routes.items() if k.endswith("/ensemble")}, args))
+    print("TILE_CHILD " + json.dumps(out))
+
+
+def main_ensemble(args, dev):
+    results = {}
+    for B in args.ensemble:
+        for integrator in ("euler", "rk4"):
+            res = summary(time_routes(ensemble_routes(B, integrator, dev), args))
+            med, t = res["median"], res["us_per_step"]
+            res["sequential_over_ensemble"] = {m: round(med[m + "/sequential"] / med[m + "/ensemble"], 4) for m in ("fwd", "fwd_bwd")}
+            # faster by more than the spread of both routes: the slowest ensemble repeat below the fastest sequential repeat
+            res["every_ensemble_repeat_below_every_sequential_repeat"] = {
+                m: max(t[m + "/ensemble"]) < min(t[m + "/sequential"]) for m in ("fwd", "fwd_bwd")}
+            results.setdefault(str(B), {})[integrator] = res
+            print(B, integrator, json.dumps(res["median"]), file=sys.stderr)
+    tiles = {}
+    for tile in (8, 16):
+        env = dict(os.environ, PERCNN_PI_LIB=tile_library(tile, args.rebuild_tiles))
+        cmd = [sys.executable, os.path.abspath(__file__), "--ensemble", ",".join(map(str, args.ensemble)), "--tile-child",
+               "--seconds", str(args.seconds), "--repeats", str(args.repeats)]
+        line = [ln for ln in subprocess.run(cmd, env=env, capture_output=True, text=True, check=True).stdout.splitlines()
+                if ln.startswith("TILE_CHILD ")][-1]
+        tiles[str(tile)] = json.loads(line[len("TILE_CHILD "):])
+    def tile_rule(B):                                       # csrc/pi_lib.h: rk4_tile
+        n8, n16 = B * ((H + 7) // 8) * ((W + 7) // 8), B * ((H + 15) // 16) * ((W + 15) // 16)
+        if B == 1:
+            return 8 if n8 <= 256 else 16
+        return 8 if -(-n8 // 1280) * 5 < -(-n16 // 768) * 10 else 16
+
+    rule = {str(B): tile_rule(B) for B in args.ensemble}
+    out = {"metric": "microseconds per step of the whole ensemble (B members advance one step): rollout forward only (no tape) and "
+                     "forward + backward (one fine-tuning iteration / steps)",
+           "workload": {"shape": [H, W], "dtype": "float64", "steps": STEPS, "members": args.ensemble,
+                        "equation": "Burgers (Stage3BurgersCell.INIT scaled by 1 + b / 100 per member)", "loss": "mean(traj^2)"},
+           "routes": {"ensemble": "one LibraryEnsemble rollout", "sequential": "B LibraryCell rollouts one after the other"},
+           "device": torch.cuda.get_device_name(0), "seconds_per_region": args.seconds, "repeats": args.repeats,
+           "results": results,
+           "rk4_tile": {"rule": rule, "ensemble_route_with_the_tile_pinned": tiles,
+                        "note": "own processes on builds with -DPERCNN_PI_LIB_RK4_TILE; the tile changes no bit"}}
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+    if 4 in args.ensemble:
+        lost = [(i, m) for i in ("euler", "rk4") for m in ("fwd", "fwd_bwd")
+                if not results["4"][i]["every_ensemble_repeat_below_every_sequential_repeat"][m]]
+        if lost:
+            sys.exit(f"library_cell_bench.py: at B = 4 the ensemble route is not faster than the sequential route beyond the "
+                     f"spread of their repeats: {lost}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--integrator", choices=("euler", "rk4"), default="euler")
+    ap.add_argument("--ensemble", default=None, type=lambda s: [int(b) for b in s.split(",")], metavar="B[,B...]")
+    ap.add_argument("--rebuild-tiles", action="store_true")
+    ap.add_argument("--tile-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "library_cell.json" if args.integrator == "euler" else "library_cell_rk4.json")
+        args.out = os.path.join(ROOT, "profiles", "library_cell_ensemble.json" if args.ensemble else
+                                "library_cell.json" if args.integrator == "euler" else "library_cell_rk4.json")
     if not torch.cuda.is_available():
         sys.exit("library_cell_bench.py measures on a HIP device; none found")
     dev = torch.device("cuda:0")
+    if args.ensemble:
+        return main_ensemble_child(args, dev) if args.tile_child else main_ensemble(args, dev)
     if args.integrator == "rk4":
         return main_rk4(args, dev)
     stage3 = pa.Stage3BurgersCell().to(dev)
