@@ -1029,7 +1029,7 @@ class PiRolloutFunction(torch.autograd.Function):
 
 
 def _dense_prefix_view(grads, traj):
-    """The T+1 per-frame gradients as ONE [T+1,2,*S] view if they are consecutive slices of one buffer, else None."""
+    """The T+1 per-frame gradients as ONE view of traj's shape if they are consecutive slices of one buffer, else None."""
     T1 = traj.shape[0]
     g0 = grads[0]
     if any(g is None for g in grads) or not g0.is_contiguous() or g0.dtype != traj.dtype:
@@ -1047,7 +1047,7 @@ def _dense_prefix_view(grads, traj):
 
 
 def _assemble_frame_grads(grads, frames, traj):
-    """dL/dtraj from the per-frame gradients autograd hands back.  ``frames`` = the dense list 0..T (what
+    """dL/dtraj [T+1,R,2,*S] from the per-frame gradients [R,2,*S] autograd hands back.  ``frames`` = the dense list 0..T (what
     ``torch.cat(tuple(outputs))`` followed by any dense loss produces: CatBackward narrows its incoming gradient, so
     the per-frame gradients are consecutive slices of one buffer -> zero-copy view), optionally FOLLOWED by extra
     frames (``RCNN.forward`` returns ``second_last_state`` as one more output): extras without a gradient cost
@@ -1062,7 +1062,7 @@ def _assemble_frame_grads(grads, frames, traj):
                 return view, None
             g_traj = view.clone()                              # autograd owns `view`: never accumulate into it
             for k, g in extras:
-                g_traj[k].add_(g[0])
+                g_traj[k].add_(g)
             return g_traj, None
     g_traj = torch.empty_like(traj)
     mask = [False] * T1
@@ -1070,9 +1070,9 @@ def _assemble_frame_grads(grads, frames, traj):
         if g is None:
             continue
         if mask[k]:
-            g_traj[k].add_(g[0])
+            g_traj[k].add_(g)
         else:
-            g_traj[k].copy_(g[0])
+            g_traj[k].copy_(g)
             mask[k] = True
     return g_traj, mask
 
@@ -1134,6 +1134,37 @@ def link_frames(frames: Sequence[torch.Tensor], stacked: torch.Tensor) -> None:
             f._pi_stacked = stacked
 
 
+def frame_outputs(ctx, buf: torch.Tensor, frames: Sequence[int]):
+    """Forward half of the frame-list protocol every fused rollout node shares.  buf: the trajectory buffer [T+1,R,2,*S]
+    (R = 1: one trajectory, R = B: a batch or an ensemble).  -> the requested frames ``buf[k]`` [R,2,*S] as ``Frame``s (what makes
+    the caller's ``torch.cat(tuple(outputs))`` free) and, LAST, the buffer as [(T+1)*R,2,*S]: what that ``torch.cat`` is."""
+    ctx.frames = tuple(int(k) for k in frames)
+    ctx.set_materialize_grads(False)
+    views = buf.unbind(0)                                   # all frame views in one call
+    outs = []
+    for k in ctx.frames:
+        f = views[k].as_subclass(Frame)
+        f._pi_index = k
+        outs.append(f)
+    return tuple(outs) + (buf.view((-1,) + tuple(buf.shape[2:])),)
+
+
+def frame_grads(frames, grads, buf: torch.Tensor):
+    """Backward half: ``grads`` = the gradients of ``frame_outputs``' outputs (one per frame, then the stacked one).
+    -> None when nothing carries a gradient, else (dL/dtraj of buf's shape, contiguous; frame mask or None = every frame)."""
+    g_stacked, grads = grads[-1], grads[:-1]
+    per_frame = any(g is not None for g in grads)
+    if g_stacked is None:
+        return _assemble_frame_grads(grads, frames, buf) if per_frame else None
+    if not per_frame:                                       # the loss was written on `outputs.stacked` alone: zero-copy
+        return g_stacked.contiguous().view(buf.shape), None
+    g_traj = g_stacked.clone(memory_format=torch.contiguous_format).view(buf.shape)
+    for k, g in zip(frames, grads):                         # both: per-frame gradients on top of a copy of the stacked one
+        if g is not None:
+            g_traj[k].add_(g)
+    return g_traj, None
+
+
 class PiRolloutFramesFunction(torch.autograd.Function):
     """T fused steps, returned as the reference returns them: a tuple of [1,2,*S] frames (train_2drd.py:162-190
     appends every effective step to a Python list).  The frames are views of ONE trajectory buffer; the backward
@@ -1151,32 +1182,15 @@ class PiRolloutFramesFunction(torch.autograd.Function):
         traj[0].copy_(h0[0])
         rollout_fwd_(traj, P)
         ctx.save_for_backward(traj, P)
-        ctx.frames = tuple(int(k) for k in frames)
-        ctx.set_materialize_grads(False)
-        views = traj.unsqueeze(1).unbind(0)                 # all [1,2,*S] frame views in one call
-        outs = []
-        for k in ctx.frames:
-            f = views[k].as_subclass(Frame)                 # (see Frame: what makes the caller's torch.cat free)
-            f._pi_index = k
-            outs.append(f)
-        return tuple(outs) + (traj.view(traj.shape),)
+        return frame_outputs(ctx, traj.unsqueeze(1), frames)
 
     @staticmethod
     def backward(ctx, *grads):
         traj, P = ctx.saved_tensors
-        g_stacked, grads = grads[-1], grads[:-1]
-        if g_stacked is None and all(g is None for g in grads):
+        routed = frame_grads(ctx.frames, grads, traj.unsqueeze(1))
+        if routed is None:
             return None, None, None, None
-        if g_stacked is not None and all(g is None for g in grads):
-            g_traj, mask = g_stacked.contiguous(), None     # the loss was written on `outputs.stacked` alone: zero-copy
-        elif g_stacked is None:
-            g_traj, mask = _assemble_frame_grads(grads, ctx.frames, traj)
-        else:                                               # both: per-frame gradients on top of a copy of the stacked one
-            g_traj, mask = g_stacked.clone(), None
-            for k, g in zip(ctx.frames, grads):
-                if g is not None:
-                    g_traj[k].add_(g[0])
-        g_h0, pg = rollout_bwd(traj, g_traj, P, frame_mask=mask)
+        g_h0, pg = rollout_bwd(traj, routed[0].squeeze(1), P, frame_mask=routed[1])
         return g_h0[None], pg.to(P.dtype), None, None
 
 
@@ -1189,8 +1203,8 @@ class PiRolloutBatchedFramesFunction(torch.autograd.Function):
     """``PiRolloutFramesFunction`` for a batched initial state [B,2,*S]: one ``torch.ops.percnn.pi_rollout_batched`` call (P [np]:
     one block) or ``pi_rollout_ensemble`` call (P [B,np]: one block per sample), the frames are [B,2,*S] views of its
     [T+1,B,2,*S] buffer, the LAST output is that buffer as [(T+1)*B,2,*S] -- what ``torch.cat(tuple(outputs), dim=0)`` of the
-    batched frames is (train_2drd.py:394).  The backward runs ONE batched or ensemble rollout backward on the dense dL/dtraj;
-    the parameter gradient has P's shape."""
+    batched frames is (train_2drd.py:394).  The backward runs ONE batched or ensemble rollout backward on the dense dL/dtraj
+    (the operators take no frame mask: frames without a gradient are zero-filled); the parameter gradient has P's shape."""
 
     @staticmethod
     def forward(ctx, h0, P, steps, frames):
@@ -1199,33 +1213,20 @@ class PiRolloutBatchedFramesFunction(torch.autograd.Function):
         op = torch.ops.percnn.pi_rollout_ensemble if P.dim() == 2 else torch.ops.percnn.pi_rollout_batched
         traj = op(h0, P, steps, "")
         ctx.save_for_backward(traj, P)
-        ctx.frames = tuple(int(k) for k in frames)
-        ctx.set_materialize_grads(False)
-        views = traj.unbind(0)
-        outs = []
-        for k in ctx.frames:
-            f = views[k].as_subclass(Frame)
-            f._pi_index = k
-            outs.append(f)
-        return tuple(outs) + (traj.view((-1,) + tuple(traj.shape[2:])),)
+        return frame_outputs(ctx, traj, frames)
 
     @staticmethod
     def backward(ctx, *grads):
         traj, P = ctx.saved_tensors
-        g_stacked, grads = grads[-1], grads[:-1]
-        if g_stacked is None and all(g is None for g in grads):
+        routed = frame_grads(ctx.frames, grads, traj)
+        if routed is None:
             return None, None, None, None
-        if g_stacked is not None:
-            g_traj = g_stacked.reshape(traj.shape)
-            if any(g is not None for g in grads):
-                g_traj = g_traj.clone()
-        else:
-            g_traj = torch.zeros_like(traj)
-        for k, g in zip(ctx.frames, grads):
-            if g is not None:
-                g_traj[k].add_(g)
+        g_traj, mask = routed
+        for k, used in enumerate(mask or ()):
+            if not used:
+                g_traj[k].zero_()
         op = torch.ops.percnn.pi_rollout_ensemble_backward if P.dim() == 2 else torch.ops.percnn.pi_rollout_batched_backward
-        g_h0, pg = op(traj, P, g_traj.contiguous(), "")
+        g_h0, pg = op(traj, P, g_traj, "")
         return g_h0, pg, None, None
 
 

@@ -27,129 +27,164 @@ import torch.nn as nn
 
 from . import _lib
 from .discovery import LIBRARY_TERMS, _A, _B
-from .functional import _stream, _assemble_frame_grads, Frame
+from .functional import _stream, _mask_bytes, frame_outputs, frame_grads
 
 NCOEF = 140                              # PERCNN_PI_LIB_COEFS
 INTEGRATORS = ("euler", "rk4")
 
 
-def _entry(integrator: str, name: str):
-    """the C entry point ``name`` of the step ``integrator`` takes"""
+# ---- host path: one body per call; ``ens`` = the ensemble flavour (a sample axis B after the frame axis, one block per sample) --
+_WHO = {False: "LibraryCell", True: "LibraryEnsemble"}
+_WANT = {(False, False): "[1,2,H,W] (one trajectory; B samples go through LibraryEnsemble)", (False, True): "[T+1,2,H,W]",
+         (True, False): "[B,2,H,W] (2D, two species)", (True, True): "[T+1,B,2,H,W] (2D, two species)"}
+
+
+def _entry(integrator: str, name: str, ens: bool = False):
+    """the C entry point ``[ensemble_]<name>`` of the step ``integrator`` takes"""
     if integrator not in INTEGRATORS:
-        raise ValueError(f"LibraryCell: integrator must be one of {INTEGRATORS}, got {integrator!r}")
-    return getattr(_lib.lib(), f"percnn_pi_lib_{'rk4_' if integrator == 'rk4' else ''}{name}")
+        raise ValueError(f"{_WHO[ens]}: integrator must be one of {INTEGRATORS}, got {integrator!r}")
+    return getattr(_lib.lib(), f"percnn_pi_lib_{'rk4_' if integrator == 'rk4' else ''}{'ensemble_' if ens else ''}{name}")
 
 
-def _check_state(t: torch.Tensor, name: str, lead) -> None:
-    """[lead, 2, H, W] float64 on the device, contiguous, H and W >= 5 (``lead`` None: any leading extent)"""
+def _check_state(t: torch.Tensor, name: str, ens: bool, traj: bool = False) -> None:
+    """[1,2,H,W] / [B,2,H,W] (``traj``: [T+1,2,H,W] / [T+1,B,2,H,W]) float64 on the device, contiguous, H and W >= 5"""
+    who = _WHO[ens]
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"LibraryCell: {name} must be a tensor on the HIP device (there is no CPU path)")
+        raise RuntimeError(f"{who}: {name} must be a tensor on the HIP device (there is no CPU path)")
     if t.dtype != torch.float64:
-        raise TypeError(f"LibraryCell: {name} must be float64, got {t.dtype}")
-    if t.dim() != 4 or t.shape[1] != 2 or (lead is not None and t.shape[0] != lead):
-        want = "[1,2,H,W] (one trajectory; B samples go through LibraryEnsemble)" if lead == 1 else "[T+1,2,H,W]"
-        raise ValueError(f"LibraryCell: {name} must be {want}, got {tuple(t.shape)}")
-    if t.shape[2] < 5 or t.shape[3] < 5:
-        raise ValueError(f"LibraryCell: {name} needs H, W >= 5 (radius-2 periodic stencils), got H = {t.shape[2]}, W = {t.shape[3]}")
+        raise TypeError(f"{who}: {name} must be float64, got {t.dtype}")
+    if ens:
+        ok = t.dim() == (5 if traj else 4) and t.shape[-3] == 2 and t.shape[-4] >= 1
+    else:
+        ok = t.dim() == 4 and t.shape[1] == 2 and (traj or t.shape[0] == 1)
+    if not ok:
+        raise ValueError(f"{who}: {name} must be {_WANT[ens, traj]}, got {tuple(t.shape)}")
+    if t.shape[-2] < 5 or t.shape[-1] < 5:
+        raise ValueError(f"{who}: {name} needs H, W >= 5 (radius-2 periodic stencils), got H = {t.shape[-2]}, W = {t.shape[-1]}")
     if not t.is_contiguous():
-        raise ValueError(f"LibraryCell: {name} must be contiguous")
+        raise ValueError(f"{who}: {name} must be contiguous")
 
 
-def _check_coef(C: torch.Tensor) -> None:
+def _check_coef(C: torch.Tensor, B: Optional[int] = None) -> None:
+    """[2,10,7], or with ``B`` (the ensemble flavour) [B,2,10,7]: float64 on the device, contiguous"""
+    who = _WHO[B is not None]
     if not isinstance(C, torch.Tensor) or not C.is_cuda:
-        raise RuntimeError("LibraryCell: coef must be a tensor on the HIP device (there is no CPU path)")
-    if C.dtype != torch.float64 or C.numel() != NCOEF or not C.is_contiguous():
-        raise ValueError(f"LibraryCell: coef must be contiguous float64 [2,10,7], got {C.dtype} {tuple(C.shape)}")
+        raise RuntimeError(f"{who}: coef must be a tensor on the HIP device (there is no CPU path)")
+    ok = C.dtype == torch.float64 and C.is_contiguous() and C.numel() == (1 if B is None else B) * NCOEF
+    if not ok or (B is not None and (C.dim() < 2 or C.shape[0] != B)):
+        want = "[2,10,7]" if B is None else f"[B,2,10,7] with B = {B} (one block per sample)"
+        raise ValueError(f"{who}: coef must be contiguous float64 {want}, got {C.dtype} {tuple(C.shape)}")
+
+
+def _step_fwd(ens, h, C, dx, dt, out, integrator):
+    fn = _entry(integrator, "step_fwd_f64", ens)
+    _check_state(h, "h", ens)
+    B = (h.shape[0],) if ens else ()                        # (the single entry points take no B)
+    _check_coef(C, *B)
+    out = torch.empty_like(h) if out is None else out
+    with torch.cuda.device(h.device):
+        _lib.check(fn(h.data_ptr(), out.data_ptr(), C.data_ptr(), _lib.shape_arg(h.shape[2:]), *B, float(dx), float(dt), _stream()),
+                   f"lib_{'ensemble_' if ens else ''}step_fwd")
+    return out
+
+
+def _rollout_fwd_(ens, traj, C, dx, dt, integrator):
+    fn = _entry(integrator, "rollout_fwd_f64", ens)
+    _check_state(traj, "traj", ens, traj=True)
+    B = (traj.shape[1],) if ens else ()
+    _check_coef(C, *B)
+    with torch.cuda.device(traj.device):
+        _lib.check(fn(traj.data_ptr(), C.data_ptr(), _lib.shape_arg(traj.shape[-2:]), *B, traj.shape[0] - 1, float(dx), float(dt),
+                      _stream()), f"lib_{'ensemble_' if ens else ''}rollout_fwd")
+    return traj
+
+
+def _rollout_bwd(ens, traj, g_traj, C, dx, dt, frame_mask, integrator):
+    ws_bytes, fn = _entry(integrator, "rollout_bwd_workspace_bytes", ens), _entry(integrator, "rollout_bwd_f64", ens)
+    _check_state(traj, "traj", ens, traj=True)
+    _check_state(g_traj, "g_traj", ens, traj=True)
+    if g_traj.shape != traj.shape:
+        raise ValueError(f"{_WHO[ens]}: g_traj must have the trajectory's shape {tuple(traj.shape)}, got {tuple(g_traj.shape)}")
+    B = (traj.shape[1],) if ens else ()
+    _check_coef(C, *B)
+    T, shape = traj.shape[0] - 1, _lib.shape_arg(traj.shape[-2:])
+    ws = torch.empty(ws_bytes(shape, *B, T), dtype=torch.uint8, device=traj.device)
+    g_h0 = torch.empty_like(traj[0])
+    gC = torch.empty(B + (2, 10, 7), dtype=torch.float64, device=traj.device)
+    with torch.cuda.device(traj.device):
+        _lib.check(fn(traj.data_ptr(), g_traj.data_ptr(), _mask_bytes(frame_mask, T + 1), g_h0.data_ptr(), gC.data_ptr(),
+                      ws.data_ptr(), ws.numel(), C.data_ptr(), shape, *B, T, float(dx), float(dt), _stream()),
+                   f"lib_{'ensemble_' if ens else ''}rollout_bwd")
+        ws.record_stream(torch.cuda.current_stream())
+    return g_h0, gC
 
 
 def step_fwd(h: torch.Tensor, C: torch.Tensor, dx: float, dt: float, out: Optional[torch.Tensor] = None,
              integrator: str = "euler") -> torch.Tensor:
     """h: [1,2,H,W] -> the next state"""
-    fn = _entry(integrator, "step_fwd_f64")
-    _check_state(h, "h", 1)
-    _check_coef(C)
-    out = torch.empty_like(h) if out is None else out
-    with torch.cuda.device(h.device):
-        _lib.check(fn(h.data_ptr(), out.data_ptr(), C.data_ptr(), _lib.shape_arg(h.shape[2:]), float(dx), float(dt), _stream()),
-                   "lib_step_fwd")
-    return out
+    return _step_fwd(False, h, C, dx, dt, out, integrator)
 
 
 def rollout_fwd_(traj: torch.Tensor, C: torch.Tensor, dx: float, dt: float, integrator: str = "euler") -> torch.Tensor:
     """In place: traj[0] holds the initial state, frames 1..T are written.  traj: [T+1,2,H,W]."""
-    fn = _entry(integrator, "rollout_fwd_f64")
-    _check_state(traj, "traj", None)
-    _check_coef(C)
-    with torch.cuda.device(traj.device):
-        _lib.check(fn(traj.data_ptr(), C.data_ptr(), _lib.shape_arg(traj.shape[2:]), traj.shape[0] - 1, float(dx), float(dt),
-                      _stream()), "lib_rollout_fwd")
-    return traj
+    return _rollout_fwd_(False, traj, C, dx, dt, integrator)
 
 
 def rollout_bwd(traj: torch.Tensor, g_traj: torch.Tensor, C: torch.Tensor, dx: float, dt: float, frame_mask=None,
                 integrator: str = "euler"):
     """-> (dL/dh0 [2,H,W], dL/dC [2,10,7]: all 140 entries, whatever the support)"""
-    ws_bytes, fn = _entry(integrator, "rollout_bwd_workspace_bytes"), _entry(integrator, "rollout_bwd_f64")
-    _check_state(traj, "traj", None)
-    _check_state(g_traj, "g_traj", traj.shape[0])
-    if g_traj.shape != traj.shape:
-        raise ValueError(f"LibraryCell: g_traj must have the trajectory's shape {tuple(traj.shape)}, got {tuple(g_traj.shape)}")
-    _check_coef(C)
-    T, shape = traj.shape[0] - 1, traj.shape[2:]
-    ws = torch.empty(ws_bytes(_lib.shape_arg(shape), T), dtype=torch.uint8, device=traj.device)
-    mask = None
-    if frame_mask is not None:
-        assert len(frame_mask) == T + 1
-        mask = bytes(bytearray(1 if m else 0 for m in frame_mask))
-    g_h0 = torch.empty_like(traj[0])
-    gC = torch.empty((2, 10, 7), dtype=torch.float64, device=traj.device)
-    with torch.cuda.device(traj.device):
-        _lib.check(fn(traj.data_ptr(), g_traj.data_ptr(), mask, g_h0.data_ptr(), gC.data_ptr(), ws.data_ptr(), ws.numel(),
-                      C.data_ptr(), _lib.shape_arg(shape), T, float(dx), float(dt), _stream()), "lib_rollout_bwd")
-        ws.record_stream(torch.cuda.current_stream())
-    return g_h0, gC
+    return _rollout_bwd(False, traj, g_traj, C, dx, dt, frame_mask, integrator)
+
+
+def ensemble_step_fwd(h: torch.Tensor, C: torch.Tensor, dx: float, dt: float, out: Optional[torch.Tensor] = None,
+                      integrator: str = "euler") -> torch.Tensor:
+    """h: [B,2,H,W], C: [B,2,10,7] -> the next states, sample b with block b"""
+    return _step_fwd(True, h, C, dx, dt, out, integrator)
+
+
+def ensemble_rollout_fwd_(traj: torch.Tensor, C: torch.Tensor, dx: float, dt: float, integrator: str = "euler") -> torch.Tensor:
+    """In place: traj[0] holds the B initial states, frames 1..T are written.  traj: [T+1,B,2,H,W], C: [B,2,10,7]."""
+    return _rollout_fwd_(True, traj, C, dx, dt, integrator)
+
+
+def ensemble_rollout_bwd(traj: torch.Tensor, g_traj: torch.Tensor, C: torch.Tensor, dx: float, dt: float, frame_mask=None,
+                         integrator: str = "euler"):
+    """-> (dL/dh0 [B,2,H,W], dL/dC [B,2,10,7]: all 140 entries per member, whatever the supports)"""
+    return _rollout_bwd(True, traj, g_traj, C, dx, dt, frame_mask, integrator)
 
 
 class LibraryRolloutFramesFunction(torch.autograd.Function):
-    """T fused steps with the contract of ``stage1.Stage1RolloutFramesFunction``: the requested [1,2,H,W] frames are views of
-    ONE trajectory buffer and outputs of ONE autograd node; the trajectory itself rides along as the last output."""
+    """T fused steps with the contract of ``functional.PiRolloutFramesFunction`` / ``PiRolloutBatchedFramesFunction``: the
+    requested frames are views of ONE trajectory buffer and outputs of ONE autograd node; the buffer itself rides along as the
+    last output.  The rank of C chooses the flavour -- [2,10,7]: one trajectory, h0 and frames [1,2,H,W], last output
+    [T+1,2,H,W]; [B,2,10,7]: B members, h0 and frames [B,2,H,W], last output [(T+1)*B,2,H,W].  Frames without a gradient are
+    masked out of the backward sweep."""
 
     @staticmethod
     def forward(ctx, h0, C, dx, dt, steps, frames, integrator="euler"):
-        _check_state(h0, "h0", 1)
+        ens = C.dim() == 4
+        _check_state(h0, "h0", ens)
         C = C.contiguous()
-        traj = torch.empty((steps + 1,) + tuple(h0.shape[1:]), dtype=torch.float64, device=h0.device)
-        traj[0].copy_(h0[0])
-        rollout_fwd_(traj, C, dx, dt, integrator=integrator)
-        ctx.save_for_backward(traj, C)
+        buf = torch.empty((steps + 1,) + tuple(h0.shape), dtype=torch.float64, device=h0.device)    # [T+1,R,2,H,W], R = 1 or B
+        buf[0].copy_(h0)
+        _rollout_fwd_(ens, buf if ens else buf.squeeze(1), C, dx, dt, integrator)
+        ctx.save_for_backward(buf, C)
         ctx.dx, ctx.dt, ctx.integrator = dx, dt, integrator
-        ctx.frames = tuple(int(k) for k in frames)
-        ctx.set_materialize_grads(False)
-        views = traj.unsqueeze(1).unbind(0)
-        outs = []
-        for k in ctx.frames:                                # functional.Frame: the caller's torch.cat(tuple(output)) is a view
-            f = views[k].as_subclass(Frame)
-            f._pi_index = k
-            outs.append(f)
-        return tuple(outs) + (traj.view(traj.shape),)
+        return frame_outputs(ctx, buf, frames)
 
     @staticmethod
     def backward(ctx, *grads):
-        traj, C = ctx.saved_tensors
-        g_stacked, grads = grads[-1], grads[:-1]
-        if g_stacked is None and all(g is None for g in grads):
+        buf, C = ctx.saved_tensors
+        routed = frame_grads(ctx.frames, grads, buf)
+        if routed is None:
             return None, None, None, None, None, None, None
-        if g_stacked is not None and all(g is None for g in grads):
-            g_traj, mask = g_stacked.contiguous(), None
-        elif g_stacked is None:
-            g_traj, mask = _assemble_frame_grads(grads, ctx.frames, traj)
-        else:
-            g_traj, mask = g_stacked.clone(), None
-            for k, g in zip(ctx.frames, grads):
-                if g is not None:
-                    g_traj[k].add_(g[0])
-        g_h0, gC = rollout_bwd(traj, g_traj, C, ctx.dx, ctx.dt, frame_mask=mask, integrator=ctx.integrator)
-        return g_h0[None], gC.reshape(C.shape), None, None, None, None, None
+        ens = C.dim() == 4
+        traj, g_traj = (buf, routed[0]) if ens else (buf.squeeze(1), routed[0].squeeze(1))
+        g_h0, gC = _rollout_bwd(ens, traj, g_traj, C, ctx.dx, ctx.dt, routed[1], ctx.integrator)
+        return g_h0.view(buf.shape[1:]), gC.reshape(C.shape), None, None, None, None, None
+
+
+LibraryEnsembleRolloutFramesFunction = LibraryRolloutFramesFunction    # (one node: the rank of C chooses the entry points)
 
 
 def _term_index(term: str) -> int:
@@ -291,140 +326,6 @@ class LibraryCell(nn.Module):
         return prev_state.to(self.coef.device)
 
 
-# ---- ensembles: B equations per launch -----------------------------------------------------------------------------------------
-def _ens_entry(integrator: str, name: str):
-    """the C entry point ``ensemble_<name>`` of the step ``integrator`` takes"""
-    if integrator not in INTEGRATORS:
-        raise ValueError(f"LibraryEnsemble: integrator must be one of {INTEGRATORS}, got {integrator!r}")
-    return getattr(_lib.lib(), f"percnn_pi_lib_{'rk4_' if integrator == 'rk4' else ''}ensemble_{name}")
-
-
-def _check_ens_state(t: torch.Tensor, name: str, traj: bool = False) -> None:
-    """[B,2,H,W] (``traj``: [T+1,B,2,H,W]) float64 on the device, contiguous, H and W >= 5"""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"LibraryEnsemble: {name} must be a tensor on the HIP device (there is no CPU path)")
-    if t.dtype != torch.float64:
-        raise TypeError(f"LibraryEnsemble: {name} must be float64, got {t.dtype}")
-    if t.dim() != (5 if traj else 4) or t.shape[-3] != 2 or t.shape[-4] < 1:
-        raise ValueError(f"LibraryEnsemble: {name} must be {'[T+1,B,2,H,W]' if traj else '[B,2,H,W]'} (2D, two species), "
-                         f"got {tuple(t.shape)}")
-    if t.shape[-2] < 5 or t.shape[-1] < 5:
-        raise ValueError(f"LibraryEnsemble: {name} needs H, W >= 5 (radius-2 periodic stencils), got H = {t.shape[-2]}, "
-                         f"W = {t.shape[-1]}")
-    if not t.is_contiguous():
-        raise ValueError(f"LibraryEnsemble: {name} must be contiguous")
-
-
-def _check_ens_coef(C: torch.Tensor, B: int) -> None:
-    if not isinstance(C, torch.Tensor) or not C.is_cuda:
-        raise RuntimeError("LibraryEnsemble: coef must be a tensor on the HIP device (there is no CPU path)")
-    if C.dtype != torch.float64 or C.dim() < 2 or C.shape[0] != B or C.numel() != B * NCOEF or not C.is_contiguous():
-        raise ValueError(f"LibraryEnsemble: coef must be contiguous float64 [B,2,10,7] with B = {B} (one block per sample), got "
-                         f"{C.dtype} {tuple(C.shape)}")
-
-
-def ensemble_step_fwd(h: torch.Tensor, C: torch.Tensor, dx: float, dt: float, out: Optional[torch.Tensor] = None,
-                      integrator: str = "euler") -> torch.Tensor:
-    """h: [B,2,H,W], C: [B,2,10,7] -> the next states, sample b with block b"""
-    fn = _ens_entry(integrator, "step_fwd_f64")
-    _check_ens_state(h, "h")
-    _check_ens_coef(C, h.shape[0])
-    out = torch.empty_like(h) if out is None else out
-    with torch.cuda.device(h.device):
-        _lib.check(fn(h.data_ptr(), out.data_ptr(), C.data_ptr(), _lib.shape_arg(h.shape[2:]), h.shape[0], float(dx), float(dt),
-                      _stream()), "lib_ensemble_step_fwd")
-    return out
-
-
-def ensemble_rollout_fwd_(traj: torch.Tensor, C: torch.Tensor, dx: float, dt: float, integrator: str = "euler") -> torch.Tensor:
-    """In place: traj[0] holds the B initial states, frames 1..T are written.  traj: [T+1,B,2,H,W], C: [B,2,10,7]."""
-    fn = _ens_entry(integrator, "rollout_fwd_f64")
-    _check_ens_state(traj, "traj", traj=True)
-    _check_ens_coef(C, traj.shape[1])
-    with torch.cuda.device(traj.device):
-        _lib.check(fn(traj.data_ptr(), C.data_ptr(), _lib.shape_arg(traj.shape[3:]), traj.shape[1], traj.shape[0] - 1, float(dx),
-                      float(dt), _stream()), "lib_ensemble_rollout_fwd")
-    return traj
-
-
-def ensemble_rollout_bwd(traj: torch.Tensor, g_traj: torch.Tensor, C: torch.Tensor, dx: float, dt: float, frame_mask=None,
-                         integrator: str = "euler"):
-    """-> (dL/dh0 [B,2,H,W], dL/dC [B,2,10,7]: all 140 entries per member, whatever the supports)"""
-    ws_bytes, fn = _ens_entry(integrator, "rollout_bwd_workspace_bytes"), _ens_entry(integrator, "rollout_bwd_f64")
-    _check_ens_state(traj, "traj", traj=True)
-    _check_ens_state(g_traj, "g_traj", traj=True)
-    if g_traj.shape != traj.shape:
-        raise ValueError(f"LibraryEnsemble: g_traj must have the trajectory's shape {tuple(traj.shape)}, got {tuple(g_traj.shape)}")
-    T, B, shape = traj.shape[0] - 1, traj.shape[1], traj.shape[3:]
-    _check_ens_coef(C, B)
-    ws = torch.empty(ws_bytes(_lib.shape_arg(shape), B, T), dtype=torch.uint8, device=traj.device)
-    mask = None
-    if frame_mask is not None:
-        assert len(frame_mask) == T + 1
-        mask = bytes(bytearray(1 if m else 0 for m in frame_mask))
-    g_h0 = torch.empty_like(traj[0])
-    gC = torch.empty((B, 2, 10, 7), dtype=torch.float64, device=traj.device)
-    with torch.cuda.device(traj.device):
-        _lib.check(fn(traj.data_ptr(), g_traj.data_ptr(), mask, g_h0.data_ptr(), gC.data_ptr(), ws.data_ptr(), ws.numel(),
-                      C.data_ptr(), _lib.shape_arg(shape), B, T, float(dx), float(dt), _stream()), "lib_ensemble_rollout_bwd")
-        ws.record_stream(torch.cuda.current_stream())
-    return g_h0, gC
-
-
-class LibraryEnsembleRolloutFramesFunction(torch.autograd.Function):
-    """``LibraryRolloutFramesFunction`` for B members with the conventions of ``functional.PiRolloutBatchedFramesFunction``: the
-    requested frames are [B,2,H,W] views of ONE [T+1,B,2,H,W] buffer and outputs of ONE autograd node; the LAST output is that
-    buffer as [(T+1)*B,2,H,W], what ``torch.cat(tuple(outputs), dim=0)`` of the frames is.  Frames without a gradient are masked
-    out of the backward sweep."""
-
-    @staticmethod
-    def forward(ctx, h0, C, dx, dt, steps, frames, integrator="euler"):
-        _check_ens_state(h0, "h0")
-        C = C.contiguous()
-        _check_ens_coef(C, h0.shape[0])
-        traj = torch.empty((steps + 1,) + tuple(h0.shape), dtype=torch.float64, device=h0.device)
-        traj[0].copy_(h0)
-        ensemble_rollout_fwd_(traj, C, dx, dt, integrator=integrator)
-        ctx.save_for_backward(traj, C)
-        ctx.dx, ctx.dt, ctx.integrator = dx, dt, integrator
-        ctx.frames = tuple(int(k) for k in frames)
-        ctx.set_materialize_grads(False)
-        views = traj.unbind(0)
-        outs = []
-        for k in ctx.frames:
-            f = views[k].as_subclass(Frame)
-            f._pi_index = k
-            outs.append(f)
-        return tuple(outs) + (traj.view((-1,) + tuple(traj.shape[2:])),)
-
-    @staticmethod
-    def backward(ctx, *grads):
-        traj, C = ctx.saved_tensors
-        g_stacked, grads = grads[-1], grads[:-1]
-        if g_stacked is None and all(g is None for g in grads):
-            return None, None, None, None, None, None, None
-        mask = None
-        if g_stacked is not None:
-            g_traj = g_stacked.reshape(traj.shape)
-            if any(g is not None for g in grads):
-                g_traj = g_traj.clone()
-                for k, g in zip(ctx.frames, grads):
-                    if g is not None:
-                        g_traj[k].add_(g)
-        else:
-            g_traj, mask = torch.empty_like(traj), [False] * traj.shape[0]
-            for k, g in zip(ctx.frames, grads):
-                if g is None:
-                    continue
-                if mask[k]:
-                    g_traj[k].add_(g)
-                else:
-                    g_traj[k].copy_(g)
-                    mask[k] = True
-        g_h0, gC = ensemble_rollout_bwd(traj, g_traj.contiguous(), C, ctx.dx, ctx.dt, frame_mask=mask, integrator=ctx.integrator)
-        return g_h0, gC.reshape(C.shape), None, None, None, None, None
-
-
 class LibraryEnsemble(nn.Module):
     """B ``LibraryCell``s advanced side by side: sample b of a state [B,2,H,W] runs with member b's 140 coefficients in the
     launches of one trajectory (``csrc/pi_lib.h``: the sample index rides on ``blockIdx.z``) -- what batched ``discover()``
@@ -477,7 +378,7 @@ class LibraryEnsemble(nn.Module):
         return torch.stack([c.param_block() for c in self.cells])
 
     def _check_h0(self, h0, name: str = "h0") -> None:
-        _check_ens_state(h0, name)
+        _check_state(h0, name, True)
         if h0.shape[0] != len(self.cells):
             raise ValueError(f"LibraryEnsemble: {name} must be [B,2,H,W] with B = len(cells) = {len(self.cells)} (sample b runs "
                              f"with member b), got {tuple(h0.shape)}")

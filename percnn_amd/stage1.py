@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .functional import _require, _stream, check_star_stencil, _assemble_frame_grads, _observe, _scatter_observed, Frame
+from .functional import _require, _stream, check_star_stencil, _observe, _scatter_observed, frame_outputs, frame_grads
 
 NP = 16 + 6 * 16 * 52 + 32 + 2          # PERCNN_PI_S1_PARAMS
 _OFF_W, _OFF_W4, _OFF_B4 = 16, 16 + 4992, 16 + 4992 + 32
@@ -161,32 +161,15 @@ class Stage1RolloutFramesFunction(torch.autograd.Function):
         traj[0].copy_(h0[0])
         rollout_fwd_(traj, P)
         ctx.save_for_backward(traj, P)
-        ctx.frames = tuple(int(k) for k in frames)
-        ctx.set_materialize_grads(False)
-        views = traj.unsqueeze(1).unbind(0)                 # all [1,2,*S] frame views in one call
-        outs = []
-        for k in ctx.frames:                                # functional.Frame: the caller's torch.cat(tuple(output)) is a view
-            f = views[k].as_subclass(Frame)
-            f._pi_index = k
-            outs.append(f)
-        return tuple(outs) + (traj.view(traj.shape),)       # last output: the trajectory itself (bur1:607's torch.cat, no copy)
+        return frame_outputs(ctx, traj.unsqueeze(1), frames)    # last output: the trajectory itself (bur1:607's torch.cat, no copy)
 
     @staticmethod
     def backward(ctx, *grads):
         traj, P = ctx.saved_tensors
-        g_stacked, grads = grads[-1], grads[:-1]
-        if g_stacked is None and all(g is None for g in grads):
+        routed = frame_grads(ctx.frames, grads, traj.unsqueeze(1))
+        if routed is None:
             return None, None, None, None
-        if g_stacked is not None and all(g is None for g in grads):
-            g_traj, mask = g_stacked.contiguous(), None
-        elif g_stacked is None:
-            g_traj, mask = _assemble_frame_grads(grads, ctx.frames, traj)
-        else:
-            g_traj, mask = g_stacked.clone(), None
-            for k, g in zip(ctx.frames, grads):
-                if g is not None:
-                    g_traj[k].add_(g[0])
-        g_h0, pg = rollout_bwd(traj, g_traj, P, frame_mask=mask)
+        g_h0, pg = rollout_bwd(traj, routed[0].squeeze(1), P, frame_mask=routed[1])
         return g_h0[None], pg.to(torch.float32), None, None
 
 

@@ -264,27 +264,27 @@ def test_stage3_forward_rk4_vs_reference(name):
         assert np.abs(g[-1].numpy() - z["rk4_grad_meansq_h0"]).max() <= 1e-12 * max(1e-30, np.abs(z["rk4_grad_meansq_h0"]).max())
 
 
-def test_frame_gradient_assembly_zero_copy_and_masked():
-    """RCNN.forward hands back T+1 frames; their gradients come back as slices of one buffer when the caller cats
-    them (zero-copy), or individually / partly missing (copied, rest masked)."""
+def _frame_gradient_assembly(R):
+    """the cases of ``_assemble_frame_grads`` on a buffer [6,R,2,4,4]: frame k is rows k*R..(k+1)*R of the stacked gradient"""
     from percnn_amd import functional as Fp
-    traj = torch.zeros(6, 2, 4, 4)
-    big = torch.arange(2 * 6 * 2 * 4 * 4, dtype=torch.float32).reshape(12, 2, 4, 4)
-    dense = big[3:9]                                        # a gradient buffer that does not start at its storage's origin
-    grads = tuple(dense[k:k + 1] for k in range(6))         # what CatBackward produces
+    traj = torch.zeros(6, R, 2, 4, 4)
+    big = torch.arange(2 * 6 * R * 2 * 4 * 4, dtype=torch.float32).reshape(12 * R, 2, 4, 4)
+    rows = lambda g: g.reshape(-1, 2, 4, 4)                 # [n,R,2,4,4] -> the n*R rows torch.cat of the frames has
+    full = lambda v: torch.full((R, 2, 4, 4), v)
+    dense = big[3 * R:9 * R]                                # a gradient buffer that does not start at its storage's origin
+    grads = tuple(dense[k * R:(k + 1) * R] for k in range(6))   # what CatBackward produces
     g, mask = Fp._assemble_frame_grads(grads, tuple(range(6)), traj)
-    assert mask is None and g.data_ptr() == dense.data_ptr() and torch.equal(g, dense)
+    assert mask is None and g.data_ptr() == dense.data_ptr() and g.shape == traj.shape and torch.equal(rows(g), dense)
     # the last frame would run past the end of the storage -> no aliasing, falls back to copies
-    tail = tuple(big[7 + k:8 + k] for k in range(5)) + (torch.ones(1, 2, 4, 4),)
+    tail = tuple(big[(7 + k) * R:(8 + k) * R] for k in range(5)) + (torch.ones(R, 2, 4, 4),)
     g, mask = Fp._assemble_frame_grads(tail, tuple(range(6)), traj)
-    assert mask == [True] * 6 and torch.equal(g[:5], big[7:12]) and torch.equal(g[5], torch.ones(2, 4, 4))
+    assert mask == [True] * 6 and torch.equal(rows(g[:5]), big[7 * R:12 * R]) and torch.equal(g[5], torch.ones(R, 2, 4, 4))
     # sparse frames, one missing gradient, one frame listed twice (second_last_state): summed
     frames = (0, 2, 5, 4, 4)
-    gr = (torch.full((1, 2, 4, 4), 1.0), None, torch.full((1, 2, 4, 4), 3.0), torch.full((1, 2, 4, 4), 4.0),
-          torch.full((1, 2, 4, 4), 0.5))
+    gr = (full(1.0), None, full(3.0), full(4.0), full(0.5))
     g, mask = Fp._assemble_frame_grads(gr, frames, traj)
     assert mask == [True, False, False, False, True, True]
-    assert float(g[0].mean()) == 1.0 and float(g[5].mean()) == 3.0 and float(g[4].mean()) == 4.5
+    assert torch.equal(g[0], full(1.0)) and torch.equal(g[5], full(3.0)) and torch.equal(g[4], full(4.5))
     # what RCNN.forward really produces for step >= 2: the dense list FOLLOWED by second_last_state (frame T-1).
     # Extra frame unused (gradient None) -> still the zero-copy view; extra frame used -> one copy, summed, autograd's
     # buffer left untouched
@@ -292,9 +292,60 @@ def test_frame_gradient_assembly_zero_copy_and_masked():
     g, mask = Fp._assemble_frame_grads(grads + (None,), frames, traj)
     assert mask is None and g.data_ptr() == dense.data_ptr()
     before = dense.clone()
-    g, mask = Fp._assemble_frame_grads(grads + (torch.full((1, 2, 4, 4), 0.25),), frames, traj)
+    g, mask = Fp._assemble_frame_grads(grads + (full(0.25),), frames, traj)
     assert mask is None and g.data_ptr() != dense.data_ptr() and torch.equal(dense, before)
-    assert torch.equal(g[4], dense[4] + 0.25) and torch.equal(g[:4], dense[:4]) and torch.equal(g[5], dense[5])
+    assert torch.equal(g[4], grads[4] + 0.25) and torch.equal(rows(g[:4]), dense[:4 * R]) and torch.equal(g[5], grads[5])
+
+
+def test_frame_gradient_assembly_zero_copy_and_masked():
+    """RCNN.forward hands back T+1 frames; their gradients come back as slices of one buffer when the caller cats
+    them (zero-copy), or individually / partly missing (copied, rest masked)."""
+    _frame_gradient_assembly(1)
+
+
+def test_frame_gradient_assembly_rows_per_frame():
+    """the same for the [B,2,*S] frames of a batched or ensemble rollout: three rows per frame"""
+    _frame_gradient_assembly(3)
+
+
+@pytest.mark.parametrize("R", [1, 3])
+def test_frame_list_protocol_cat_reaches_backward_as_view(R):
+    """A toy CPU node on ``frame_outputs`` / ``frame_grads``: the reference's ``torch.cat(tuple(outputs))`` followed by a dense
+    loss hands the backward ONE view of CatBackward's buffer (no copy, no mask); the stacked output alone and both together
+    route the same gradient."""
+    from percnn_amd import functional as Fp
+    seen = []
+
+    class Toy(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, h0):
+            buf = torch.stack([h0 * (k + 1) for k in range(4)])             # [T+1,R,2,6,6]
+            return Fp.frame_outputs(ctx, buf, range(4))
+
+        @staticmethod
+        def backward(ctx, *grads):
+            g_traj, mask = Fp.frame_grads(ctx.frames, grads, torch.empty(4, R, 2, 6, 6))
+            seen.append((g_traj, mask, [g for g in grads[:-1] if g is not None], grads[-1]))
+            return sum(g_traj[k] * (k + 1) for k in range(4))
+
+    h0 = torch.arange(R * 72, dtype=torch.float32).reshape(R, 2, 6, 6).requires_grad_()
+    outs = Toy.apply(h0)
+    assert all(type(f) is Fp.Frame and f._pi_index == k and f.shape == (R, 2, 6, 6) for k, f in enumerate(outs[:-1]))
+    assert outs[-1].shape == (4 * R, 2, 6, 6) and all(f.data_ptr() == outs[-1][k * R].data_ptr() for k, f in enumerate(outs[:-1]))
+    torch.cat(outs[:-1], 0).square().sum().backward()
+    g_traj, mask, per_frame, g_stacked = seen[-1]
+    assert g_stacked is None
+    assert mask is None and g_traj.shape == (4, R, 2, 6, 6) and g_traj.is_contiguous()
+    assert len(per_frame) == 4 and g_traj.data_ptr() == per_frame[0].data_ptr()
+    assert per_frame[0].untyped_storage().nbytes() >= g_traj.numel() * 4     # (CatBackward's buffer, not a copy of frame 0)
+    want = h0.grad.clone()
+    assert torch.equal(want, sum(2.0 * (k + 1) ** 2 * h0.detach() for k in range(4)))
+    for loss in (lambda o: o[-1].square().sum(), lambda o: 0.5 * (o[-1].square().sum() + torch.cat(o[:-1], 0).square().sum())):
+        h0.grad = None
+        loss(Toy.apply(h0)).backward()
+        assert seen[-1][1] is None and torch.equal(h0.grad, want)
+    g_traj, _, per_frame, g_stacked = seen[-2]                              # stacked alone: that gradient itself, no copy
+    assert not per_frame and g_traj.data_ptr() == g_stacked.data_ptr()
 
 
 def test_dt_change_after_first_use_is_honoured():
