@@ -1,4 +1,4 @@
-"""ctypes binding of libpercnn_pi.so (the C-ABI declared in include/percnn_pi.h).
+"""ctypes binding of libpercnn_pi.so, derived at import from the prototypes of the C-ABI's headers (include/percnn_pi*.h).
 
 The product path has NO CPU fallback: if the HIP library is missing or a call fails, a
 RuntimeError is raised.  Build with ``python __graft_entry__.py`` or ``percnn_amd.build()``.
@@ -7,12 +7,12 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("PERCNN_PI_LIB", os.path.join(CSRC, "libpercnn_pi.so"))
-ABI_VERSION = 3
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC"]
 _INC = os.path.join("..", "..", "include")
@@ -50,45 +50,80 @@ def _torch_ext_commands():
     return obj, compile_cmd, link_cmd
 
 
-EXPORTS = [
-    "percnn_pi_abi_version", "percnn_pi_param_count", "percnn_pi_bwd_workspace_bytes",
-    "percnn_pi_rollout_bwd_workspace_bytes", "percnn_pi_set_option", "percnn_pi_persist_status", "percnn_pi_persist_fence", "percnn_pi_halo_ring_bytes",
-    "percnn_pi_peer_box_bytes", "percnn_pi_peer_box_alloc", "percnn_pi_peer_box_free", "percnn_pi_peer_box_export",
-    "percnn_pi_peer_box_open", "percnn_pi_peer_box_close", "percnn_pi_peer_box_status",
-    "percnn_pi_peer_exchange_f32", "percnn_pi_peer_exchange_f64",
-    "percnn_pi_pack_fwd_f32", "percnn_pi_pack_fwd_f64", "percnn_pi_pack_bwd_f32", "percnn_pi_pack_bwd_f64",
-    "percnn_pi_pack_fwd_guard_f32", "percnn_pi_pack_fwd_guard_f64", "percnn_pi_host_words_alloc", "percnn_pi_host_words_free",
-    "percnn_pi_debug_hog",
-    "percnn_pi_debug_blockmap", "percnn_pi_debug_plan", "percnn_pi_debug_batch_plan", "percnn_pi_residual_sqloss_workspace_bytes",
-    "percnn_pi_residual_sqloss_f32", "percnn_pi_residual_sqloss_f64", "percnn_pi_residual_sqloss_bwd_f32",
-    "percnn_pi_residual_sqloss_bwd_f64",
-] + [f"percnn_pi_{op}_{suf}" for suf in ("f32", "f64")
-     for op in ("step_fwd", "step_bwd", "rollout_fwd", "rollout_bwd", "slab_step_fwd", "slab_step_bwd", "slab_wgrad",
-                "slab_step_fwd_range", "slab_step_bwd_range", "slab_rollout_fwd", "slab_rollout_bwd", "residual_fwd",
-                "residual_bwd", "contract_fwd", "contract_bwd", "step_fwd_opt", "step_bwd_opt", "rollout_fwd_opt",
-                "rollout_bwd_opt", "rollout_bwd_sqerr", "traj_sqerr", "step_bwd_rows", "bwd_rows_finish", "rollout_bwd_top",
-                "batch_step_fwd", "batch_step_bwd", "batch_rollout_fwd", "batch_rollout_bwd", "ensemble_step_fwd",
-                "ensemble_step_bwd", "ensemble_rollout_fwd", "ensemble_rollout_bwd", "batch_traj_sqerr",
-                "batch_rollout_bwd_sqerr", "ensemble_rollout_bwd_sqerr", "batch_traj_obs_sqerr",
-                "batch_rollout_bwd_obs_sqerr", "ensemble_rollout_bwd_obs_sqerr", "batch_residual_sqloss",
-                "batch_residual_sqloss_bwd", "ensemble_residual_sqloss", "ensemble_residual_sqloss_bwd")] + [
-    "percnn_pi_batch_traj_sqerr_workspace_bytes", "percnn_pi_batch_residual_sqloss_workspace_bytes",
-    "percnn_pi_debug_residual_sqloss_accepts",
-    "percnn_pi_batch_bwd_workspace_bytes", "percnn_pi_batch_rollout_bwd_workspace_bytes",
-    "percnn_pi_ensemble_bwd_workspace_bytes", "percnn_pi_ensemble_rollout_bwd_workspace_bytes",
-    "percnn_pi_s1_param_count", "percnn_pi_s1_step_fwd_f32", "percnn_pi_s1_rollout_fwd_f32",
-    "percnn_pi_s1_rollout_bwd_workspace_bytes", "percnn_pi_s1_rollout_bwd_f32", "percnn_pi_s1_set_option",
-    "percnn_pi_conv3d_k5c8_f32", "percnn_pi_conv3d_k5c8_wgrad_workspace_bytes", "percnn_pi_conv3d_k5c8_wgrad_f32",
-    "percnn_pi_library_moments_workspace_bytes", "percnn_pi_library_moments_f32", "percnn_pi_library_moments_f64",
-    "percnn_pi_lib_step_fwd_f64", "percnn_pi_lib_rollout_fwd_f64", "percnn_pi_lib_rollout_bwd_workspace_bytes",
-    "percnn_pi_lib_rollout_bwd_f64",
-    "percnn_pi_lib_rk4_step_fwd_f64", "percnn_pi_lib_rk4_rollout_fwd_f64", "percnn_pi_lib_rk4_rollout_bwd_workspace_bytes",
-    "percnn_pi_lib_rk4_rollout_bwd_f64",
-    "percnn_pi_lib_ensemble_step_fwd_f64", "percnn_pi_lib_ensemble_rollout_fwd_f64",
-    "percnn_pi_lib_ensemble_rollout_bwd_workspace_bytes", "percnn_pi_lib_ensemble_rollout_bwd_f64",
-    "percnn_pi_lib_rk4_ensemble_step_fwd_f64", "percnn_pi_lib_rk4_ensemble_rollout_fwd_f64",
-    "percnn_pi_lib_rk4_ensemble_rollout_bwd_workspace_bytes", "percnn_pi_lib_rk4_ensemble_rollout_bwd_f64",
-]
+class ParamPtrs(ctypes.Structure):
+    """percnn_pi_param_ptrs of include/percnn_pi.h: device pointers of the reference's parameter tensors"""
+    _fields_ = [("c", ctypes.c_void_p * 2), ("w", ctypes.c_void_p), ("branch", ctypes.c_void_p * 16)]
+
+
+class PeerRing(ctypes.Structure):
+    """percnn_pi_peer_ring of include/percnn_pi.h: this rank's mailbox, the mapped mailboxes of its ring neighbours"""
+    _fields_ = [("my_box", ctypes.c_void_p), ("prev_box", ctypes.c_void_p), ("next_box", ctypes.c_void_p),
+                ("slot_bytes", ctypes.c_size_t), ("epoch", ctypes.c_uint64), ("timeout_ticks", ctypes.c_uint64)]
+
+
+class HaloRing(ctypes.Structure):
+    """percnn_pi_halo_ring of include/percnn_pi.h: communicator, neighbours and the four RCCL entry points as addresses,
+    or (``peer`` set) the peer-mailbox transport"""
+    _fields_ = [("comm", ctypes.c_void_p), ("prev", ctypes.c_int), ("next", ctypes.c_int),
+                ("dtype_f32", ctypes.c_int), ("dtype_f64", ctypes.c_int),
+                ("group_start", ctypes.c_void_p), ("group_end", ctypes.c_void_p),
+                ("send", ctypes.c_void_p), ("recv", ctypes.c_void_p), ("peer", ctypes.POINTER(PeerRing)),
+                ("stage", ctypes.c_void_p), ("stage_bytes", ctypes.c_size_t)]
+
+
+# ---- the binding follows from the prototypes: one ctypes class per C type of the headers, nothing typed per entry point ----
+HEADERS = ("percnn_pi.h", "percnn_pi_stage1.h", "percnn_pi_discovery.h", "percnn_pi_library_cell.h")
+
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "size_t": ctypes.c_size_t, "double": ctypes.c_double,
+            "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32}
+_POINTEES = {"float": ctypes.c_void_p, "double": ctypes.c_void_p, "void": ctypes.c_void_p,     # device / opaque memory
+             "percnn_pi_param_ptrs": ctypes.POINTER(ParamPtrs), "percnn_pi_peer_ring": ctypes.POINTER(PeerRing),
+             "percnn_pi_halo_ring": ctypes.POINTER(HaloRing)}
+_POINTEES.update({t: ctypes.POINTER(_SCALARS[t]) for t in ("int", "long", "int64_t", "uint64_t")})
+# key: a declaration without its name, words one blank apart, `*` attached; `const` is optional for every pointee above
+CTYPES = {**_SCALARS, "void**": ctypes.POINTER(ctypes.c_void_p),
+          "const char*": ctypes.c_char_p, "const unsigned char*": ctypes.c_char_p,             # strings; frame masks as bytes
+          **{t + "*": c for t, c in _POINTEES.items()}, **{"const " + t + "*": c for t, c in _POINTEES.items()}}
+
+
+def parse_prototypes(text: str, header: str = "<text>") -> dict:
+    """C header text -> {name: (restype, [argtypes])} of every ``<return type> percnn_pi_<name>(<args>);`` in it, by the
+    rows of CTYPES.  A type without a row is a RuntimeError that names the prototype: a new kind of argument gets a row
+    on purpose, never a default."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text.replace("\\\n", " "), flags=re.M)
+
+    def ctype(decl, name):
+        m = re.fullmatch(r"((?:const )?(?:unsigned )?\w+) ?(\**) ?\w*", " ".join(decl.split()))
+        key = m and m.group(1) + m.group(2)
+        if key not in CTYPES:
+            raise RuntimeError(f"percnn_amd: {header}: prototype of {name}: no ctypes class for {decl.strip()!r} "
+                               f"(add a row to percnn_amd._lib.CTYPES)")
+        return CTYPES[key]
+
+    out = {}
+    for ret, name, args in re.findall(r"([\w\s*]+?)\b(percnn_pi_\w+)\s*\(([^()]*)\)\s*;", text):
+        out[name] = (ctype(ret, name), [] if args.strip() == "void" else [ctype(a, name) for a in args.split(",")])
+    return out
+
+
+def _read_headers():
+    """(PROTOTYPES, ABI_VERSION) from the headers build() compiles against"""
+    inc = os.path.normpath(os.path.join(CSRC, _INC))
+    protos, texts = {}, {}
+    for h in HEADERS:
+        try:
+            with open(os.path.join(inc, h)) as f:
+                texts[h] = f.read()
+        except OSError as e:
+            raise RuntimeError(f"percnn_amd: the C ABI's header {h} was not found in {inc} ({e}); the Python binding is "
+                               f"derived from the headers {', '.join(HEADERS)} there") from None
+        protos.update(parse_prototypes(texts[h], h))
+    return protos, int(re.search(r"^#define\s+PERCNN_PI_ABI_VERSION\s+(\d+)", texts["percnn_pi.h"], flags=re.M).group(1))
+
+
+PROTOTYPES, ABI_VERSION = _read_headers()
+EXPORTS = list(PROTOTYPES)
 
 
 def build(force: bool = False, extra_flags=(), out: str | None = None) -> str:
@@ -170,189 +205,15 @@ def lib() -> ctypes.CDLL:
             f"percnn_amd: HIP library not found at {LIB_PATH}. There is no CPU fallback -- build it with "
             f"`python -c 'import percnn_amd; percnn_amd.build()'` (needs hipcc).")
     L = ctypes.CDLL(LIB_PATH)
-    for name in EXPORTS:
+    for name, (restype, argtypes) in PROTOTYPES.items():
         if not hasattr(L, name):
             raise RuntimeError(f"percnn_amd: {LIB_PATH} does not export {name}")
-    L.percnn_pi_abi_version.restype = ctypes.c_int
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
     if L.percnn_pi_abi_version() != ABI_VERSION:
         raise RuntimeError("percnn_amd: ABI version mismatch between python package and libpercnn_pi.so")
-    vp, i64p, ci, sz = ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_size_t
-    L.percnn_pi_param_count.restype = sz
-    L.percnn_pi_param_count.argtypes = [ci]
-    L.percnn_pi_bwd_workspace_bytes.restype = sz
-    L.percnn_pi_bwd_workspace_bytes.argtypes = [ci, ci, i64p, ci]
-    L.percnn_pi_rollout_bwd_workspace_bytes.restype = sz
-    L.percnn_pi_rollout_bwd_workspace_bytes.argtypes = [ci, ci, i64p, ci, ci]
-    L.percnn_pi_set_option.restype = ci
-    L.percnn_pi_set_option.argtypes = [ctypes.c_char_p, ctypes.c_long]
-    L.percnn_pi_persist_status.restype, L.percnn_pi_persist_status.argtypes = ci, [ctypes.POINTER(ctypes.c_long)]
-    L.percnn_pi_halo_ring_bytes.restype, L.percnn_pi_halo_ring_bytes.argtypes = sz, []
     if L.percnn_pi_halo_ring_bytes() != ctypes.sizeof(HaloRing):
         raise RuntimeError("percnn_amd: percnn_pi_halo_ring layout differs between the python binding and libpercnn_pi.so")
-    vpp = ctypes.POINTER(ctypes.c_void_p)
-    L.percnn_pi_peer_box_bytes.restype, L.percnn_pi_peer_box_bytes.argtypes = sz, [sz]
-    L.percnn_pi_peer_box_alloc.restype, L.percnn_pi_peer_box_alloc.argtypes = ci, [vpp, sz]
-    L.percnn_pi_peer_box_free.restype, L.percnn_pi_peer_box_free.argtypes = ci, [vp]
-    L.percnn_pi_peer_box_export.restype, L.percnn_pi_peer_box_export.argtypes = ci, [vp, vp]
-    L.percnn_pi_peer_box_open.restype, L.percnn_pi_peer_box_open.argtypes = ci, [vp, vpp]
-    L.percnn_pi_peer_box_close.restype, L.percnn_pi_peer_box_close.argtypes = ci, [vp]
-    L.percnn_pi_peer_box_status.restype = ci
-    L.percnn_pi_peer_box_status.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), vp]
-    L.percnn_pi_debug_blockmap.restype = ci
-    L.percnn_pi_debug_blockmap.argtypes = [ci, i64p, ci, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
-    L.percnn_pi_debug_plan.restype = ci
-    L.percnn_pi_debug_plan.argtypes = [ci, ci, i64p, ci, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
-    L.percnn_pi_debug_batch_plan.restype = ci
-    L.percnn_pi_debug_batch_plan.argtypes = [ci, ci, i64p, ci, ci, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
-    cd = ctypes.c_double
-    for suf in ("f32", "f64"):
-        f = getattr(L, f"percnn_pi_pack_fwd_{suf}")
-        f.restype, f.argtypes = ci, [ctypes.POINTER(ParamPtrs), ci, ci, cd, cd, ci, ci, vp, vp]
-        f = getattr(L, f"percnn_pi_pack_bwd_{suf}")
-        f.restype, f.argtypes = ci, [ctypes.POINTER(ParamPtrs), ctypes.POINTER(ParamPtrs), ci, ci, cd, cd, ci, ci, vp, vp]
-        f = getattr(L, f"percnn_pi_pack_fwd_guard_{suf}")
-        f.restype, f.argtypes = ci, [ctypes.POINTER(ParamPtrs), ci, ci, cd, cd, ci, ci, vp, cd, cd, vp, cd, vp]
-    L.percnn_pi_host_words_alloc.restype, L.percnn_pi_host_words_alloc.argtypes = ci, [ctypes.POINTER(ctypes.c_void_p), sz]
-    L.percnn_pi_host_words_free.restype, L.percnn_pi_host_words_free.argtypes = ci, [vp]
-    L.percnn_pi_debug_hog.restype, L.percnn_pi_debug_hog.argtypes = ci, [ci, ci, ci, vp]
-    for suf in ("f32", "f64"):
-        f = getattr(L, f"percnn_pi_peer_exchange_{suf}")
-        f.restype, f.argtypes = ci, [vp, ci, i64p, ci, ci, ctypes.POINTER(PeerRing), vp]
-    for suf in ("f32", "f64"):
-        f = getattr(L, f"percnn_pi_contract_fwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, ci, vp, vp]
-        f = getattr(L, f"percnn_pi_contract_bwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, ci, vp, vp, vp]
-        f = getattr(L, f"percnn_pi_step_fwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, vp, ci, ci, i64p, vp]
-        f = getattr(L, f"percnn_pi_step_bwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, vp, vp, vp, vp, sz, vp, ci, ci, i64p, vp]
-        f = getattr(L, f"percnn_pi_slab_step_fwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, vp, ci, ci, i64p, ci, ci, vp]
-        f = getattr(L, f"percnn_pi_slab_step_bwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, vp, vp, vp, vp, sz, vp, ci, ci, i64p, ci, ci, vp]
-        f = getattr(L, f"percnn_pi_slab_step_fwd_range_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, vp, ci, ci, i64p, ci, ci, ci, vp]
-        f = getattr(L, f"percnn_pi_slab_step_bwd_range_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, vp, vp, vp, vp, sz, vp, ci, ci, i64p, ci, ci, ci, ci, vp]
-        f = getattr(L, f"percnn_pi_slab_rollout_fwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, ci, ci, i64p, ci, ci, vp, ci, vp]
-        f = getattr(L, f"percnn_pi_slab_rollout_bwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, vp, vp, vp, sz, vp, ci, ci, i64p, ci, ci, vp, ci, vp]
-        f = getattr(L, f"percnn_pi_slab_wgrad_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, vp, vp, sz, vp, ci, ci, i64p, ci, ci, vp]
-        f = getattr(L, f"percnn_pi_residual_fwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, vp, ci, i64p, ci, vp]
-        f = getattr(L, f"percnn_pi_residual_bwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, vp, vp, ci, i64p, ci, vp]
-        f = getattr(L, f"percnn_pi_residual_sqloss_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, ci, i64p, ci, ci, vp, vp, sz, vp]
-        f = getattr(L, f"percnn_pi_residual_sqloss_bwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, vp, ci, i64p, ci, ci, ci, vp, vp, vp]
-        for kind in ("batch", "ensemble"):                  # the unbatched signatures with `batch` after `shape`
-            f = getattr(L, f"percnn_pi_{kind}_residual_sqloss_{suf}")
-            f.restype, f.argtypes = ci, [vp, vp, ci, i64p, ci, ci, ci, vp, vp, sz, vp]
-            f = getattr(L, f"percnn_pi_{kind}_residual_sqloss_bwd_{suf}")
-            f.restype, f.argtypes = ci, [vp, vp, vp, ci, i64p, ci, ci, ci, ci, vp, vp, vp]
-        f = getattr(L, f"percnn_pi_rollout_fwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, ci, ci, i64p, ci, vp]
-        f = getattr(L, f"percnn_pi_rollout_bwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, ctypes.c_char_p, vp, vp, vp, sz, vp, ci, ci, i64p, ci, vp]
-        cs = ctypes.c_char_p
-        f = getattr(L, f"percnn_pi_step_fwd_opt_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, vp, ci, ci, i64p, cs, vp]
-        f = getattr(L, f"percnn_pi_step_bwd_opt_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, vp, vp, vp, vp, sz, vp, ci, ci, i64p, cs, vp]
-        f = getattr(L, f"percnn_pi_rollout_fwd_opt_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, ci, ci, i64p, ci, cs, vp]
-        f = getattr(L, f"percnn_pi_rollout_bwd_opt_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, cs, vp, vp, vp, sz, vp, ci, ci, i64p, ci, cs, vp]
-        f = getattr(L, f"percnn_pi_rollout_bwd_sqerr_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, cs, cd, vp, vp, vp, vp, sz, vp, ci, ci, i64p, ci, cs, vp]
-        f = getattr(L, f"percnn_pi_traj_sqerr_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, cs, ci, ci, i64p, cd, vp, vp, sz, vp]
-        f = getattr(L, f"percnn_pi_batch_step_fwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, vp, ci, ci, i64p, ci, cs, vp]
-        f = getattr(L, f"percnn_pi_batch_step_bwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, vp, vp, vp, vp, sz, vp, ci, ci, i64p, ci, cs, vp]
-        f = getattr(L, f"percnn_pi_batch_rollout_fwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, ci, ci, i64p, ci, ci, cs, vp]
-        f = getattr(L, f"percnn_pi_batch_rollout_bwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, cs, vp, vp, vp, sz, vp, ci, ci, i64p, ci, ci, cs, vp]
-        f = getattr(L, f"percnn_pi_ensemble_step_fwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, vp, ci, ci, i64p, ci, cs, vp]
-        f = getattr(L, f"percnn_pi_ensemble_step_bwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, vp, vp, vp, vp, sz, vp, ci, ci, i64p, ci, cs, vp]
-        f = getattr(L, f"percnn_pi_ensemble_rollout_fwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, ci, ci, i64p, ci, ci, cs, vp]
-        f = getattr(L, f"percnn_pi_ensemble_rollout_bwd_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, cs, vp, vp, vp, sz, vp, ci, ci, i64p, ci, ci, cs, vp]
-        f = getattr(L, f"percnn_pi_batch_traj_sqerr_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, cs, ci, ci, i64p, ci, cd, vp, vp, sz, vp]
-        f = getattr(L, f"percnn_pi_batch_rollout_bwd_sqerr_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, cs, cd, vp, vp, vp, vp, sz, vp, ci, ci, i64p, ci, ci, cs, vp]
-        f = getattr(L, f"percnn_pi_ensemble_rollout_bwd_sqerr_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, cs, cd, vp, vp, vp, vp, sz, vp, ci, ci, i64p, ci, ci, cs, vp]
-        ip = ctypes.POINTER(ctypes.c_int)
-        f = getattr(L, f"percnn_pi_batch_traj_obs_sqerr_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, cs, ci, ci, i64p, ip, ci, cd, vp, vp, sz, vp]
-        f = getattr(L, f"percnn_pi_batch_rollout_bwd_obs_sqerr_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, cs, ip, cd, vp, vp, vp, vp, sz, vp, ci, ci, i64p, ci, ci, cs, vp]
-        f = getattr(L, f"percnn_pi_ensemble_rollout_bwd_obs_sqerr_{suf}")
-        f.restype, f.argtypes = ci, [vp, vp, cs, ip, cd, vp, vp, vp, vp, sz, vp, ci, ci, i64p, ci, ci, cs, vp]
-    L.percnn_pi_batch_traj_sqerr_workspace_bytes.restype = sz
-    L.percnn_pi_batch_traj_sqerr_workspace_bytes.argtypes = [ci]
-    L.percnn_pi_batch_bwd_workspace_bytes.restype = sz
-    L.percnn_pi_batch_bwd_workspace_bytes.argtypes = [ci, ci, i64p, ci, ci]
-    L.percnn_pi_batch_rollout_bwd_workspace_bytes.restype = sz
-    L.percnn_pi_batch_rollout_bwd_workspace_bytes.argtypes = [ci, ci, i64p, ci, ci, ci]
-    L.percnn_pi_ensemble_bwd_workspace_bytes.restype = sz
-    L.percnn_pi_ensemble_bwd_workspace_bytes.argtypes = [ci, ci, i64p, ci, ci]
-    L.percnn_pi_ensemble_rollout_bwd_workspace_bytes.restype = sz
-    L.percnn_pi_ensemble_rollout_bwd_workspace_bytes.argtypes = [ci, ci, i64p, ci, ci, ci]
-    L.percnn_pi_residual_sqloss_workspace_bytes.restype, L.percnn_pi_residual_sqloss_workspace_bytes.argtypes = sz, []
-    L.percnn_pi_batch_residual_sqloss_workspace_bytes.restype = sz
-    L.percnn_pi_batch_residual_sqloss_workspace_bytes.argtypes = [ci]
-    L.percnn_pi_debug_residual_sqloss_accepts.restype = ci
-    L.percnn_pi_debug_residual_sqloss_accepts.argtypes = [ci, i64p, ci, ci, ci, ci, ctypes.POINTER(ci)]
-    L.percnn_pi_s1_param_count.restype = sz
-    L.percnn_pi_s1_param_count.argtypes = []
-    L.percnn_pi_s1_step_fwd_f32.restype, L.percnn_pi_s1_step_fwd_f32.argtypes = ci, [vp, vp, vp, i64p, vp]
-    L.percnn_pi_s1_rollout_fwd_f32.restype, L.percnn_pi_s1_rollout_fwd_f32.argtypes = ci, [vp, vp, i64p, ci, vp]
-    L.percnn_pi_s1_rollout_bwd_workspace_bytes.restype = sz
-    L.percnn_pi_s1_rollout_bwd_workspace_bytes.argtypes = [i64p, ci]
-    L.percnn_pi_conv3d_k5c8_f32.restype, L.percnn_pi_conv3d_k5c8_f32.argtypes = ci, [vp, vp, vp, vp, i64p, vp]
-    L.percnn_pi_conv3d_k5c8_wgrad_workspace_bytes.restype, L.percnn_pi_conv3d_k5c8_wgrad_workspace_bytes.argtypes = sz, []
-    L.percnn_pi_conv3d_k5c8_wgrad_f32.restype = ci
-    L.percnn_pi_conv3d_k5c8_wgrad_f32.argtypes = [vp, vp, vp, vp, sz, i64p, vp]
-    L.percnn_pi_s1_set_option.restype, L.percnn_pi_s1_set_option.argtypes = ci, [ctypes.c_char_p, ctypes.c_long]
-    L.percnn_pi_s1_rollout_bwd_f32.restype = ci
-    L.percnn_pi_s1_rollout_bwd_f32.argtypes = [vp, vp, ctypes.c_char_p, vp, vp, vp, sz, vp, i64p, ci, vp]
-    L.percnn_pi_library_moments_workspace_bytes.restype = sz
-    L.percnn_pi_library_moments_workspace_bytes.argtypes = [i64p, ci, ci]
-    i64, u64 = ctypes.c_int64, ctypes.c_uint64
-    for suf in ("f32", "f64"):
-        f = getattr(L, f"percnn_pi_library_moments_{suf}")
-        f.restype = ci
-        f.argtypes = [vp, i64, i64, i64p, ci, ci, cd, cd, ci, ctypes.c_uint32, u64, u64, vp, vp, vp, vp, vp, sz, vp]
-    for pre in ("percnn_pi_lib_", "percnn_pi_lib_rk4_"):      # the Euler step and the Runge-Kutta step: the same signatures
-        f = getattr(L, pre + "step_fwd_f64")
-        f.restype, f.argtypes = ci, [vp, vp, vp, i64p, cd, cd, vp]
-        f = getattr(L, pre + "rollout_fwd_f64")
-        f.restype, f.argtypes = ci, [vp, vp, i64p, ci, cd, cd, vp]
-        f = getattr(L, pre + "rollout_bwd_workspace_bytes")
-        f.restype, f.argtypes = sz, [i64p, ci]
-        f = getattr(L, pre + "rollout_bwd_f64")
-        f.restype, f.argtypes = ci, [vp, vp, ctypes.c_char_p, vp, vp, vp, sz, vp, i64p, ci, cd, cd, vp]
-        # B members per launch: the same signatures with `B` after `shape`
-        f = getattr(L, pre + "ensemble_step_fwd_f64")
-        f.restype, f.argtypes = ci, [vp, vp, vp, i64p, ci, cd, cd, vp]
-        f = getattr(L, pre + "ensemble_rollout_fwd_f64")
-        f.restype, f.argtypes = ci, [vp, vp, i64p, ci, ci, cd, cd, vp]
-        f = getattr(L, pre + "ensemble_rollout_bwd_workspace_bytes")
-        f.restype, f.argtypes = sz, [i64p, ci, ci]
-        f = getattr(L, pre + "ensemble_rollout_bwd_f64")
-        f.restype, f.argtypes = ci, [vp, vp, ctypes.c_char_p, vp, vp, vp, sz, vp, i64p, ci, ci, cd, cd, vp]
     # process-wide tuning defaults from the environment ("key=value,..."; the keys of percnn_pi_set_option) -- what a launcher
     # uses to A/B an option in worker processes it does not construct itself
     spec = os.environ.get("PERCNN_PI_OPTIONS", "")
@@ -362,27 +223,6 @@ def lib() -> ctypes.CDLL:
             raise RuntimeError(f"percnn_amd: PERCNN_PI_OPTIONS: bad option {kv!r}")
     _lib = L
     return L
-
-
-class ParamPtrs(ctypes.Structure):
-    """percnn_pi_param_ptrs of include/percnn_pi.h: device pointers of the reference's parameter tensors"""
-    _fields_ = [("c", ctypes.c_void_p * 2), ("w", ctypes.c_void_p), ("branch", ctypes.c_void_p * 16)]
-
-
-class PeerRing(ctypes.Structure):
-    """percnn_pi_peer_ring of include/percnn_pi.h: this rank's mailbox, the mapped mailboxes of its ring neighbours"""
-    _fields_ = [("my_box", ctypes.c_void_p), ("prev_box", ctypes.c_void_p), ("next_box", ctypes.c_void_p),
-                ("slot_bytes", ctypes.c_size_t), ("epoch", ctypes.c_uint64), ("timeout_ticks", ctypes.c_uint64)]
-
-
-class HaloRing(ctypes.Structure):
-    """percnn_pi_halo_ring of include/percnn_pi.h: communicator, neighbours and the four RCCL entry points as addresses,
-    or (``peer`` set) the peer-mailbox transport"""
-    _fields_ = [("comm", ctypes.c_void_p), ("prev", ctypes.c_int), ("next", ctypes.c_int),
-                ("dtype_f32", ctypes.c_int), ("dtype_f64", ctypes.c_int),
-                ("group_start", ctypes.c_void_p), ("group_end", ctypes.c_void_p),
-                ("send", ctypes.c_void_p), ("recv", ctypes.c_void_p), ("peer", ctypes.POINTER(PeerRing)),
-                ("stage", ctypes.c_void_p), ("stage_bytes", ctypes.c_size_t)]
 
 
 def persist_fence(stream=None) -> None:
