@@ -251,12 +251,6 @@ pi_fwd3d_brick_kernel(const T* __restrict__ h, T* __restrict__ out, const T* __r
 #pragma clang loop unroll(disable)
         for (int s = 0; s < 2; ++s) {
             T rr[VEC];
-#if defined(PI_BRICK_SKELETON)      // access-pattern ceiling (tools/gpu_brick_skeleton.sh; WRONG results): loads, LDS traffic, stencil
-            if constexpr (true) {   // taps and stores of the step, without the reaction term
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) rr[i] = T(0);
-            } else
-#endif
             if constexpr (HC == POLY) {
                 const T* c = P + P_W + 10 * s;
 #pragma unroll
@@ -411,9 +405,6 @@ template <typename T> struct BrickMomAcc<T, true> {
     using type = BV2<T>;
     static __device__ __forceinline__ T total(BV2<T> a) { return a.x + a.y; }
 };
-#ifndef PI_BRICK_MOM_PAIR_MIN_RZ
-#define PI_BRICK_MOM_PAIR_MIN_RZ 2     // one-plane bricks hold 128 registers for four waves per SIMD: 20 more spill (24.5 vs 17.7 us at 128^3)
-#endif
 struct NoPut {};
 template <bool PUT> struct AdjPutArg { using type = NoPut; };
 template <> struct AdjPutArg<true> { using type = PeerPutFused; };
@@ -422,10 +413,7 @@ template <> struct AdjPutArg<true> { using type = PeerPutFused; };
 // rows` (block of sample blockIdx.y, partial row blockIdx.y * rows + blockIdx.x).  Workgroup (x, b) walks bricks x, x + gridDim.x,
 // ... of sample b; bases and placement as in the forward kernel's sample flavours; the loss forms read their sample's factor.
 template <typename T, int HC, int RZ, bool MOM, int LOSS = 0, int NT = BRICK_NT, bool PUT = false, typename... X>
-#ifndef PI_ADJ_RZ2_WAVES
-#define PI_ADJ_RZ2_WAVES 2
-#endif
-__global__ void __launch_bounds__(NT, (RZ == 1 && HC == POLY && LOSS != 2 && sizeof(T) == 4 && !PUT) ? 4 : (RZ == 2 && HC == POLY && LOSS == 0 && sizeof(T) == 4 && NT == 256 && !PUT ? PI_ADJ_RZ2_WAVES : 2))   // one-plane bricks of pre-contracted float32
+__global__ void __launch_bounds__(NT, (RZ == 1 && HC == POLY && LOSS != 2 && sizeof(T) == 4 && !PUT) ? 4 : 2)   // 4: one-plane bricks of pre-contracted float32
 pi_adj3d_brick_kernel(const T* __restrict__ h, const T* __restrict__ G, const T* __restrict__ inj, T* __restrict__ Gp,
                       double* __restrict__ partials, const T* __restrict__ P, BrickGeom g, int hc_rt,
                       typename AdjPutArg<PUT>::type put, X... x)
@@ -471,7 +459,9 @@ pi_adj3d_brick_kernel(const T* __restrict__ h, const T* __restrict__ G, const T*
     // lane's chunk -- operands that sit in adjacent registers as loaded, so the sums issue as v_pk_fma_f32 without the
     // v_mov_b32 shuffles hipcc's own packing of the scalar form paid (round 5: 314 of 1037 VALU instructions of the
     // two-plane kernel were moves; profiles/r05_brick_adjoint_packed_moments.txt)
-    constexpr bool PAIR = MOM && sizeof(T) == 4 && VEC == 4 && RZ >= PI_BRICK_MOM_PAIR_MIN_RZ;
+    // (one-plane bricks hold 128 registers for four waves per SIMD: 20 more spill -- 24.5 vs 17.7 us at 128^3)
+    constexpr int PAIR_MIN_RZ = 2;
+    constexpr bool PAIR = MOM && sizeof(T) == 4 && VEC == 4 && RZ >= PAIR_MIN_RZ;
     using MAcc = typename BrickMomAcc<T, PAIR>::type;
     MAcc macc[MOM ? 2 : 1][MOM ? 10 : 1];
     if constexpr (MOM) {
@@ -533,12 +523,6 @@ pi_adj3d_brick_kernel(const T* __restrict__ h, const T* __restrict__ G, const T*
             T du[VEC], dv[VEC];
 #pragma unroll
             for (int i = 0; i < VEC; ++i) du[i] = dv[i] = T(0);
-#if defined(PI_BRICK_SKELETON)      // access-pattern ceiling: no Jacobian, no moments, no coefficient sums (the operands are
-            if constexpr (true) {   // still loaded and consumed by one add each)
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) { du[i] = u.v[i]; dv[i] = v.v[i]; }
-            } else
-#endif
             if constexpr (HC == POLY) {
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {

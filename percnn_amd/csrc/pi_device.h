@@ -51,14 +51,10 @@ __device__ __forceinline__ void st(T* p, const Pack<T, N>& x) { *reinterpret_cas
 // The compiler only emits sc1 on <= 8-byte atomic stores (two 8-byte sc1 stores per lane were measured SLOWER than plain
 // stores: 512^2 forward 2.28 us), hence inline asm; the s_nop covers the gfx9 hazard "VMEM store of more than 64 bits
 // followed by a write of its data VGPRs", which the hazard recogniser cannot see through inline asm (without it: corrupted
-// frames -- caught by the parity tests).  PI_WT_STORES = 0 restores plain stores.
-#ifndef PI_WT_STORES
-#define PI_WT_STORES 1
-#endif
+// frames -- caught by the parity tests).
 template <typename T, int N>
 __device__ __forceinline__ void st_frame_wt(T* p, const Pack<T, N>& x)
 {
-#if PI_WT_STORES
     if constexpr (sizeof(T) * N == 16) {
         typedef unsigned v4u __attribute__((ext_vector_type(4)));
         const v4u v = __builtin_bit_cast(v4u, x);
@@ -66,9 +62,6 @@ __device__ __forceinline__ void st_frame_wt(T* p, const Pack<T, N>& x)
     } else {
         *reinterpret_cast<Pack<T, N>*>(p) = x;
     }
-#else
-    *reinterpret_cast<Pack<T, N>*>(p) = x;
-#endif
 }
 
 // Explicit fused multiply-add; the translation unit is built with -ffp-contract=off so every
@@ -217,11 +210,8 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nblocks)
 }
 
 // ---- wave-level sum (all 64 lanes) -----------------------------------------------------------
-#ifndef PI_USE_DPP
-#define PI_USE_DPP 1      // 0 = ds_bpermute butterflies: 6 dependent LDS-crossbar round trips per sum (measured: the
-#endif                    // two fp64 sums at the end of the tile adjoint kernel cost ~1 us that way)
-#if PI_USE_DPP
-// DPP row shifts + row broadcasts: 6 VALU adds, no LDS crossbar traffic. Total lands in lane 63.
+// DPP row shifts + row broadcasts: 6 VALU adds, no LDS crossbar traffic. Total lands in lane 63.  (ds_bpermute butterflies are 6
+// dependent LDS-crossbar round trips per sum: the two fp64 sums at the end of the tile adjoint kernel cost ~1 us that way.)
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ float dpp_mov(float v)
 {
@@ -247,15 +237,5 @@ __device__ __forceinline__ T wave_sum_to_last(T v)
     return v;
 }
 constexpr int REDUCE_LANE = 63;
-#else
-template <typename T>
-__device__ __forceinline__ T wave_sum_to_last(T v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, WAVE);
-    return v;
-}
-constexpr int REDUCE_LANE = 0;
-#endif
 
 }  // namespace pi

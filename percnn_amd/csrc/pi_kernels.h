@@ -290,12 +290,7 @@ __device__ __forceinline__ void star2_inplane(const char* __restrict__ pb, const
             const int jr = L.row + k;
             unsigned off = L.eb + (unsigned)(k * (int)Wb);
             if (wrap) off += jr < 0 ? span : (jr >= nrow ? 0u - span : 0u);
-#if defined(PI_EXPERIMENT) && PI_EXPERIMENT >= 2      // timing experiments only (wrong results): no row-neighbour loads
-            const Pack<T, VEC> nb = c;
-            (void)off;
-#else
             const Pack<T, VEC> nb = ldb<T, VEC>(pb, off);
-#endif
             const T w = P[TB + t];
 #pragma unroll
             for (int i = 0; i < VEC; ++i) lap[i] = fma_(w, nb.v[i], lap[i]);
@@ -350,9 +345,6 @@ struct PlaneWindow {
             jz -= jz >= g.n0 ? nw : 0;
             if (RZ > 1) jz -= jz >= g.n0 ? nw : 0;          // partial last group of a grid with fewer than RZ + 2 planes
             jz = min(jz, hi);
-#if defined(PI_EXPERIMENT) && PI_EXPERIMENT >= 1      // timing experiments only (wrong results): no plane-neighbour loads
-            if (j < 2 || j >= RZ + 2) { w[j] = Pack<T, VEC>{}; continue; }
-#endif
             w[j] = ldb<T, VEC>(sgpr_ptr(reinterpret_cast<const char*>(fs + (long)jz * g.s0)), L.eb);
         }
     }

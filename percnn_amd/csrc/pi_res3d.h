@@ -33,6 +33,9 @@
 // Per step:  interior strips (768 of 2048: no halo needed) | halo lands | the other strips | write back + frame store |
 // publish + request -- the hand-over's round trip sits under the interior strips of the NEXT step.
 // Arithmetic and its order are pi::star's / pi_fwd3d_brick_kernel's: every frame is bit-identical to the brick kernels'.
+//
+// This header holds what the library launches -- the resident REVERSE SWEEP (launch_adj_res3d) and the hand-over machinery.  The
+// resident forward kernel described above is not dispatched by the library; it lives with its harness in tools/res3d/res3d_fwd.h.
 #pragma once
 #include "pi_device.h"
 
@@ -126,70 +129,9 @@ __device__ __forceinline__ unsigned lds_of(const Task& t) { return (unsigned)((t
 __device__ __forceinline__ v4f lds4(const unsigned char* p) { return *reinterpret_cast<const v4f*>(p); }
 __device__ __forceinline__ v2f lds2(const unsigned char* p) { return *reinterpret_cast<const v2f*>(p); }
 
-// one strip (4 points along x, both species) of one forward step, operands from the LDS window; pi::star's order: centre,
-// axis 0 (-2, -1, +1, +2), axis 1, axis 2; coef * lap + react and h + res * dt keep their two roundings (train_3drd.py:123-139)
-// `fr` (nullable, wave-uniform): frame of the state being READ -- the strip's own values are stored there on the way.  The frame
-// of step t thus leaves during the strips of step t + 1, two stores at a time between arithmetic, instead of as one burst of 64 KB
-// per CU that the ring request would queue behind (a CU drains ~12 B per clock to memory: 2.2 us of a step).
+// a strip in global memory: wave-uniform frame base + the lane's 32-bit byte offset
 typedef __attribute__((address_space(1))) v4f gv4f;
 typedef __attribute__((address_space(1))) char gchar;
-__device__ __forceinline__ void fwd_strip(const unsigned char* smem, unsigned lo, const float* __restrict__ P, v4f& ou, v4f& ov,
-                                          float* fr, long ss, unsigned go)
-{
-    v4f c[2], lap[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        const unsigned char* b = smem + s * SP + lo;
-        c[s] = lds4(b);
-#ifndef R3D_NO_FRAME
-        if (fr) *(gv4f*)((gchar*)(fr + s * ss) + go) = c[s];
-#endif
-        v4f l;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) l[i] = P[P_C0] * c[s][i];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int k = t < 2 ? t - 2 : t - 1;
-            const v4f nb = lds4(b + k * ZS);
-            const float w = P[P_TAPS + t];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) l[i] = fma_(w, nb[i], l[i]);
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int k = t < 2 ? t - 2 : t - 1;
-            const v4f nb = lds4(b + k * YS);
-            const float w = P[P_TAPS + 4 + t];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) l[i] = fma_(w, nb[i], l[i]);
-        }
-        const v2f xl = lds2(b - 8), xr = lds2(b + 16);
-        const float win[8] = {xl[0], xl[1], c[s][0], c[s][1], c[s][2], c[s][3], xr[0], xr[1]};
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int k = t < 2 ? t - 2 : t - 1;
-            const float w = P[P_TAPS + 8 + t];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) l[i] = fma_(w, win[2 + i + k], l[i]);
-        }
-        lap[s] = l;
-    }
-    const float dt = P[P_DT];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        const float* cf = P + P_W + 10 * s;
-        const float coef = P[P_COEF + s];
-        v4f o;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float rr = poly_r(cf, c[0][i], c[1][i]);
-            const float res = coef * lap[s][i] + rr;
-            const float inc = res * dt;
-            o[i] = c[s][i] + inc;
-        }
-        if (s == 0) ou = o; else ov = o;
-    }
-}
 
 // the face granules of a computed strip into the staging area (payload only, outbox order): two x-adjacent points per granule
 __device__ __forceinline__ void stage_strip(unsigned char* smem, const Task& t, const v4f& u, const v4f& v)
@@ -384,147 +326,6 @@ __device__ __forceinline__ unsigned locate_block(const Args& a, int b, int& bz, 
     return local;
 }
 
-// forward rollout: frames[0] is the initial state (read), frames[1 .. nsteps] are written.
-// Per step:  S: the strips that read the halo, their faces staged | publish | I: the interior strips, the ring requested after the
-// first of them | write-back | ring lands, halo unpacked -- publish to need is the whole of I + write-back (~2.5 us).
-template <int NT>
-__global__ void __launch_bounds__(NT, 1)
-pi_fwd3d_resident_kernel(float* __restrict__ frames, const float* __restrict__ P, Args a, unsigned long long* stamps)
-{
-    using S = Shape<NT>;
-    constexpr int SLOTS = S::SLOTS, NW = S::NW, BOX_BYTES = S::BOX_BYTES;
-    constexpr int WS = NS / WAVE;                                       // wave-slots of phase S
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    unsigned char* smem = smem_raw + 8;                                 // the window (see ROWB)
-    int* wg_abort = reinterpret_cast<int*>(smem + STG0 + NGRAN * 16);
-    const int tid = (int)threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
-    const int nblk = a.gz * a.gy * a.gx;
-    const int b = (int)blockIdx.x;
-    int bx, by, bz;
-    const unsigned local = locate_block(a, b, bz, by, bx);
-    const unsigned skipf = ((a.skip & 1) ? local : 0u) | ((a.skip & 2) ? (~local & 63u) : 0u);
-    const int me = (bz * a.gy + by) * a.gx + bx;                        // outbox slot = block number (not workgroup number)
-    if (tid == 0) {
-        *wg_abort = 0;
-        const unsigned n = __hip_atomic_fetch_add(a.sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
-        if (n == (unsigned)nblk && a.host) __hip_atomic_store(a.host, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    const int half_bytes = nblk * BOX_BYTES;
-    const __amdgpu_buffer_rsrc_t box = __builtin_amdgcn_make_buffer_rsrc(a.outbox, 0, 2 * half_bytes, 0x00020000);
-
-    // ---- fixed geometry of this lane -------------------------------------------------------------------------------------
-    unsigned lo[SLOTS], go[SLOTS], tk[SLOTS];
-#pragma unroll
-    for (int s = 0; s < SLOTS; ++s) {
-        const Task t = task_of<NT>(s, tid);
-        lo[s] = lds_of(t);
-        tk[s] = (unsigned)t.z | (unsigned)t.y << 8 | (unsigned)t.xs << 16;
-        go[s] = (unsigned)((((bz * BZ + t.z) * a.n1 + by * BY + t.y) * a.n2 + bx * BX + 4 * t.xs) * 4);
-    }
-    Ring<NT> R;
-    ring_setup<NT>(R, a, bz, by, bx, local);
-
-    // ---- the window of frame 0: own block and halo straight from memory ---------------------------------------------------
-    for (int i = tid; i < 2 * (BZ + 4) * (BY + 4) * (BX + 4); i += NT) {
-        const int x = i % (BX + 4), y = (i / (BX + 4)) % (BY + 4), z = (i / ((BX + 4) * (BY + 4))) % (BZ + 4), s = i / ((BX + 4) * (BY + 4) * (BZ + 4));
-        const int g0 = (bz * BZ + z - 2 + a.n0) % a.n0, g1 = (by * BY + y - 2 + a.n1) % a.n1, g2 = (bx * BX + x - 2 + a.n2) % a.n2;
-        const float v = frames[s * a.ss + ((long)g0 * a.n1 + g1) * a.n2 + g2];
-        *reinterpret_cast<float*>(smem + s * SP + z * ZS + y * YS + OWN0 - 8 + 4 * x) = v;
-    }
-    __syncthreads();
-
-    Landing<NT> L;
-    bool failed = false;
-    for (int t = 0; t < a.nsteps; ++t) {
-        const unsigned ep = (unsigned)t + 1u;                           // the state this step produces
-        const bool more = t + 1 < a.nsteps, ring = more && !(a.skip & 4);
-        float* fr = t > 0 ? frames + (long)t * a.frame_stride : nullptr;      // frame 0 is the caller's
-        v4f ou[SLOTS], ov[SLOTS];
-        R3D_STAMP(0);
-        // ---- phase S: the strips that read the halo; what the neighbours wait for goes to the staging area ----
-#pragma unroll
-        for (int s = 0; s < SLOTS; ++s)
-            if (s * NW + wave < WS) {                                   // wave-uniform
-                fwd_strip(smem, lo[s], P, ou[s], ov[s], fr, a.ss, go[s]);
-                const Task tt = {(int)(tk[s] & 255u), (int)(tk[s] >> 8 & 255u), (int)(tk[s] >> 16)};
-                stage_strip(smem, tt, ou[s], ov[s]);
-            }
-        R3D_STAMP(1);
-        lds_barrier();                                                  // faces staged; nobody reads the halo of state t any more
-        R3D_STAMP(2);
-        if (ring) {
-            const __amdgpu_buffer_rsrc_t mine = __builtin_amdgcn_make_buffer_rsrc(
-                static_cast<char*>(a.outbox) + ((size_t)(ep & 1u) * (size_t)half_bytes + (size_t)me * BOX_BYTES), 0, BOX_BYTES, 0x00020000);
-            publish<NT>(smem, R, mine, ep, skipf);
-        }
-        R3D_STAMP(3);
-        // ---- phase I: interior strips; the ring of state t + 1 is requested after the first of them ----
-        bool asked = !ring;
-#pragma unroll
-        for (int s = 0; s < SLOTS; ++s)
-            if (s * NW + wave >= WS) {
-                fwd_strip(smem, lo[s], P, ou[s], ov[s], fr, a.ss, go[s]);
-                if (!asked) {
-                    for (int i = 0; i < a.pause; ++i) __builtin_amdgcn_s_sleep(1);
-                    request<NT>(L, R, box, (int)(ep & 1u) * half_bytes, skipf);
-                    asked = true;
-                }
-            }
-        R3D_STAMP(4);
-        lds_barrier();                                                  // every read of state t is done
-        R3D_STAMP(5);
-        // ---- state t + 1 into the window ----
-#pragma unroll
-        for (int s = 0; s < SLOTS; ++s) {
-            *reinterpret_cast<v4f*>(smem + lo[s]) = ou[s];
-            *reinterpret_cast<v4f*>(smem + SP + lo[s]) = ov[s];
-        }
-        if (!more) {                                                    // the last frame has no next step to carry it
-#ifndef R3D_NO_FRAME
-            float* out = frames + (long)(t + 1) * a.frame_stride;
-#pragma unroll
-            for (int s = 0; s < SLOTS; ++s) {
-                *(gv4f*)((gchar*)out + go[s]) = ou[s];
-                *(gv4f*)((gchar*)(out + a.ss) + go[s]) = ov[s];
-            }
-#endif
-            break;
-        }
-        R3D_STAMP(6);
-        // ---- the halo of state t + 1 lands ----
-        if (ring) {
-            const int rd = (int)(ep & 1u) * half_bytes;
-            const unsigned long long t0 = ticks();
-            const unsigned long long bound = t == 0 ? a.first_timeout_ticks : a.timeout_ticks;
-            while (!landed<NT>(L, R, box, rd, ep, skipf)) {
-                if (ticks() - t0 > bound || __hip_atomic_load(a.sync + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { failed = true; break; }
-                __builtin_amdgcn_s_sleep(1);
-            }
-            if (failed) {
-                if (tid % WAVE == 0) *wg_abort = 1;
-            } else {
-                unpack<NT>(smem, L, R, skipf);
-            }
-        }
-        R3D_STAMP(7);
-        lds_barrier();
-        if (*wg_abort) {
-            // ABORT: the host learns it from its status slot and runs the launch-per-step kernels instead; frames already
-            // written are the correct ones, nothing of the ones not yet written is
-            if (tid == 0) {
-                __hip_atomic_fetch_add(a.sync + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (__hip_atomic_exchange(a.sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u && a.host) {
-                    __hip_atomic_store(a.host + 1, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    __hip_atomic_store(a.host + 2, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    __hip_atomic_store(a.host + 3, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
-            }
-            return;
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // REVERSE SWEEP, resident: the adjoint state G lives in the LDS window for the whole sweep; a step reads only its pointwise
 // operands from memory (the state h_{t-1} and, where that frame carries a gradient, dL/dtraj[t-1]: 16 + 16 instead of the brick
@@ -542,7 +343,6 @@ struct AdjArgs {
     unsigned frames[128];          // bit f: frame f carries a gradient (f < 4096)
 };
 
-typedef float av2 __attribute__((ext_vector_type(2)));
 struct AdjOps { v4f u, v; };
 
 __device__ __forceinline__ void adj_load(AdjOps& o, const float* hfr, long ss, unsigned go)
@@ -553,7 +353,7 @@ __device__ __forceinline__ void adj_load(AdjOps& o, const float* hfr, long ss, u
 
 // one strip of one adjoint step: Gp = G + coef * (dt * LapT(G)) + dt * J_react(h)^T G (+ inj); pi_adj3d_brick_kernel's order
 // `jfr` (nullable, wave-uniform): the frame of dL/dtraj this step injects; its strip is requested at the top and used at the bottom
-__device__ __forceinline__ void adj_strip_whole(const unsigned char* smem, unsigned lo, const float* __restrict__ P, const AdjOps& o,
+__device__ __forceinline__ void adj_strip(const unsigned char* smem, unsigned lo, const float* __restrict__ P, const AdjOps& o,
                                           const float* jfr, long ss, unsigned go, v4f& ou, v4f& ov, float (&mom)[2][10], double (&lane_c)[2])
 {
     v4f ju, jv;
@@ -645,159 +445,6 @@ __device__ __forceinline__ void adj_strip_whole(const unsigned char* smem, unsig
     }
 }
 
-// ---- the strip as TWO HALF-STRIPS on explicit pairs (round 6, late) ----
-// The four-point strip above (kept below as adj_strip_whole, R3D_ADJ_HALVES = 0) is scalar source that hipcc's SLP vectoriser packs
-// by itself: 418 vector instructions per strip where ~200 packed ones would do (118 v_mov building operand pairs), 256 registers and
-// 128 bytes of scratch.  Written as two halves of two x-adjacent points each on 2-vectors -- every LDS read is an 8-byte pair that
-// IS the operand of a v_pk_fma_f32 -- the same IEEE operations in the same order per point (adjoint state bit-identical) need no
-// pair building, and a half's temporaries are half a strip's.  R3D_MOM_PAIRS: the 20 moment sums as pairs (40 registers, one
-// packed FMA per moment and half) or as scalars (20 registers, two FMAs).
-// MEASURED AND NOT ADOPTED (tools/res3d, 128^3, dense injection, us per step): whole strips 16.3 | halves 21.9 (pairs) / 22.3
-// (scalar sums) | halves without the scheduling barrier between them 20.0 | whole strips with the parameter block re-read per strip
-// (R3D_P_RELOAD) 24.1.  All bit-identical.  The halves do drop ~50 v_mov per strip (264 v_mov_b32 against 590 + 100 v_pk_mov in the
-// kernel) but the allocator answers with MORE spills (216 bytes of scratch against 128, 136 scalar registers spilled to lanes
-// against 122): the kernel's wall is the 32 held outputs + 20 sums + operand ring next to ~50 live constants, not the strip's shape.
-#ifndef R3D_ADJ_HALVES
-#define R3D_ADJ_HALVES 0
-#endif
-#ifndef R3D_MOM_PAIRS
-#define R3D_MOM_PAIRS 1
-#endif
-#ifndef R3D_HALF_BARRIER
-#define R3D_HALF_BARRIER 1
-#endif
-#if R3D_ADJ_HALVES && R3D_MOM_PAIRS
-typedef v2f MomSum;
-__device__ __forceinline__ float mom_total(v2f a) { return a.x + a.y; }
-__device__ __forceinline__ v2f mom_zero() { return v2f{0.f, 0.f}; }
-#else
-typedef float MomSum;
-__device__ __forceinline__ float mom_total(float a) { return a; }
-__device__ __forceinline__ float mom_zero() { return 0.f; }
-#endif
-__device__ __forceinline__ v2f bc2(float x) { return v2f{x, x}; }
-__device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ void mom_add(v2f& acc, v2f gr, v2f phi) { acc = fma2(gr, phi, acc); }
-__device__ __forceinline__ void mom_add(float& acc, v2f gr, v2f phi) { acc = fma_(gr.x, phi.x, acc); acc = fma_(gr.y, phi.y, acc); }
-__device__ __forceinline__ void mom_add1(v2f& acc, v2f gr) { acc += gr; }
-__device__ __forceinline__ void mom_add1(float& acc, v2f gr) { acc += gr.x; acc += gr.y; }
-// pi::poly_dr on pairs (same operations in the same order)
-__device__ __forceinline__ void poly_dr2(const float* __restrict__ c, v2f u, v2f v, v2f& ru, v2f& rv)
-{
-    const v2f A1 = fma2(v, fma2(v, bc2(c[8]), bc2(c[4])), bc2(c[1]));
-    const v2f A2x2 = fma2(v, bc2(2.f * c[7]), bc2(2.f * c[3]));
-    ru = fma2(u, fma2(u, bc2(3.f * c[6]), A2x2), A1);
-    const v2f B0 = fma2(v, fma2(v, bc2(3.f * c[9]), bc2(2.f * c[5])), bc2(c[2]));
-    const v2f B1 = fma2(v, bc2(2.f * c[8]), bc2(c[4]));
-    rv = fma2(u, fma2(u, bc2(c[7]), B1), B0);
-}
-// the two points at window byte offset `lo` (8-byte aligned); hu / hv: their state operands
-template <typename MOM>
-__device__ __forceinline__ void adj_half(const unsigned char* smem, unsigned lo, const float* __restrict__ P, v2f hu, v2f hv,
-                                         v2f& ou, v2f& ov, MOM (&mom)[2][10], double (&lane_c)[2])
-{
-    v2f gc[2], dl[2];
-    const v2f dt = bc2(P[P_DT]);
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        const unsigned char* b = smem + s * SP + lo;
-        const v2f W[3] = {lds2(b - 8), lds2(b), lds2(b + 8)};
-        gc[s] = W[1];
-        v2f l = bc2(P[P_C0]) * W[1];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int k = -(t < 2 ? t - 2 : t - 1);                      // the transposed stencil: taps at mirrored offsets
-            l = fma2(bc2(P[P_TAPS + t]), lds2(b + k * ZS), l);
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int k = -(t < 2 ? t - 2 : t - 1);
-            l = fma2(bc2(P[P_TAPS + 4 + t]), lds2(b + k * YS), l);
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int k = -(t < 2 ? t - 2 : t - 1);
-            const int idx = 2 + k;                                       // element of the six-point row window W
-            const v2f nb = (idx & 1) ? v2f{W[idx / 2].y, W[idx / 2 + 1].x} : W[idx / 2];
-            l = fma2(bc2(P[P_TAPS + 8 + t]), nb, l);
-        }
-        dl[s] = l * dt;
-    }
-    v2f du = {0.f, 0.f}, dv = {0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        const float* c = P + P_W + 10 * s;
-        const v2f gr = gc[s] * dt;
-        const v2f ch = dl[s] * (s == 0 ? hu : hv);
-        double acc_c = 0.0;
-        acc_c += (double)ch.x;
-        acc_c += (double)ch.y;
-        lane_c[s] += acc_c;
-        v2f ru, rv;
-        poly_dr2(c, hu, hv, ru, rv);
-        du = fma2(gr, ru, du);
-        dv = fma2(gr, rv, dv);
-    }
-    {
-        const v2f u2 = hu * hu, uv = hu * hv, v2 = hv * hv;
-        const v2f u3 = u2 * hu, u2v = u2 * hv, uv2 = hu * v2, v3 = v2 * hv;
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const v2f gr = gc[s] * dt;
-            MOM (&acc)[10] = mom[s];
-            mom_add1(acc[0], gr);
-            mom_add(acc[1], gr, hu); mom_add(acc[2], gr, hv);
-            mom_add(acc[3], gr, u2); mom_add(acc[4], gr, uv); mom_add(acc[5], gr, v2);
-            mom_add(acc[6], gr, u3); mom_add(acc[7], gr, u2v); mom_add(acc[8], gr, uv2); mom_add(acc[9], gr, v3);
-        }
-    }
-    const v2f tu = bc2(P[P_COEF + 0]) * dl[0] + du;
-    const v2f tv = bc2(P[P_COEF + 1]) * dl[1] + dv;
-    ou = gc[0] + tu;
-    ov = gc[1] + tv;
-}
-
-// one strip of one adjoint step: Gp = G + coef * (dt * LapT(G)) + dt * J_react(h)^T G (+ inj); pi_adj3d_brick_kernel's order
-// `jfr` (nullable, wave-uniform): the frame of dL/dtraj this step injects; its strip is requested at the top and used at the bottom
-template <typename MOM>
-__device__ __forceinline__ void adj_strip(const unsigned char* smem, unsigned lo, const float* __restrict__ P, const AdjOps& o,
-                                          const float* jfr, long ss, unsigned go, v4f& ou, v4f& ov, MOM (&mom)[2][10], double (&lane_c)[2])
-{
-    v4f ju, jv;
-    if (jfr) {
-        ju = *(const gv4f*)((const gchar*)jfr + go);
-        jv = *(const gv4f*)((const gchar*)(jfr + ss) + go);
-    }
-    v2f au, av, bu, bv;
-    adj_half(smem, lo, P, v2f{o.u[0], o.u[1]}, v2f{o.v[0], o.v[1]}, au, av, mom, lane_c);
-#if R3D_HALF_BARRIER
-    __builtin_amdgcn_sched_barrier(0);                                  // one half at a time (interleaved, their temporaries add up)
-#endif
-    adj_half(smem, lo + 8, P, v2f{o.u[2], o.u[3]}, v2f{o.v[2], o.v[3]}, bu, bv, mom, lane_c);
-    ou = v4f{au.x, au.y, bu.x, bu.y};
-    ov = v4f{av.x, av.y, bv.x, bv.y};
-    if (jfr) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { ou[i] += ju[i]; ov[i] += jv[i]; }
-    }
-}
-
-// R3D_P_RELOAD: the parameter block is read again for every strip (scalar loads from the constant cache) instead of living in ~50
-// scalar registers for the whole sweep, from where the allocator spilled it to vector lanes
-#ifndef R3D_P_RELOAD
-#define R3D_P_RELOAD 0
-#endif
-__device__ __forceinline__ const float* r3d_launder(const float* p) { asm volatile("" : "+s"(p)); return p; }
-#if R3D_P_RELOAD
-#define R3D_P(P) r3d_launder(P)
-#else
-#define R3D_P(P) (P)
-#endif
-#if R3D_ADJ_HALVES
-#define R3D_ADJ_STRIP adj_strip
-#else
-#define R3D_ADJ_STRIP adj_strip_whole
-#endif
 template <int NT>
 __global__ void __launch_bounds__(NT, 1)
 pi_adj3d_resident_kernel(const float* __restrict__ P, Args a, AdjArgs aa, unsigned long long* stamps)
@@ -863,20 +510,20 @@ pi_adj3d_resident_kernel(const float* __restrict__ P, Args a, AdjArgs aa, unsign
     }
     __syncthreads();
 
-    MomSum mom[2][10];
+    float mom[2][10];
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
-        for (int m = 0; m < 10; ++m) mom[s][m] = mom_zero();
+        for (int m = 0; m < 10; ++m) mom[s][m] = 0.f;
     double lane_c[2] = {0.0, 0.0};
     auto fold = [&]() {
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll
             for (int m = 0; m < 10; ++m) {
-                const float tot = wave_sum_to_last(mom_total(mom[s][m]));
+                const float tot = wave_sum_to_last(mom[s][m]);
                 if (lane == REDUCE_LANE) msum[wave * 20 + 10 * s + m] += (double)tot;
-                mom[s][m] = mom_zero();
+                mom[s][m] = 0.f;
             }
     };
 
@@ -900,7 +547,7 @@ pi_adj3d_resident_kernel(const float* __restrict__ P, Args a, AdjArgs aa, unsign
 #pragma unroll
         for (int s = 0; s < SLOTS; ++s)
             if (s * NW + wave < WS) {
-                R3D_ADJ_STRIP(smem, lo_of(s), R3D_P(P), ops[s & 1], jcu, a.ss, go_of(s), ou[s], ov[s], mom, lane_c);
+                adj_strip(smem, lo_of(s), P, ops[s & 1], jcu, a.ss, go_of(s), ou[s], ov[s], mom, lane_c);
                 next_ops(s);
                 __builtin_amdgcn_sched_barrier(0);                      // one strip at a time: interleaved strips spill
                 stage_strip(smem, task(s), ou[s], ov[s]);
@@ -918,7 +565,7 @@ pi_adj3d_resident_kernel(const float* __restrict__ P, Args a, AdjArgs aa, unsign
 #pragma unroll
         for (int s = 0; s < SLOTS; ++s)
             if (s * NW + wave >= WS) {
-                R3D_ADJ_STRIP(smem, lo_of(s), R3D_P(P), ops[s & 1], jcu, a.ss, go_of(s), ou[s], ov[s], mom, lane_c);
+                adj_strip(smem, lo_of(s), P, ops[s & 1], jcu, a.ss, go_of(s), ou[s], ov[s], mom, lane_c);
                 next_ops(s);
                 __builtin_amdgcn_sched_barrier(0);                      // one strip at a time: interleaved strips spill
             }

@@ -20,29 +20,6 @@
 
 namespace pi {
 
-#ifndef PI_TILE_ADJ_PIPE
-#define PI_TILE_ADJ_PIPE 1
-#endif
-#ifndef PI_PIN_MOMENTS
-#define PI_PIN_MOMENTS 1
-#endif
-#ifndef PI_FWD_IDLE_STORE
-#define PI_FWD_IDLE_STORE 1
-#endif
-#ifndef PI_FWD_IDLE_MAX
-#define PI_FWD_IDLE_MAX 4
-#endif
-#ifndef PI_PERSIST_GEO
-#define PI_PERSIST_GEO 1
-#endif
-#ifndef PI_PERSIST_LAUNDER
-#define PI_PERSIST_LAUNDER 0
-#endif
-#ifndef PI_PERSIST_OPAQUE_TID
-#define PI_PERSIST_OPAQUE_TID 1
-#endif
-
-
 #ifdef PI_TILE_TIMING
 // debug build only: per-workgroup s_memtime stamps {start, window loaded, after each sub-step (compute, store issued), end}
 __device__ long long pi_tile_stamps[4096 * 16];
@@ -376,20 +353,14 @@ __device__ __forceinline__ void poly_dr_v(const T* __restrict__ c, V2<T> u, V2<T
 // The Jacobian's coefficient multiples as ready pairs held in vector registers (persistent split sweep).  gfx950 has no scalar
 // float multiply: 2 c / 3 c are VALU products of a uniform value, and every use of one in a packed FMA needs the pair {x, x}
 // built by a v_mov -- per pass, in a loop bound by instruction issue.  Entry j of species s: 0 2c7, 1 2c3, 2 3c6, 3 3c9, 4 2c5,
-// 5 2c8, 6 c4; PI_JAC_MASK says which are held (the others are formed as before; all seven since the two parts of a mixed
-// pass share one body and the registers are there -- masks measured: profiles/r04_persist_issue_trim.txt).  Same single
+// 5 2c8, 6 c4; bit j of held_masks::jac says which are held (the others are formed as before; all seven since the two parts of
+// a mixed pass share one body and the registers are there -- masks measured: profiles/r04_persist_issue_trim.txt).  Same single
 // multiplication: bit-identical.
-#ifndef PI_JAC_MASK
-#define PI_JAC_MASK 0x7F
-#endif
-#ifndef PI_STEN_MASK
-#define PI_STEN_MASK 0xFFF
-#endif
 // ... and `st`: the pairs of dt (0), the diffusion coefficients (1, 2), c0 (3) and the eight taps (4..11) -- P[0..11] in P's own
-// order; PI_STEN_MASK says which are held
+// order; bit i of held_masks::sten says which are held (all twelve)
 template <typename T> struct JacPairs { V2<T> m[2][7]; V2<T> st[12]; };
 // (float32 only: a float64 pair is four registers -- 26 held pairs would be 104 of the 256; float64 forms them where they are used)
-template <typename T> struct held_masks { static constexpr int jac = sizeof(T) == 4 ? (PI_JAC_MASK) : 0, sten = sizeof(T) == 4 ? (PI_STEN_MASK) : 0; };
+template <typename T> struct held_masks { static constexpr int jac = sizeof(T) == 4 ? 0x7F : 0, sten = sizeof(T) == 4 ? 0xFFF : 0; };
 template <typename T>
 __device__ __forceinline__ void jac_pairs_load(JacPairs<T>& jp, const T* __restrict__ P)
 {
@@ -508,10 +479,11 @@ constexpr int fwd_first_idle_lane()
 {
     constexpr int rn4 = Tile<K, BX, BY>::region_n(M) / PTS;
     constexpr int busy = (rn4 + WAVE - 1) / WAVE * WAVE;
-    // only where the idle waves get away with <= PI_FWD_IDLE_MAX chunks per lane: ONE idle wave storing a whole frame (8 chunks
+    // only where the idle waves get away with <= IDLE_MAX chunks per lane: ONE idle wave storing a whole frame (8 chunks
     // per lane, 16 in float64) takes longer than the sub-step it hides behind and becomes the critical path (measured: 512^2
     // forward 1.70 -> 1.86 us per step, lambda-omega 2.78 -> 4.04)
-    return (busy < NT && CHUNKS <= PI_FWD_IDLE_MAX * (NT - busy)) ? busy : NT;
+    constexpr int IDLE_MAX = 4;
+    return (busy < NT && CHUNKS <= IDLE_MAX * (NT - busy)) ? busy : NT;
 }
 
 // tile_store by the lanes from FIRST on only (whole waves): frame M of the launch, written while the other waves compute
@@ -567,7 +539,7 @@ __device__ __forceinline__ void fwd_substeps(T* b0, T* b1, T* __restrict__ frame
     constexpr int CHUNKS = 2 * BY * BX / vec_width<T>::value;
     constexpr int PTS = HALFS ? 2 : 4;
     constexpr int IDLE = fwd_first_idle_lane<K, BX, BY, NT, M, CHUNKS, PTS>();
-    constexpr bool STORE_HERE = PI_FWD_IDLE_STORE && M >= 1 && IDLE < NT;       // frame M: by this sub-step's idle waves
+    constexpr bool STORE_HERE = M >= 1 && IDLE < NT;       // frame M: by this sub-step's idle waves
     if constexpr (STORE_HERE) {
         if ((int)threadIdx.x >= IDLE)
             tile_store_by_idle<T, K, BX, BY, NT, IDLE, ((M - 1) & 1) != 0, WT>(cur, frames + (long)M * frame_stride, g, ty0, tx0);
@@ -584,7 +556,7 @@ __device__ __forceinline__ void fwd_substeps(T* b0, T* b1, T* __restrict__ frame
     PI_STAMP(2 + 2 * M);
     lds_barrier();                                         // do not drain the previous frame's global stores
     // frame M + 1: left to the idle waves of the next sub-step if it has any, else stored now by everybody
-    constexpr bool NEXT_STORES = PI_FWD_IDLE_STORE && M + 1 < K && fwd_first_idle_lane<K, BX, BY, NT, (M + 1 < K ? M + 1 : M), CHUNKS, PTS>() < NT;
+    constexpr bool NEXT_STORES = M + 1 < K && fwd_first_idle_lane<K, BX, BY, NT, (M + 1 < K ? M + 1 : M), CHUNKS, PTS>() < NT;
     if constexpr (!NEXT_STORES && (M + 1 < K || LAST_STORE))
         tile_store<T, K, BX, BY, NT, (M & 1) != 0, WT>(nxt, frames + (long)(M + 1) * frame_stride, g, ty0, tx0);
     PI_STAMP(3 + 2 * M);
@@ -993,12 +965,10 @@ __device__ __forceinline__ void adj_substep(T* cur, T* nxt, const T* __restrict_
     static_assert(!HALFS || (GEO && PRE && HC == POLY), "half-strips: resident sweep passes with geometry words and prefetched operands");
     constexpr int NH = HALFS ? 1 : 2;                       // point pairs per lane
     int tid = (int)threadIdx.x;
-#if PI_PERSIST_OPAQUE_TID
     // split persistent sweep: eight passes inlined into one loop.  Everything derived from the lane's strip position (LDS
     // offsets, ownership masks, ...) is loop-invariant there and would be hoisted out of the group loop for ALL eight passes
     // at once -- ~80 VGPRs held for the whole kernel, which then spills.  An opaque lane id keeps each pass's geometry local.
     if constexpr (PART != PART_FULL) asm volatile("" : "+v"(tid));
-#endif
 #pragma unroll
     for (int q = 0; q < PT; ++q) {
         int off;
@@ -1224,7 +1194,6 @@ __device__ __forceinline__ void adj_substeps(T* b0, T* b1, const T* __restrict__
     adj_substep<T, HC, K, BX, BY, NT, M, PRE, MOM, PART_FULL, 0, GEO, NT, HALFS>(cur, nxt, hbase + fo, (inj_mask >> M) & 1u ? gbase + fo : nullptr, g,
                                                                                  ty0, tx0, P, acc_c, ops, mom, lacc, GEO ? geo + M * NT : nullptr, jp,
                                                                                  ob...);
-#if PI_PIN_MOMENTS
     // Pin this sub-step's moment accumulation HERE.  Left alone, the scheduler sinks the moment FMAs of all four sub-steps
     // (they depend on no LDS traffic) behind the last barrier -- 350 VALU instructions in the tail of the launch, where all
     // 256 workgroups execute them at the same time with nothing to overlap; inside the sub-step they fill LDS-latency and
@@ -1235,7 +1204,6 @@ __device__ __forceinline__ void adj_substeps(T* b0, T* b1, const T* __restrict__
 #pragma unroll
             for (int m = 0; m < 10; ++m) asm volatile("" : "+v"(mom.a[s][m]));
     }
-#endif
     PI_STAMP(2 + 3 * M);
     lds_barrier();
     PI_STAMP(3 + 3 * M);
@@ -1283,7 +1251,7 @@ pi_adj2d_tile_kernel(const T* __restrict__ hframe_t, const T* __restrict__ gfram
     // measured slower (17.6 vs 15.5 us per K=4 launch: 64 extra VGPRs, requests queued ahead of the window load).
     // (the float64 fused-moments flavour gives the operand pipeline's 32 registers to its 20 accumulators: with both it
     // needs ~270 of the 256 registers a 512-thread workgroup can have and spills -- 20 -> 47 us per launch, measured)
-    constexpr bool PRE = PI_TILE_ADJ_PIPE && TL::region_n(0) / 4 <= NT;
+    constexpr bool PRE = TL::region_n(0) / 4 <= NT;
     constexpr bool MOM_LACC = MOM && sizeof(T) == 8;       // float64: per-lane moment accumulators in LDS (adj_substep)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T* b0 = reinterpret_cast<T*>(smem_raw) + lds_pad0<T>::value;
@@ -1711,14 +1679,9 @@ pi_adj2d_persist_kernel(const T* __restrict__ hframe_t, const T* __restrict__ gf
 // (requests are what a hand-over costs, not bytes).  float64 (round 5, configs[2]): {lo32, tag, hi32, tag} = one value as two
 // self-validating 8-byte words.  float32 (round 6): {value 0, tag, value 1, tag} = TWO x-adjacent values -- the 8-byte {tag, value}
 // words of rounds 3-5 cost a request per handed-over float (3 + 5 per lane and group; now 2 + 3), VERDICT r5 #2.  The reader
-// accepts when BOTH tags match, so a torn pair is just "not yet".  PI_GRANULE_PAIR=0 keeps the 8-byte float32 words (A/B builds of
-// the harnesses only; the library is built with pairs).
-#ifndef PI_GRANULE_PAIR
-#define PI_GRANULE_PAIR 1
-#endif
+// accepts when BOTH tags match, so a torn pair is just "not yet".
 typedef unsigned pi_v4u __attribute__((ext_vector_type(4)));
 template <typename T> struct GranuleIO;
-#if PI_GRANULE_PAIR
 template <> struct GranuleIO<float> {
     using Raw = pi_v4u;
     static constexpr int BYTES = 16, VALS = 2;
@@ -1740,23 +1703,6 @@ template <> struct GranuleIO<float> {
         st<float, 2>(dst, Pack<float, 2>{{__builtin_bit_cast(float, a), __builtin_bit_cast(float, b)}});
     }
 };
-#else
-template <> struct GranuleIO<float> {
-    typedef __attribute__((address_space(1))) unsigned long long gu64;
-    using Raw = unsigned long long;
-    static constexpr int BYTES = 8, VALS = 1;
-    gu64* base;
-    __device__ __forceinline__ GranuleIO(void* outbox, size_t) : base((gu64*)outbox) {}
-    __device__ __forceinline__ void put(size_t idx, unsigned epoch, const float* src) const
-    {
-        __hip_atomic_store(base + idx, ((unsigned long long)epoch << 32) | __builtin_bit_cast(unsigned, *src), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __device__ __forceinline__ Raw get(size_t idx) const { return __hip_atomic_load(base + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    static __device__ __forceinline__ bool ok(Raw x, unsigned epoch) { return (unsigned)(x >> 32) == epoch; }
-    static __device__ __forceinline__ void land(Raw x, float* dst) { *dst = __builtin_bit_cast(float, (unsigned)x); }
-};
-#endif
 template <> struct GranuleIO<double> {
     using Raw = pi_v4u;
     static constexpr int BYTES = 16, VALS = 1;
@@ -1804,8 +1750,8 @@ pi_adj2d_persist_small_kernel(const T* __restrict__ hframe_t, const T* __restric
     constexpr int GV = PAIRS ? 2 : 1;
     static_assert(OWN % (2 * GV) == 0 && RINGH % GV == 0 && BX % GV == 0 && HW % GV == 0, "granules of x-adjacent values");
     constexpr int NPUB = (2 * OWN / GV + NT - 1) / NT, NGAT = (2 * RINGH / GV + NT - 1) / NT;
-    constexpr bool PRE = PI_TILE_ADJ_PIPE && TL::region_n(0) / (HALFS ? 2 : 4) <= NT;
-    static_assert(!HALFS || (PRE && PI_PERSIST_GEO != 0), "half-strips: prefetched operands, geometry words");
+    constexpr bool PRE = TL::region_n(0) / (HALFS ? 2 : 4) <= NT;
+    static_assert(!HALFS || PRE, "half-strips: prefetched operands (with the geometry words)");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T* b0 = reinterpret_cast<T*>(smem_raw) + lds_pad0<T>::value;
     T* b1 = reinterpret_cast<T*>(smem_raw) + 2 * TL::PLANE + lds_pad1<T>::value;
@@ -1901,10 +1847,10 @@ pi_adj2d_persist_small_kernel(const T* __restrict__ hframe_t, const T* __restric
         const bool last = grp + 1 == pa.ngroups;
         // every adjoint frame goes to memory (the moments pass reads them); the last one of the sweep may be dL/dh0 itself.  The
         // frame a group ends on is stored AFTER the tile has been published: the neighbours wait for the granules, nobody for it
-        adj_substeps<T, POLY, K, BX, BY, NT, 0, PRE, false, PI_PERSIST_GEO != 0, HALFS>(b0, b1, hframe_t + go, gframe_t + go, aframe_t + go,
-                                                                                        frame_stride, gmask, g_h0, g_h0 && last ? K : 0, g, ty0,
-                                                                                        tx0, P, acc_c, ops0, mom, sa, nullptr, last, tab_geo, &jp,
-                                                                                        hoff);
+        adj_substeps<T, POLY, K, BX, BY, NT, 0, PRE, false, true, HALFS>(b0, b1, hframe_t + go, gframe_t + go, aframe_t + go,
+                                                                         frame_stride, gmask, g_h0, g_h0 && last ? K : 0, g, ty0,
+                                                                         tx0, P, acc_c, ops0, mom, sa, nullptr, last, tab_geo, &jp,
+                                                                         hoff);
         if (last) break;
         const long gn = go - (long)K * frame_stride;
         gmask = persist_mask<K>(pa, pa.t_top - K * (grp + 1));
@@ -2104,25 +2050,11 @@ constexpr int PERSIST_SPLIT_TABLE_ROWS = 19;
 // eight waves: one wave per SIMD issues a 450-instruction strip at the single-wave rate (1.04 us per pass) while the other wave of the
 // SIMD idles; P2, where two strips share a SIMD, does them in 0.8 us each.  On half-strips these passes occupy all eight waves
 // (512 / 448 / 128 + 384 lanes) with half the points per lane.  P0 .. P2 keep whole strips.
-#ifndef PI_ADJ_PERSIST_PAUSE
-#define PI_ADJ_PERSIST_PAUSE 0          // split sweep: s_sleep units before the ring request (round 6: 0 / 8 / 32 measured, see profiles)
-#endif
-#ifndef PI_SWEEP_HALF
-#define PI_SWEEP_HALF 1
-#endif
-#ifndef PI_SWEEP_HALF_MASK
-#define PI_SWEEP_HALF_MASK 0x39         // bit p: pass p runs on half-strips: P0, P3, P4, P5 (P2 mixes two sub-steps and keeps whole strips;
-                                        // P1 on half-strips measured slower: 1.79 -> 1.81 us per step)
-#endif
 template <typename T, int PASS> struct sweep_half_pass {
-#ifndef PI_SWEEP_HALF_F64
-#define PI_SWEEP_HALF_F64 1
-#endif
-#ifndef PI_SWEEP_HALF_MASK_F64
-#define PI_SWEEP_HALF_MASK_F64 0x39         // (P1 too, 0x3B: 3.29 -> 3.29 us per step, no change)
-#endif
-    static constexpr bool value = PI_SWEEP_HALF != 0 && (sizeof(T) == 4 || PI_SWEEP_HALF_F64 != 0) && PASS != 2 &&
-                                  ((((sizeof(T) == 8 ? (PI_SWEEP_HALF_MASK_F64) : (PI_SWEEP_HALF_MASK))) >> PASS) & 1) != 0;
+    // bit p: pass p runs on half-strips: P0, P3, P4, P5, both element types (P2 mixes two sub-steps and keeps whole strips; P1 on
+    // half-strips measured slower)
+    static constexpr int HALF_PASS_MASK = 0x39;
+    static constexpr bool value = PASS != 2 && ((HALF_PASS_MASK >> PASS) & 1) != 0;
 };
 constexpr int SWEEP_HALF_P5_SPLIT = 128;                   // P5 on half-strips: I_3 = 64 strips on lanes 0 .. 127, A_3 = 192 from lane 128 on
 
@@ -2135,14 +2067,6 @@ template <> struct PersistPass<2> { static constexpr int M1 = 2, P1 = PART_PYR, 
 template <> struct PersistPass<3> { static constexpr int M1 = 1, P1 = PART_ANN, SPLIT = 1 << 30, M2 = 1, P2 = PART_ANN; };
 template <> struct PersistPass<4> { static constexpr int M1 = 2, P1 = PART_ANN, SPLIT = 1 << 30, M2 = 2, P2 = PART_ANN; };
 template <> struct PersistPass<5> { static constexpr int M1 = 3, P1 = PART_PYR, SPLIT = 64, M2 = 3, P2 = PART_ANN; };
-
-// the sub-step whose frame a lane's strip of pass PASS belongs to (wave-uniform)
-template <int PASS>
-__device__ __forceinline__ int persist_level(bool upper)
-{
-    using PP = PersistPass<PASS>;
-    return upper ? PP::M2 : PP::M1;
-}
 
 template <typename T, int K, int BX, int BY, int NT, int PASS>
 __device__ __forceinline__ StripOff persist_pass_off(const TileGeom& g, int ty0, int tx0, bool upper)
@@ -2214,8 +2138,7 @@ __device__ __forceinline__ void persist_pass(T* b0, T* b1, const T* const (&hf)[
                                              const unsigned* geo, const JacPairs<T>& jp, double* lacc = nullptr)
 {
     using PP = PersistPass<PASS>;
-    constexpr bool GEO = PI_PERSIST_GEO != 0;
-    constexpr bool HALF_HERE = GEO && sweep_half_pass<T, PASS>::value, HALF_NEXT = GEO && sweep_half_pass<T, (PASS + 1) % 6>::value;
+    constexpr bool HALF_HERE = sweep_half_pass<T, PASS>::value, HALF_NEXT = sweep_half_pass<T, (PASS + 1) % 6>::value;
     if constexpr (HALF_NEXT) persist_load_ops_half<T>(ahead, hn, gn, g, so_next.o0);
     else persist_load_ops<T>(ahead, hn, gn, g, so_next);
     constexpr int LACC = sizeof(T) == 8 ? NT / 2 : NT;     // float64: moments straight into the shared LDS rows (adj_substep)
@@ -2223,34 +2146,24 @@ __device__ __forceinline__ void persist_pass(T* b0, T* b1, const T* const (&hf)[
         // every lane a half-strip of sub-step M (P5: both parts are sub-step 3 and share the injection frame)
         static_assert(PP::M1 == PP::M2 || PP::SPLIT >= NT, "half-strip passes: one sub-step");
         constexpr int M = PP::M1;
-        adj_substep<T, POLY, K, BX, BY, NT, M, true, true, PP::P1, 0, GEO, LACC, true>((M & 1) ? b1 : b0, (M & 1) ? b0 : b1, hf[M], gf[M], g, ty0,
-                                                                                       tx0, P, acc_c, ops, mom, lacc, geo, &jp);
-    } else if constexpr (PP::SPLIT >= NT || GEO) {
+        adj_substep<T, POLY, K, BX, BY, NT, M, true, true, PP::P1, 0, true, LACC, true>((M & 1) ? b1 : b0, (M & 1) ? b0 : b1, hf[M], gf[M], g, ty0,
+                                                                                        tx0, P, acc_c, ops, mom, lacc, geo, &jp);
+    } else {
         // With the geometry in a table the sub-step's body no longer depends on WHICH strips a wave works on: the two parts of a
         // mixed pass (same parity of M: same buffers) run the same instructions with their own table words and their own
         // injection frame -- one body instead of two behind a branch (the moments' 20 register pairs were copied at every merge).
         static_assert(PP::SPLIT >= NT || ((PP::M1 ^ PP::M2) & 1) == 0, "both parts read the same buffer");
         constexpr int M = PP::M1;
         const T* gfr = (PP::SPLIT < NT && upper) ? gf[PP::M2] : gf[M];
-        adj_substep<T, POLY, K, BX, BY, NT, M, true, true, PP::P1, 0, GEO, LACC>((M & 1) ? b1 : b0, (M & 1) ? b0 : b1, hf[M], gfr, g, ty0,
-                                                                                 tx0, P, acc_c, ops, mom, lacc, geo, &jp);
-    } else if (!upper) {                                   // wave-uniform
-        constexpr int M = PP::M1;
-        adj_substep<T, POLY, K, BX, BY, NT, M, true, true, PP::P1, 0, GEO, LACC>((M & 1) ? b1 : b0, (M & 1) ? b0 : b1, hf[M], gf[M], g, ty0,
-                                                                                 tx0, P, acc_c, ops, mom, lacc, geo, &jp);
-    } else {
-        constexpr int M = PP::M2;
-        adj_substep<T, POLY, K, BX, BY, NT, M, true, true, PP::P2, PP::SPLIT, GEO, LACC>((M & 1) ? b1 : b0, (M & 1) ? b0 : b1, hf[M], gf[M],
-                                                                                         g, ty0, tx0, P, acc_c, ops, mom, lacc, geo, &jp);
+        adj_substep<T, POLY, K, BX, BY, NT, M, true, true, PP::P1, 0, true, LACC>((M & 1) ? b1 : b0, (M & 1) ? b0 : b1, hf[M], gfr, g, ty0,
+                                                                                  tx0, P, acc_c, ops, mom, lacc, geo, &jp);
     }
-#if PI_PIN_MOMENTS
     if constexpr (sizeof(T) == 4) {                        // (float64 keeps no moment registers: LDS rows)
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll
             for (int m = 0; m < 10; ++m) asm volatile("" : "+v"(mom.a[s][m]));
     }
-#endif
     lds_barrier();
 }
 
@@ -2370,9 +2283,6 @@ pi_adj2d_persist_split_kernel(const T* __restrict__ hframe_t, const T* __restric
         int gs[NGAT];
         typename GranuleIO<T>::Raw gx[NGAT];
         if (grp > 0) {
-#if PI_ADJ_PERSIST_PAUSE
-            __builtin_amdgcn_s_sleep(PI_ADJ_PERSIST_PAUSE);
-#endif
 #pragma unroll
             for (int q = 0; q < NGAT; ++q) {
                 gs[q] = tab_gs[q * NT + (int)threadIdx.x];
@@ -2550,118 +2460,6 @@ __device__ __forceinline__ void fwd_strip_geo(const T* cur, T* nxt, const T* __r
     }
 }
 
-// The same strip with ALL its LDS reads issued first (float32; round 6).  hipcc schedules the second species' stencil rows behind
-// the first species' arithmetic and store -- three load -> wait -> compute phases in a strip that is alone on its SIMD; with the
-// 14 reads of both species in flight at once the strip waits once.  Same operations in the same order per value as lds_star4 /
-// fwd_strip_geo: bit-identical.
-template <typename T, int LX>
-struct StarRows {
-    Pack<T, 2> l, r;         // x = -2, -1 | +4, +5 of the centre row
-    Pack<T, 4> m, n[4];      // the centre row's own four points; rows -2, -1, +1, +2
-    __device__ __forceinline__ void load(const T* c)
-    {
-        l = ld<T, 2>(c - 2); m = ld<T, 4>(c); r = ld<T, 2>(c + 4);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) n[t] = ld<T, 4>(c + (t < 2 ? t - 2 : t - 1) * LX);
-    }
-    __device__ __forceinline__ void star(const T* __restrict__ P, T (&ctr)[4], T (&lap)[4]) const
-    {
-        const T win[8] = {l.v[0], l.v[1], m.v[0], m.v[1], m.v[2], m.v[3], r.v[0], r.v[1]};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { ctr[i] = win[2 + i]; lap[i] = P[P_C0] * win[2 + i]; }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const T w = P[P_TAPS + t];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) lap[i] = fma_(w, n[t].v[i], lap[i]);
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int k = t < 2 ? t - 2 : t - 1;
-            const T w = P[P_TAPS + 4 + t];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) lap[i] = fma_(w, win[2 + i + k], lap[i]);
-        }
-    }
-};
-
-template <typename T, int K, int BX, int BY>
-__device__ __forceinline__ void fwd_strip_geo_loads_first(const T* cur, T* nxt, const T* __restrict__ P, unsigned w)
-{
-    static_assert(sizeof(T) == 4, "float32 (lds_star4's 16-byte reads)");
-    using TL = Tile<K, BX, BY>;
-    if (__builtin_amdgcn_ballot_w64(((w >> 16) & 1u) != 0u) == 0ull) return;
-    const int off = (int)(w & 0xFFFFu);
-    StarRows<T, TL::LX> ru, rv;
-    ru.load(cur + off);
-    rv.load(cur + TL::PLANE + off);
-    __builtin_amdgcn_sched_barrier(0);                     // nothing is scheduled across: every read is issued before the arithmetic
-    const T dt = P[P_DT];
-    T u[4], v[4], lap[2][4];
-    ru.star(P, u, lap[0]);
-    rv.star(P, v, lap[1]);
-    T o[2][4];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        T rr[4];
-        const T* c = P + P_W + 10 * s;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) rr[i] = poly_r(c, u[i], v[i]);
-        const T coef = P[P_COEF + s];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const T lp = s == 0 ? lap[0][i] : lap[1][i];
-            const T res = coef * lp + rr[i];
-            const T inc = res * dt;
-            o[s][i] = (s == 0 ? u[i] : v[i]) + inc;
-        }
-    }
-    lds_store4(nxt + off, o[0]);
-    lds_store4(nxt + TL::PLANE + off, o[1]);
-}
-
-// the owned BX x BY region of a level buffer -> its frame, by the lanes [FIRST, NT).  WHICH 0: all of it; 1: the block of rows /
-// 16-byte chunks that covers what I_2 overwrites (level 1 only); 2: everything but that block
-template <typename T, int K, int BX, int BY, int NT, int FIRST, bool PADDED, int WHICH>
-__device__ __forceinline__ void persist_fwd_store(const T* buf, T* __restrict__ dst, const TileGeom& g, int ty0, int tx0)
-{
-    using TL = Tile<K, BX, BY>;
-    constexpr int VEC = vec_width<T>::value;                               // 16-byte chunks: 4 float32 / 2 float64
-    constexpr int BXV = BX / VEC, N = 2 * BY * BXV, LANES = NT - FIRST;
-    constexpr int SIDE = BX - 4 * (K - 1), O2 = (BX - SIDE) / 2;           // I_2's output square: side 20 at offset 6
-    constexpr int R0 = O2, R1 = O2 + SIDE, C0 = O2 / VEC, C1 = (O2 + SIDE + VEC - 1) / VEC;
-    static_assert(C0 * VEC >= 2 && C1 * VEC <= BX - 2 && R0 >= 2 && R1 <= BY - 2, "the early block lies inside I_0's output");
-    if ((int)threadIdx.x < FIRST) return;
-    for (int i = (int)threadIdx.x - FIRST; i < N; i += LANES) {
-        const int s = i / (BY * BXV);
-        const int r = i - s * (BY * BXV);
-        const int y = r / BXV, c = r - y * BXV;
-        const bool early = y >= R0 && y < R1 && c >= C0 && c < C1;
-        if (WHICH == 1 && !early) continue;
-        if (WHICH == 2 && early) continue;
-        const T* src = buf + s * TL::PLANE + (2 * K + y) * TL::LX + 2 * K + c * VEC;
-        Pack<T, VEC> p;
-        if constexpr (PADDED && lds_pad0<T>::value != 0) {
-            const Pack<T, 2> a = ld<T, 2>(src), b = ld<T, 2>(src + 2);
-            p.v[0] = a.v[0]; p.v[1] = a.v[1]; p.v[2] = b.v[0]; p.v[3] = b.v[1];
-        } else {
-            p = ld<T, VEC>(src);
-        }
-        #if PI_FWD_PERSIST_WT
-        st_frame_wt<T, VEC>(dst + s * g.ss + (long)(ty0 + y) * g.W + tx0 + c * VEC, p);
-#else
-        *reinterpret_cast<Pack<T, VEC>*>(dst + s * g.ss + (long)(ty0 + y) * g.W + tx0 + c * VEC) = p;
-#endif
-    }
-}
-
-#ifndef PI_FWD_PERSIST_REQ_AFTER
-#define PI_FWD_PERSIST_REQ_AFTER 0      // the ring is requested after pass P<this> (0 or 1).  Measured (tools/fwd_dev.hip): after P0 --
-#endif                                  // 0.76 us into the group -- 5.74 us per group; after P1 (1.6 us) 6.55; one launch per group 6.64
-#ifndef PI_FWD_PERSIST_WT
-#define PI_FWD_PERSIST_WT 0             // frame stores of the resident forward: 0 = plain (write-back) stores.  Nobody reads a frame from
-#endif                                  // memory before the launch ends (the state lives in LDS, halos travel as granules), and write-through
-                                        // stores compete with the latency-critical granule loads: 5.8 -> 5.45 us per group (tools/fwd_dev.hip)
 // HALF STRIPS (round 6; float32 and float64).  The annulus passes A_0 .. A_3 of a group are the loop ring -> A_0 .. A_3 -> publish -> flight that
 // sets the resident forward's pace, and each of them is ONE four-point strip per wave on four to six of the eight waves: 128
 // instructions (0.19 us of VALU issue) that take 0.56 us because the wave waits for its own LDS round trips with nobody to
@@ -2732,10 +2530,14 @@ __device__ __forceinline__ void fwd_half_strip_geo(const T* cur, T* nxt, const T
     }
 }
 
-// The same with the lane's chunks located ONCE per rollout (round 6): which chunks a lane stores never changes, but the loop
-// above re-derived species / row / column, the early-block test and both addresses for every chunk of every level of every group
-// -- ~40 VALU instructions per chunk on the SIMD that a computing wave shares.  Here: LDS element offset + frame element offset per
-// chunk in registers, a store is a read, a 32-bit offset next to the frame's wave-uniform base, and the write.
+// The owned BX x BY region of a level buffer -> its frame, by the lanes [FIRST, NT), with the lane's chunks located ONCE per rollout
+// (round 6): which chunks a lane stores never changes, but a loop over them re-derived species / row / column, the early-block
+// test and both addresses for every chunk of every level of every group -- ~40 VALU instructions per chunk on the SIMD that a
+// computing wave shares.  Here: LDS element offset + frame element offset per chunk in registers, a store is a read, a 32-bit
+// offset next to the frame's wave-uniform base, and the write.  WHICH 0: all of the region; 1: the block of rows / 16-byte chunks
+// that covers what I_2 overwrites (level 1 only); 2: everything but that block.
+// The stores are plain (write-back): nobody reads a frame from memory before the launch ends (the state lives in LDS, halos travel
+// as granules), and write-through stores compete with the latency-critical granule loads.
 template <typename T, int K, int BX, int BY, int NT, int FIRST>
 struct FwdStoreMap {
     using TL = Tile<K, BX, BY>;
@@ -2776,51 +2578,13 @@ struct FwdStoreMap {
             } else {
                 p = ld<T, VEC>(src);
             }
-#if PI_FWD_PERSIST_WT
-            st_frame_wt<T, VEC>(dst + glb[j], p);
-#else
             *reinterpret_cast<Pack<T, VEC>*>(dst + glb[j]) = p;
-#endif
         }
     }
 };
 
-#ifndef PI_FWD_I2_EARLY
-#define PI_FWD_I2_EARLY 0               // resident forward: the pyramid's third level under the ring's flight instead of next to A_0
-                                        // (round 6: bit-identical, 1.26 -> 1.27-1.32 us per step: the extra barrier costs what P2 gains).  Off.
-#endif
-#ifndef PI_FWD_HALF_STRIPS_F64
-#define PI_FWD_HALF_STRIPS_F64 1        // ... of the float64 forward (a strip is twice the instructions there)
-#endif
-#ifndef PI_FWD_HALF_I3
-#define PI_FWD_HALF_I3 1                // half-strip builds: I_3 (P5) on half-strips too, on waves 0 and 7, instead of whole strips on wave 0
-#endif
-#ifndef PI_FWD_HALF_PYR_F64
-#define PI_FWD_HALF_PYR_F64 0           // ... and its pyramid passes P0 / P1 (I_0 on seven waves instead of four, I_1 on five instead of three):
-                                        // bit-identical, lambda-omega forward 1.807 -> 1.838 us per step (they run under the ring's flight).  Off.
-#endif
-#ifndef PI_FWD_HALF_PYR
-#define PI_FWD_HALF_PYR 0                   // (float32: 1.239 -> 1.236 us per step, nothing)
-#endif
-#ifndef PI_FWD_HALF_STRIPS
-#define PI_FWD_HALF_STRIPS 1            // float32 resident forward: the annulus passes on two-point half-strips (all eight waves).
-                                        // Measured (round 6): bit-identical, 1.26 -> 1.24 us per step -- a half-strip takes as long as a strip
-                                        // (0.52-0.56 us: the pass is LDS round trips, not arithmetic); again after the small-tile work:
-                                        // 1.27 -> 1.258; with I_3 on half-strips as well (PI_FWD_HALF_I3) 1.27 -> 1.239, headline 325.9 ->
-                                        // 328.4 k: ON since then (float64, twice the arithmetic per strip, gains 12 % from the same passes).
-#endif
-#ifndef PI_FWD_HOLD_P
-#define PI_FWD_HOLD_P 1                 // float32 resident forward: parameter block (1: vector, 2: scalar registers), strip geometry and
-                                        // frame-store map held in registers for the whole rollout; 0: round 5's body
-#endif
-#ifndef PI_FWD_LOADS_FIRST
-#define PI_FWD_LOADS_FIRST 0            // 1: fwd_strip_geo_loads_first (float32 only)
-#endif
-#ifndef PI_FWD_PERSIST_PAUSE
-#define PI_FWD_PERSIST_PAUSE 0          // s_sleep units before the request
-#endif
-
-template <typename T, int K, int BX, int BY, int NT, int HOLDP = PI_FWD_HOLD_P>
+// HOLDP: the parameter block held in vector (1) or scalar (2) registers for the whole rollout; the host picks
+template <typename T, int K, int BX, int BY, int NT, int HOLDP>
 __global__ void __launch_bounds__(NT)
 pi_fwd2d_persist_kernel(T* __restrict__ frames /* frame t0; t0+1 .. t0 + K * ngroups are written */, long frame_stride,
                         const T* __restrict__ P_in, TileGeom g, PersistArgs pa)
@@ -2877,76 +2641,51 @@ pi_fwd2d_persist_kernel(T* __restrict__ frames /* frame t0; t0+1 .. t0 + K * ngr
     //  * the lane's six strip-geometry words (the sweep, at 251 registers, keeps its LDS table; the forward uses 78 of 256);
     //  * where the lane's frame chunks lie (FwdStoreMap).
     // 512^2 x 1000, tools/fwd_dev.hip, same box: 1.335 -> 1.283 (block) -> 1.260 (+ geometry) -> 1.248 us per step (+ store map);
-    // trajectory bit-identical.  Reading all of a strip's LDS rows before its arithmetic (fwd_strip_geo_loads_first) measured no
-    // gain on top (1.26 either way) and is not used.
+    // trajectory bit-identical.
     // HOLDP 1: the block in vector registers (142 registers: one workgroup per CU); 2: in scalar registers (83 vector registers: the
-    // two-workgroups-per-CU mode of option fwd_persist_per_cu still fits; 1.29 instead of 1.26 us per step); 0: round 5's body
-    constexpr bool HOLD = HOLDP != 0;                       // (float64: 101 -> ~190 of 256 registers)
-    T Ph[HOLD ? NPOLY : 1];
-    constexpr bool HALF = HOLD && ((PI_FWD_HALF_STRIPS != 0 && sizeof(T) == 4) || (PI_FWD_HALF_STRIPS_F64 != 0 && sizeof(T) == 8));
-    constexpr bool HALF_PYR = HALF && ((PI_FWD_HALF_PYR != 0 && sizeof(T) == 4) || (PI_FWD_HALF_PYR_F64 != 0 && sizeof(T) == 8));
-    unsigned gw[HOLD ? 7 : 1];
+    // two-workgroups-per-CU mode of option fwd_persist_per_cu still fits; 1.29 instead of 1.26 us per step)
+    static_assert(HOLDP == 1 || HOLDP == 2, "the parameter block is held in vector or in scalar registers");
+    T Ph[NPOLY];                                            // (float64: 101 -> ~190 of 256 registers)
+    unsigned gw[7];
     FwdStoreMap<T, K, BX, BY, NT, IDLE> smap;
     FwdStoreMap<T, K, BX, BY, NT, 0> smap_all;              // (half-strip passes: every wave computes, every lane stores one chunk)
     const int wave_id = __builtin_amdgcn_readfirstlane(tid >> 6);
-    if constexpr (HOLD) {
 #pragma unroll
-        for (int i = 0; i < NPOLY; ++i) {
-            T x = P_in[i];
-            if constexpr (HOLDP == 2) asm volatile("" : "+s"(x));
-            else asm volatile("" : "+v"(x));
-            Ph[i] = x;
-        }
-#pragma unroll
-        for (int i = 0; i < 6; ++i) gw[i] = tab_geo[i * NT + tid];
-        gw[6] = 0u;
-        if constexpr (HALF) {
-            // P2: I_2 on waves 0-1 (four-point strips), A_0 = 576 half-strips on the 384 lanes of waves 2-7 in two rounds (gw[2], gw[6]);
-            // P3: A_1 = 512 half-strips; P4: A_2 = 448; P5: I_3 on wave 0, A_3 = 384 half-strips on waves 1-6
-            if (tid >= 128) { gw[2] = fwd_half_word<K, BX, BY, 0>(tid - 128); gw[6] = fwd_half_word<K, BX, BY, 0>(tid - 128 + 384); }
-            gw[3] = fwd_half_word<K, BX, BY, 1>(tid);
-            gw[4] = fwd_half_word<K, BX, BY, 2>(tid);
-            if (tid >= 64) gw[5] = fwd_half_word<K, BX, BY, 3>(tid - 64);
-            if constexpr (PI_FWD_HALF_I3 != 0) {            // I_3 = 128 half-strips on wave 0 and on wave 7 (idle in P5 otherwise)
-                if (tid < 64) gw[5] = fwd_half_word<K, BX, BY, 3, PART_PYR>(tid);
-                if (tid >= 448) gw[5] = fwd_half_word<K, BX, BY, 3, PART_PYR>(tid - 448 + 64);
-            }
-            if constexpr (HALF_PYR) {
-                gw[0] = fwd_half_word<K, BX, BY, 0, PART_PYR>(tid);
-                gw[1] = fwd_half_word<K, BX, BY, 1, PART_PYR>(tid);
-            }
-            smap_all.init(g, ty0, tx0);
-        }
-#pragma unroll
-        for (int i = 0; i < 7; ++i) asm volatile("" : "+v"(gw[i]));
-        smap.init(g, ty0, tx0);
+    for (int i = 0; i < NPOLY; ++i) {
+        T x = P_in[i];
+        if constexpr (HOLDP == 2) asm volatile("" : "+s"(x));
+        else asm volatile("" : "+v"(x));
+        Ph[i] = x;
     }
-    const T* P = HOLD ? Ph : P_in;
-    auto geo = [&](int i) -> unsigned { if constexpr (HOLD) return gw[i]; else return tab_geo[i * NT + tid]; };
-#define PI_FWD_GEO(i) geo(i)
-#define PI_FWD_STORE(PADDED, WHICH, buf, dst)                                                                      \
-    do {                                                                                                           \
-        if constexpr (HOLD) smap.template store<PADDED, WHICH>(buf, dst);                                          \
-        else persist_fwd_store<T, K, BX, BY, NT, IDLE, PADDED, WHICH>(buf, dst, g, ty0, tx0);                       \
-    } while (0)
-    auto PI_FWD_STRIP = [&](const T* cur, T* nxt, const T* pp, unsigned w) {
-        if constexpr (PI_FWD_LOADS_FIRST != 0 && sizeof(T) == 4) fwd_strip_geo_loads_first<T, K, BX, BY>(cur, nxt, pp, w);
-        else fwd_strip_geo<T, K, BX, BY>(cur, nxt, pp, w);
-    };
-    auto half_strip = [&](const T* cur, T* nxt, unsigned w) {
-        if constexpr (HALF) fwd_half_strip_geo<T, K, BX, BY>(cur, nxt, P, w);
-    };
+#pragma unroll
+    for (int i = 0; i < 6; ++i) gw[i] = tab_geo[i * NT + tid];
+    gw[6] = 0u;
+    // The annulus passes run on half-strips (see above), the pyramid passes P0 / P1 on whole strips (they run under the ring's flight).
+    // P2: I_2 on waves 0-1 (four-point strips), A_0 = 576 half-strips on the 384 lanes of waves 2-7 in two rounds (gw[2], gw[6]);
+    // P3: A_1 = 512 half-strips; P4: A_2 = 448; P5: A_3 = 384 half-strips on waves 1-6
+    if (tid >= 128) { gw[2] = fwd_half_word<K, BX, BY, 0>(tid - 128); gw[6] = fwd_half_word<K, BX, BY, 0>(tid - 128 + 384); }
+    gw[3] = fwd_half_word<K, BX, BY, 1>(tid);
+    gw[4] = fwd_half_word<K, BX, BY, 2>(tid);
+    if (tid >= 64) gw[5] = fwd_half_word<K, BX, BY, 3>(tid - 64);
+    // I_3 = 128 half-strips on wave 0 and on wave 7 (idle in P5 otherwise)
+    if (tid < 64) gw[5] = fwd_half_word<K, BX, BY, 3, PART_PYR>(tid);
+    if (tid >= 448) gw[5] = fwd_half_word<K, BX, BY, 3, PART_PYR>(tid - 448 + 64);
+    smap_all.init(g, ty0, tx0);
+#pragma unroll
+    for (int i = 0; i < 7; ++i) asm volatile("" : "+v"(gw[i]));
+    smap.init(g, ty0, tx0);
+    const T* P = Ph;
+    // (lambdas on purpose, `request` below too: written as plain calls the same statements compile to other code, here AND in
+    // pi_adj2d_persist_split_kernel, which shares this translation unit's device functions -- docs/NOTEBOOK.md section 21)
+    auto geo = [&](int i) -> unsigned { return gw[i]; };
+    auto strip = [&](const T* cur, T* nxt, const T* pp, unsigned w) { fwd_strip_geo<T, K, BX, BY>(cur, nxt, pp, w); };
+    auto half_strip = [&](const T* cur, T* nxt, unsigned w) { fwd_half_strip_geo<T, K, BX, BY>(cur, nxt, P, w); };
     for (int grp = 0; grp < pa.ngroups; ++grp) {
         T* fr = frames + (long)grp * K * frame_stride;                    // this group's frame t: fr + m * frame_stride = level m
         PI_PSTAMP(0);
         // ---- P0: I_0 (b0 -> b1); the idle waves store level 4 of the previous group (= this group's level 0, complete in b0) ----
-        if constexpr (HALF_PYR) {
-            if (grp > 0) smap_all.template store<true, 0>(b0, fr);
-            half_strip(b0, b1, gw[0]);
-        } else {
-            if (grp > 0) PI_FWD_STORE(true, 0, b0, fr);
-            PI_FWD_STRIP(b0, b1, P, PI_FWD_GEO(0));
-        }
+        if (grp > 0) smap.template store<true, 0>(b0, fr);
+        strip(b0, b1, P, geo(0));
         lds_barrier();
         PI_PSTAMP(1);
         const unsigned epoch = (unsigned)grp;
@@ -2955,9 +2694,6 @@ pi_fwd2d_persist_kernel(T* __restrict__ frames /* frame t0; t0+1 .. t0 + K * ngr
         typename GranuleIO<T>::Raw gx[NGAT];
         auto request = [&]() {
             if (grp > 0) {
-#if PI_FWD_PERSIST_PAUSE
-                __builtin_amdgcn_s_sleep(PI_FWD_PERSIST_PAUSE);
-#endif
 #pragma unroll
                 for (int q = 0; q < NGAT; ++q) {
                     gs[q] = tab_gs[q * NT + tid];
@@ -2965,23 +2701,12 @@ pi_fwd2d_persist_kernel(T* __restrict__ frames /* frame t0; t0+1 .. t0 + K * ngr
                 }
             }
         };
-        if constexpr (PI_FWD_PERSIST_REQ_AFTER == 0) request();
+        // ---- the halo ring is requested right after P0, 0.76 us into the group: the loads travel under P1 ----
+        request();
         // ---- P1: I_1 (b1 -> b0 centre); the idle waves store the block of level 1 that I_2 will overwrite ----
-        if constexpr (HALF_PYR) {
-            smap_all.template store<false, 1>(b1, fr + frame_stride);
-            half_strip(b1, b0, gw[1]);
-        } else {
-            PI_FWD_STORE(false, 1, b1, fr + frame_stride);
-            PI_FWD_STRIP(b1, b0, P, PI_FWD_GEO(1));
-        }
+        smap.template store<false, 1>(b1, fr + frame_stride);
+        strip(b1, b0, P, geo(1));
         PI_PSTAMP(2);
-        if constexpr (PI_FWD_PERSIST_REQ_AFTER == 1) request();
-        if constexpr (PI_FWD_I2_EARLY != 0) {
-            // I_2 (waves 0-1; it needs I_1 only) while the ring is still in flight, instead of next to A_0 behind it: P2 is then the
-            // annulus alone.  One more barrier; b1's centre is free (its early block of level 1 was stored during P1).
-            lds_barrier();
-            if (wave_id < 2) PI_FWD_STRIP(b0, b1, P, PI_FWD_GEO(2));
-        }
         if (grp > 0) {
             int gl[NGAT];
 #pragma unroll
@@ -3025,39 +2750,25 @@ pi_fwd2d_persist_kernel(T* __restrict__ frames /* frame t0; t0+1 .. t0 + K * ngr
         }
         PI_PSTAMP(3);
         // ---- P2: I_2 (b0 centre -> b1 centre) next to A_0 (b0 with its ring -> b1 outside I_0's square) ----
-        if constexpr (HALF) {
-            if (wave_id < 2) PI_FWD_STRIP(b0, b1, P, gw[2]);
-            else { half_strip(b0, b1, gw[2]); half_strip(b0, b1, gw[6]); }
-        } else if constexpr (PI_FWD_I2_EARLY != 0) {
-            if (wave_id >= 2) PI_FWD_STRIP(b0, b1, P, PI_FWD_GEO(2));
-        } else {
-            PI_FWD_STRIP(b0, b1, P, PI_FWD_GEO(2));
-        }
+        if (wave_id < 2) strip(b0, b1, P, gw[2]);
+        else { half_strip(b0, b1, gw[2]); half_strip(b0, b1, gw[6]); }
         lds_barrier();
         PI_PSTAMP(4);
         // ---- P3: A_1 (b1 -> b0); level 1 is complete in b1 outside the block stored in P1 ----
-        if constexpr (HALF) smap_all.template store<false, 2>(b1, fr + frame_stride);
-        else PI_FWD_STORE(false, 2, b1, fr + frame_stride);
+        smap_all.template store<false, 2>(b1, fr + frame_stride);
         PI_PSTAMP(9);                                      // (debug builds: what a pass is made of -- tools/fwd_dev.hip)
-        if constexpr (HALF) half_strip(b1, b0, gw[3]);
-        else PI_FWD_STRIP(b1, b0, P, PI_FWD_GEO(3));
+        half_strip(b1, b0, gw[3]);
         PI_PSTAMP(10);
         lds_barrier();
         PI_PSTAMP(5);
         // ---- P4: A_2 (b0 -> b1); level 2 is complete in b0 ----
-        if constexpr (HALF) { smap_all.template store<true, 0>(b0, fr + 2 * frame_stride); half_strip(b0, b1, gw[4]); }
-        else { PI_FWD_STORE(true, 0, b0, fr + 2 * frame_stride); PI_FWD_STRIP(b0, b1, P, PI_FWD_GEO(4)); }
+        smap_all.template store<true, 0>(b0, fr + 2 * frame_stride);
+        half_strip(b0, b1, gw[4]);
         lds_barrier();
         PI_PSTAMP(6);
         // ---- P5: I_3 + A_3 (b1 -> b0); level 3 is complete in b1 ----
-        if constexpr (HALF) {
-            smap_all.template store<false, 0>(b1, fr + 3 * frame_stride);
-            if (PI_FWD_HALF_I3 == 0 && wave_id < 1) PI_FWD_STRIP(b1, b0, P, gw[5]);
-            else half_strip(b1, b0, gw[5]);
-        } else {
-            PI_FWD_STORE(false, 0, b1, fr + 3 * frame_stride);
-            PI_FWD_STRIP(b1, b0, P, PI_FWD_GEO(5));
-        }
+        smap_all.template store<false, 0>(b1, fr + 3 * frame_stride);
+        half_strip(b1, b0, gw[5]);
         lds_barrier();
         PI_PSTAMP(7);
         if (grp + 1 == pa.ngroups) {                       // the last level 4: stored by everybody
@@ -3079,9 +2790,6 @@ pi_fwd2d_persist_kernel(T* __restrict__ frames /* frame t0; t0+1 .. t0 + K * ngr
 }
 
 // ------------------------------------------------------------------------------------------------
-#undef PI_FWD_GEO
-#undef PI_FWD_STORE
-
 // PERSISTENT FORWARD for the SMALL-TILE regime and ragged grids (round 5): grids that are not whole 32 x 32
 // tiles or have fewer than 16 of them -- the reference's own 100^2 x 200 rollout (train_2drd.py:162-190, :597-636) among them --
 // paid one launch per four steps: 5.0 us for sub-steps that take under two.  Here the T-step rollout is ONE launch of resident

@@ -98,7 +98,7 @@ int main(int argc, char** argv)
         CK(hipMalloc(&outbox, outbox_bytes));
         CK(hipMalloc(&sync, 64));
         CK(hipHostMalloc(&host, 64, hipHostMallocMapped | hipHostMallocCoherent));
-        auto* kp = pi::pi_fwd2d_persist_kernel<float, K, B, B, NT>;
+        auto* kp = pi::pi_fwd2d_persist_kernel<float, K, B, B, NT, 1>;
         const size_t lds_p = pi::tile_state_bytes<float, K, B, B>() + (size_t)pi::PERSIST_SPLIT_TABLE_ROWS * NT * sizeof(int) + 16;
         CK(hipFuncSetAttribute(reinterpret_cast<const void*>(kp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
         auto run_p = [&]() {

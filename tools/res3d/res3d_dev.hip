@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../percnn_amd/csrc/pi_res3d.h"
+#include "res3d_fwd.h"
 #ifndef R3D_NT
 #define R3D_NT 512
 #endif

@@ -24,7 +24,6 @@ __global__ void __launch_bounds__(NT) k(const float* __restrict__ P_in, float* o
     for (int i = 0; i < n; ++i) {
         if (MODE == 0) { fwd_strip_geo<float, K, B, B>(b0, b1, Ph, w); fwd_strip_geo<float, K, B, B>(b1, b0, Ph, w); }
         if (MODE == 1) { fwd_strip_geo<float, K, B, B>(b0, b1, Ph, w); lds_barrier(); fwd_strip_geo<float, K, B, B>(b1, b0, Ph, w); lds_barrier(); }
-        if (MODE == 2) { fwd_strip_geo_loads_first<float, K, B, B>(b0, b1, Ph, w); fwd_strip_geo_loads_first<float, K, B, B>(b1, b0, Ph, w); }
     }
     const unsigned long long t1 = wall_clock64();
     out[threadIdx.x + blockIdx.x * NT] = b0[sy * TL::LX + sx];
@@ -57,7 +56,6 @@ int main(int argc, char** argv)
         run<512, 0>(P, o, t, blocks, "strips back to back");
         run<256, 1>(P, o, t, blocks, "strip + barrier");
         run<512, 1>(P, o, t, blocks, "strip + barrier");
-        run<256, 2>(P, o, t, blocks, "loads first, back to back");
         run<64, 0>(P, o, t, blocks, "one wave alone");
     }
     return 0;
