@@ -156,6 +156,12 @@ size_t percnn_pi_rollout_bwd_workspace_bytes(int hc, int ndim, const int64_t *sh
  *   "tile_by"      tile height: 8, 16, 32, 0 (default) = 8 while 32x8 tiles fit one per CU, 16 while 32x32 tiles would leave
  *                  more than half the CUs idle, else 32
  *   "tile_xcd"     1 (default) = XCD-aware block -> tile map
+ *   "handover_local"  1 (default): the 32 x 32 resident FORWARD ("fwd_persist"; float32 and float64) publishes a band granule
+ *                  with a plain store when every tile that reads it runs on the publisher's XCD -- by the "tile_xcd" map, and
+ *                  only for neighbours whose hardware XCC id, which every workgroup announces at start, equals the publisher's
+ *                  own -- so that it stays in that XCD's L2; the other granules are written through as before (512^2: 1.235 ->
+ *                  1.151 us per forward step).  Results are bit-identical under any placement.  0: every granule is written
+ *                  through, as the resident sweeps always do (their ring landed no earlier with local granules).  Per call too.
  *   "stream3d"     3D plane-streaming kernels: 0 never, 1 (default) by size, 2 whenever W == 64 * lanes' vector width
  *   "zc"           planes per workgroup of the plane-streaming kernels (default 8; the adjoint uses twice that)
  *   "fuse_wgrad"   parameter gradients reduced inside the sweep launches instead of one time-parallel pass:
@@ -410,7 +416,17 @@ int percnn_pi_debug_blockmap(int ndim, const int64_t* shape, int elem_size, cons
  * tile_persist; asks the current device for its CU count -- 0 without a device), bit 1: so does its forward (fwd_persist)};
  * families: 0 direct step kernels,
  * 1 2D tile kernels, 2 3D plane streaming, 3 3D brick kernels, 4 advective block.  (The lanes are those of the launch-per-group
- * tile kernels; the resident launches of the 8- and 16-row regimes run twice as many on half-strips: fwd_small_half, adj_small_half.) */
+ * tile kernels; the resident launches of the 8- and 16-row regimes run twice as many on half-strips: fwd_small_half, adj_small_half.)
+ * With "debug_handover_local=N", N > 0, among `options` (a per-call key of this entry alone: percnn_pi_set_option and every
+ * other entry refuse it; the number of entry points is pinned, so the query has none of its own) the call answers another
+ * question, launches nothing either, and `out` is a buffer of N ints: for a 2D grid of whole 32 x 32 tiles it receives one
+ * bitmap per tile, tile after tile in row-major order, of the tile's G band granules (G = 768, float32: 16-byte granules of two
+ * values; 1536, float64; G / 32 ints per tile, bit i % 32 of int i / 32 = granule i in outbox order: species, then the band's
+ * rows of 32, its last rows, then the 2 x 8 side values of the rows between, divided by the values per granule).  A set bit:
+ * option "handover_local" lets the resident forward publish that granule with a plain store according to the "tile_xcd"
+ * rectangle map -- its readers (the side neighbour, or both side neighbours and the diagonal one for an 8 x 8 corner block,
+ * periodic wrap applied) all share the tile's XCD.  N < tiles * G / 32: PERCNN_PI_EINVAL, nothing is written.  The kernels
+ * additionally confirm every neighbour's placement at run time. */
 int percnn_pi_debug_plan(int hc, int ndim, const int64_t* shape, int elem_size, const char* options, int* out);
 /* Host-only: the kernel family of the launch-per-step part of a batched / ensemble call over `batch` samples (every step of a 3D
  * call; what a 2D call runs beside its tile groups), for 16-byte-aligned buffers and the plain injection form.

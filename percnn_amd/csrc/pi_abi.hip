@@ -50,6 +50,11 @@ struct Options {
                             // 26.0 -> 23.3 us per step, 2048^2: 45.4 -> 39.8; fp64 and the factored mode lose)
     int skip_wgrad = 0;     // diagnostics: rollout_bwd runs the adjoint sweep only (bench uses it to time the sweep alone)
     int tile_xcd = 1;       // XCD-aware block -> tile map of the 2D tile kernels (0 = identity)
+    int handover_local = 1; // 32 x 32 resident FORWARD: band granules whose readers all run on the publisher's XCD (by that map,
+                            // confirmed by the hardware's XCC ids at run time) are published with plain stores and stay in the
+                            // XCD's L2; 0: every granule is written through (the resident sweeps always do: measured, no gain)
+    int debug_handover_local = 0;   // per call, percnn_pi_debug_plan only: N > 0 = write the bitmaps of local band granules into
+                                    // an `out` of N ints instead of the plan (the entry-point count is pinned, hence no entry of its own)
     int tile_by = 0;        // tile height of the 2D tile kernels: 32, 16, or 0 = by grid size (see tile_by_for)
     int slab_fused_put_adj = 0; // ... and the adjoint sweep's faces by the sweep launch (to self: no gain; across xGMI: bench.py decides)
     int peer_upb = 2048;    // mailbox put / take launches: 16-byte units per workgroup and species (peer_prepare)
@@ -1308,6 +1313,9 @@ size_t persist_outbox_bytes(const Problem& p, int elem = 4)     // per band valu
     return (size_t)2 * (size_t)((p.n0 / TILE_B) * (p.W / TILE_B)) * PERSIST_BAND * (elem == 8 ? 16 : 8);
 }
 
+// placement words of the 32 x 32 resident forward (PersistArgs::xcc): one per tile, zeroed before the launch
+size_t persist_xcc_bytes(const Problem& p) { return align_up((size_t)((p.n0 / TILE_B) * (p.W / TILE_B)) * sizeof(unsigned), 16); }
+
 // can the tile sweep of this rollout run as one cooperative launch?  (everything the kernel assumes, checked here)
 template <typename T>
 bool persist_ok(const Problem& p, const unsigned char* mask, int t_top, int ngroups, hipStream_t st)
@@ -1436,7 +1444,8 @@ int persist_fits(F* k, int NT, size_t lds, int dev)
     return it->second;
 }
 
-// the per-device scratch of the launchers that bring no workspace: 256 B of sync words | outbox of `outbox_bytes`, allocated
+// the per-device scratch of the launchers that bring no workspace: 256 B of sync words | outbox of `outbox_bytes` (the caller
+// counts what it keeps behind its granules -- the resident forward's placement words, persist_xcc_bytes -- into them), allocated
 // once (sized for this launch or larger) and zeroed on the stream
 hipError_t persist_scratch(size_t outbox_bytes, hipStream_t st, pi_host::Resident& r)
 {
@@ -1707,10 +1716,12 @@ hipError_t launch_fwd_persist(T* frame_t0, int ngroups, const T* P, const Proble
     if (hipError_t e = allow_lds(k, lds)) return e;
     const int nb = persist_fits(k, NT, lds, r.dev);
     if (nb < 1 || (int64_t)grid > (int64_t)device_cu_count() * nb) return hipErrorCooperativeLaunchTooLarge;
-    if (hipError_t e = persist_scratch(persist_outbox_bytes(p, (int)sizeof(T)), st, r)) return e;
+    const size_t outbox_bytes = persist_outbox_bytes(p, (int)sizeof(T));                    // ... | placement words behind it
+    if (hipError_t e = persist_scratch(outbox_bytes + persist_xcc_bytes(p), st, r)) return e;
     long frame_stride = (long)(2 * p.n);
     persist_claim(p.opt, r);
     pi::PersistArgs pa = persist_args(r, reinterpret_cast<unsigned long long*>(r.scratch + 256), reinterpret_cast<unsigned*>(r.scratch), ngroups);
+    if (p.opt.handover_local) pa.xcc = reinterpret_cast<unsigned*>(r.scratch + 256 + outbox_bytes);
     void* args[] = {(void*)&frame_t0, (void*)&frame_stride, (void*)&P, (void*)&g, (void*)&pa};
     hipError_t e;
     if (p.opt.tile_persist == 2) {
@@ -3637,6 +3648,12 @@ int apply_option(Options& o, const char* key, long value)
         return 0;
     }
     if (!std::strcmp(key, "tile_xcd")) { o.tile_xcd = value != 0; return 0; }
+    if (!std::strcmp(key, "handover_local")) { o.handover_local = value != 0; return 0; }
+    if (!std::strcmp(key, "debug_handover_local")) {   // (per call only: set_option refuses it)
+        if (value < 0 || value > (1 << 24)) return PERCNN_PI_EINVAL;
+        o.debug_handover_local = (int)value;
+        return 0;
+    }
     if (!std::strcmp(key, "tile_by")) {
         if (value != 0 && value != 8 && value != 16 && value != 32) return PERCNN_PI_EINVAL;
         o.tile_by = (int)value;
@@ -3980,11 +3997,14 @@ namespace {
 //        height, lanes per tile workgroup of the adjoint (0: no tiles), the same three of the forward, 1 if the tile sweep of a
 //        long unmasked rollout runs as ONE persistent launch}; families: 0 direct, 1 2D tiles, 2 plane streaming, 3 3D bricks,
 //        4 advective block
+int debug_handover_local(const Problem& p, int elem_size, int* out);
+// query_ok: the caller's `out` may be the buffer of the per-call query debug_handover_local = N (percnn_pi_debug_plan only)
 template <typename T>
-int debug_plan_impl(int hc, int ndim, const int64_t* shape, const char* options, int* out)
+int debug_plan_impl(int hc, int ndim, const int64_t* shape, const char* options, int* out, bool query_ok = false)
 {
     Problem p;
     if (int rc = make_problem(hc, ndim, shape, false, p, options, false)) return rc;
+    if (p.opt.debug_handover_local) return query_ok ? debug_handover_local(p, (int)sizeof(T), out) : (int)PERCNN_PI_EINVAL;
     const int vec = pick_vec<T>(p, {});
     auto family = [&](bool adjoint, bool wgrad, int& planes) {
         planes = 1;
@@ -4054,6 +4074,30 @@ int debug_batch_plan_impl(int hc, int ndim, const int64_t* shape, int batch, con
     out[0] = fz ? 3 : 0; out[1] = az ? 3 : 0;
     out[2] = fz ? fz : 1; out[3] = az ? az : 1;              // (the batched direct kernels take one plane per pass)
     return 0;
+}
+
+// host-only: which band granules option handover_local publishes with plain stores (HandOver<>::pub_local): per tile one bitmap
+// of its 2 * BANDU granules in outbox order, bit i % 32 of word i / 32; `out` holds p.opt.debug_handover_local ints
+int debug_handover_local(const Problem& p, int elem_size, int* out)
+{
+    if (p.ndim != 2 || p.n0 % TILE_B || p.W % TILE_B) return PERCNN_PI_EINVAL;
+    const pi::TileGeom g = make_tile_geom(p, TILE_B);
+    const int tiles_y = (int)(p.n0 / TILE_B);
+    auto bitmaps = [&](auto ho) {
+        using HO = decltype(ho);
+        static_assert(2 * HO::BANDU % 32 == 0, "whole bitmap words per tile");
+        constexpr int WORDS = 2 * HO::BANDU / 32;
+        if ((int64_t)tiles_y * g.tiles_x * WORDS > (int64_t)p.opt.debug_handover_local) return (int)PERCNN_PI_EINVAL;   // `out` is too small
+        for (int ty = 0; ty < tiles_y; ++ty)
+            for (int tx = 0; tx < g.tiles_x; ++tx) {
+                int* w = out + (size_t)(ty * g.tiles_x + tx) * WORDS;
+                for (int i = 0; i < WORDS; ++i) w[i] = 0;
+                for (int i = 0; i < 2 * HO::BANDU; ++i)
+                    if (p.opt.handover_local && HO::pub_local(i, g, ty, tx, tiles_y)) w[i / 32] |= (int)(1u << (i % 32));
+            }
+        return 0;
+    };
+    return elem_size == 4 ? bitmaps(pi::HandOver<4, TILE_B, 2, 512>{}) : bitmaps(pi::HandOver<4, TILE_B, 1, 512>{});
 }
 
 }  // namespace
@@ -4181,7 +4225,7 @@ int percnn_pi_debug_batch_plan(int hc, int ndim, const int64_t* shape, int elem_
 int percnn_pi_debug_plan(int hc, int ndim, const int64_t* shape, int elem_size, const char* options, int* out)
 {
     if (!out || (elem_size != 4 && elem_size != 8)) return PERCNN_PI_EINVAL;
-    return elem_size == 4 ? debug_plan_impl<float>(hc, ndim, shape, options, out) : debug_plan_impl<double>(hc, ndim, shape, options, out);
+    return elem_size == 4 ? debug_plan_impl<float>(hc, ndim, shape, options, out, true) : debug_plan_impl<double>(hc, ndim, shape, options, out, true);
 }
 
 size_t percnn_pi_param_count(int hc) { return hc < -1 ? 0 : (size_t)pi::nparams(hc); }
@@ -4284,6 +4328,7 @@ size_t percnn_pi_rollout_bwd_workspace_bytes(int hc, int ndim, const int64_t* sh
 
 int percnn_pi_set_option(const char* key, long value)
 {
+    if (key && !std::strcmp(key, "debug_handover_local")) return PERCNN_PI_EINVAL;       // a query of one call, never a default
     std::lock_guard<std::mutex> lk(g_defaults_mu);
     return apply_option(g_defaults, key, value);
 }

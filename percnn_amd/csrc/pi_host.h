@@ -11,7 +11,9 @@ namespace pi_host {
 struct Resident {
     int dev = 0, slot = 0;
     volatile int* hs = nullptr;       // host-mapped status slot {roll call complete, step, task, aborted}
-    unsigned char* scratch = nullptr; // per-device scratch, zeroed on the stream: 256 B of sync words | granule outbox
+    unsigned char* scratch = nullptr; // per-device scratch, zeroed on the stream: 256 B of sync words | granule outbox |
+                                      // what the caller counted into outbox_bytes behind its granules (2D forward: one
+                                      // placement word per tile, option handover_local)
     unsigned long long timeout_ticks = 0, first_timeout_ticks = 0;   // bounds of a hand-over wait (100 MHz ticks): options persist_*_ms
 };
 

@@ -84,6 +84,8 @@ __device__ __forceinline__ int tile_of_block(int b, const TileGeom& g)
     const int ty = (xcd / g.rx) * g.rh + j / g.rw, tx = (xcd % g.rx) * g.rw + j % g.rw;
     return ty * g.tiles_x + tx;
 }
+// its inverse: the XCD (as a label: block % 8) the map hands tile (ty, tx) to; not for the identity map
+__host__ __device__ __forceinline__ int xcd_of_tile(int ty, int tx, const TileGeom& g) { return (ty / g.rh) * g.rx + tx / g.rw; }
 
 // window coordinates lie in [-2K, n + BX + 2K): one conditional add / subtract suffices for n >= BX + 2K (checked by the host)
 __device__ __forceinline__ int wrap1(int g, int n) { return g < 0 ? g + n : (g >= n ? g - n : g); }
@@ -1421,6 +1423,8 @@ struct PersistArgs {
                                    // second round trip)
     int masked;                    // 1: only the frames whose bit is set in `frames` carry a gradient (RCNN.observe's strided loss)
     unsigned frames[128];          // bit t of word t / 32: frame t carries a gradient (t < 4096)
+    unsigned* xcc;                 // 32 x 32 resident forward, option handover_local: one zeroed word per tile, where its workgroup
+                                   // leaves the id of the XCD it really runs on (handover_confirm); null: every granule is written through
 };
 
 // injection mask of the K steps below frame t: bit q = frame t - 1 - q carries a gradient
@@ -1566,7 +1570,7 @@ pi_adj2d_persist_kernel(const T* __restrict__ hframe_t, const T* __restrict__ gf
         adj_load_ops<T, K, BX, BY, NT, 0>(ops0, 0, hframe_t + gn - frame_stride, gmask & 1u ? gframe_t + gn - frame_stride : nullptr, g,
                                           ty0, tx0, &sa[0]);
         lds_barrier();                                     // sub-step K - 1 wrote buffer 0 (K even): everybody's strips are in
-        // ---- hand-over: publish my band, gather my ring ----
+        // ---- hand-over: publish my band, gather my ring (agent-scope stores: always written through, whatever handover_local says) ----
         const unsigned epoch = (unsigned)grp + 1u;
         gu64* half = outbox + (size_t)(epoch & 1u) * (size_t)ntiles * (2 * BANDH);
         gu64* mine = half + (size_t)tile * (2 * BANDH);
@@ -1688,11 +1692,14 @@ template <> struct GranuleIO<float> {
     __amdgpu_buffer_rsrc_t rs;
     __device__ __forceinline__ GranuleIO(void* outbox, size_t bytes) : rs(__builtin_amdgcn_make_buffer_rsrc(outbox, 0, (int)bytes, 0x00020000)) {}
     // src: the pair in LDS (8-byte aligned: even window column in either state buffer)
-    __device__ __forceinline__ void put(size_t idx, unsigned epoch, const float* src) const
+    // local: every reader runs under this XCD's L2 -- a plain store, the line stays there; else written through (sc1).  The policy
+    // is an immediate: a wave with both kinds issues two masked stores.  (soffset stays the constant 0: pi_res3d.h, hipcc hazard)
+    __device__ __forceinline__ void put(size_t idx, unsigned epoch, const float* src, bool local) const
     {
         const Pack<float, 2> v = ld<float, 2>(src);
         const pi_v4u w = {__builtin_bit_cast(unsigned, v.v[0]), epoch, __builtin_bit_cast(unsigned, v.v[1]), epoch};
-        __builtin_amdgcn_raw_buffer_store_b128(w, rs, (int)(idx * 16), 0, /*aux: sc1*/ 16);
+        if (local) __builtin_amdgcn_raw_buffer_store_b128(w, rs, (int)(idx * 16), 0, /*aux: plain*/ 0);
+        else __builtin_amdgcn_raw_buffer_store_b128(w, rs, (int)(idx * 16), 0, /*aux: sc1*/ 16);
     }
     __device__ __forceinline__ Raw get(size_t idx) const { return __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(idx * 16), 0, 16); }
     static __device__ __forceinline__ bool ok(Raw x, unsigned epoch) { return x.y == epoch && x.w == epoch; }
@@ -1709,11 +1716,12 @@ template <> struct GranuleIO<double> {
     __amdgpu_buffer_rsrc_t rs;
     // (the descriptor is built from kernel arguments only: wave-uniform by construction)
     __device__ __forceinline__ GranuleIO(void* outbox, size_t bytes) : rs(__builtin_amdgcn_make_buffer_rsrc(outbox, 0, (int)bytes, 0x00020000)) {}
-    __device__ __forceinline__ void put(size_t idx, unsigned epoch, const double* src) const
+    __device__ __forceinline__ void put(size_t idx, unsigned epoch, const double* src, bool local) const
     {
         const unsigned long long b = __builtin_bit_cast(unsigned long long, *src);
         const pi_v4u w = {(unsigned)b, epoch, (unsigned)(b >> 32), epoch};
-        __builtin_amdgcn_raw_buffer_store_b128(w, rs, (int)(idx * 16), 0, /*aux: sc1*/ 16);
+        if (local) __builtin_amdgcn_raw_buffer_store_b128(w, rs, (int)(idx * 16), 0, /*aux: plain*/ 0);
+        else __builtin_amdgcn_raw_buffer_store_b128(w, rs, (int)(idx * 16), 0, /*aux: sc1*/ 16);
     }
     __device__ __forceinline__ Raw get(size_t idx) const { return __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(idx * 16), 0, 16); }
     static __device__ __forceinline__ bool ok(Raw x, unsigned epoch) { return x.y == epoch && x.w == epoch; }
@@ -1872,7 +1880,7 @@ pi_adj2d_persist_small_kernel(const T* __restrict__ hframe_t, const T* __restric
                 const int sp = i / (OWN / GV), e = (i - sp * (OWN / GV)) * GV, y = e / BX, x = e - y * BX;
                 const T* src = b0 + sp * TL::PLANE + (HW + y) * LXW + HW + x;
                 if constexpr (PAIRS) {
-                    gio.put(halfu + (size_t)tile * (2 * OWN / GV) + (size_t)i, epoch, src);
+                    gio.put(halfu + (size_t)tile * (2 * OWN / GV) + (size_t)i, epoch, src, /*local*/ false);
                 } else {
                     const unsigned v = __builtin_bit_cast(unsigned, *src);
                     __hip_atomic_store(mine + i, ((unsigned long long)epoch << 32) | v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2025,6 +2033,57 @@ struct HandOver {
         else { const int m = e - 2 * HW * BX; y = HW + m / (2 * HW); const int c = m % (2 * HW); x = c < HW ? c : BX - 2 * HW + c; }
         return sp * TL::PLANE + (HW + y) * LXW + HW + x;
     }
+    // LOCAL band granules (option handover_local).  The tiles that gather band granule i into their rings, as bits
+    // (dy + 1) * 3 + (dx + 1) of the 3 x 3 neighbourhood: a side piece has one reader, an HW x HW corner block three
+    static __host__ __device__ __forceinline__ int pub_readers(int i)
+    {
+        const int e = (i % BANDU) * GV;
+        int y, x;                                          // inverse of band_index
+        if (e < HW * BX) { y = e / BX; x = e - y * BX; }
+        else if (e < 2 * HW * BX) { const int m = e - HW * BX; y = BX - HW + m / BX; x = m % BX; }
+        else { const int m = e - 2 * HW * BX; y = HW + m / (2 * HW); const int c = m % (2 * HW); x = c < HW ? c : BX - 2 * HW + c; }
+        const int dy = y < HW ? -1 : (y >= BX - HW ? 1 : 0), dx = x < HW ? -1 : (x >= BX - HW ? 1 : 0);
+        int r = 0;
+        if (dy) r |= 1 << ((dy + 1) * 3 + 1);
+        if (dx) r |= 1 << (3 + dx + 1);
+        if (dy && dx) r |= 1 << ((dy + 1) * 3 + dx + 1);
+        return r;
+    }
+    // the neighbours (same bits, periodic wrap) that the rectangle map places on the XCD of tile (tyi, txi); identity map: none
+    static __host__ __device__ __forceinline__ int same_xcd(const TileGeom& g, int tyi, int txi, int tiles_y)
+    {
+        if (g.rx == 0) return 0;
+        const int me = xcd_of_tile(tyi, txi, g);
+        int r = 0;
+        for (int dy = -1; dy <= 1; ++dy)
+            for (int dx = -1; dx <= 1; ++dx) {
+                if (!dy && !dx) continue;
+                const int ny = (tyi + dy + tiles_y) % tiles_y, nx = (txi + dx + g.tiles_x) % g.tiles_x;
+                if (xcd_of_tile(ny, nx, g) == me) r |= 1 << ((dy + 1) * 3 + dx + 1);
+            }
+        return r;
+    }
+    // band granule i of tile (tyi, txi) is local iff EVERY tile that reads it runs on the publisher's XCD: it is then published
+    // with a plain store -- the line stays in that XCD's L2, which serves the readers' sc1 loads -- and only the others are written
+    // through the fabric (at 512^2, 8 x 4 tiles per XCD: 76 % of a tile's band on average, all of an interior tile's).  The host
+    // evaluates this text (percnn_pi_debug_plan, debug_handover_local); the kernels take the two factors apart, because a neighbour counts
+    // only once its placement word has confirmed the map (PUB_* below).
+    static __host__ __device__ __forceinline__ bool pub_local(int i, const TileGeom& g, int tyi, int txi, int tiles_y)
+    {
+        return (pub_readers(i) & ~same_xcd(g, tyi, txi, tiles_y)) == 0;
+    }
+    // entry of the publish table: -1 (no granule), or LDS position | readers << 16 | PUB_LOCAL.  The prologue writes the
+    // readers the map places on this XCD (PUB_NEVER otherwise: bit 4, the tile itself, is never confirmed); before the first
+    // publish handover_confirm turns them into the PUB_LOCAL bit, which is all a publish looks at.
+    static constexpr int PUB_POS = 0xFFFF, PUB_READERS = 0x1FF, PUB_NEVER = 1 << 4, PUB_LOCAL = 1 << 30;
+    static_assert(2 * TL::PLANE <= PUB_POS, "an LDS position fits the low half of a table entry");
+    static __device__ __forceinline__ int pub_entry(int i, int same)
+    {
+        const int pl = pub_pos(i);
+        if (pl < 0) return -1;
+        const int rd = pub_readers(i);
+        return pl | ((rd & ~same) == 0 ? rd : PUB_NEVER) << 16;
+    }
     // ring granule r: gl = LDS position of its first value (-1: none), gs = granule index inside a parity half of the outbox
     static __device__ __forceinline__ void gat_pos(int r, const TileGeom& g, int ty0, int tx0, int tiles_y, int& gl, int& gs)
     {
@@ -2042,6 +2101,43 @@ struct HandOver {
         gs = (nty * g.tiles_x + ntx) * (2 * BANDU) + sp * BANDU + band_index<BX, HW>(ly, lx) / GV;
     }
 };
+
+// PLACEMENT IS VERIFIED, NOT ASSUMED.  "Block b runs on XCD b % 8" is an observation about the dispatcher, good enough to choose a
+// tile map for speed; a plain granule store that only a reader under the same L2 can see makes it a matter of correctness.  So every
+// workgroup leaves the hardware id of its XCD (HW_REG_XCC_ID, bits 3:0) in its tile's placement word at start (handover_announce,
+// written through), and before its FIRST publish -- one group later -- reads the words of its eight neighbours: a neighbour is
+// local only if its word has been written and equals this workgroup's own id.  A granule keeps its plain store only if all its
+// readers passed; the others are written through for the whole launch (a slot's policy never changes during a launch).
+// Whatever the placement, the trajectory is the same bit for bit: the policy decides how a granule travels, not what it holds.
+__device__ __forceinline__ unsigned handover_xcc_word()
+{
+    return 0x80000000u | (unsigned)__builtin_amdgcn_s_getreg(/*hwreg(HW_REG_XCC_ID, 0, 4)*/ 20 | (3 << 11));
+}
+__device__ __forceinline__ void handover_announce(const PersistArgs& pa, int tile)
+{
+    if (pa.xcc) __hip_atomic_store(pa.xcc + tile, handover_xcc_word(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// the lane's NPUB entries of the publish table: readers -> PUB_LOCAL.  Every lane rewrites its own entries (no barrier).
+template <typename HO, int NT>
+__device__ __forceinline__ void handover_confirm(const PersistArgs& pa, const TileGeom& g, int tyi, int txi, int tiles_y, int* tab_pub)
+{
+    int ok = 0;
+    if (pa.xcc) {
+        const unsigned me = handover_xcc_word();
+#pragma unroll
+        for (int b = 0; b < 9; ++b) {
+            if (b == 4) continue;
+            const int ny = (tyi + b / 3 - 1 + tiles_y) % tiles_y, nx = (txi + b % 3 - 1 + g.tiles_x) % g.tiles_x;
+            const unsigned w = __hip_atomic_load(pa.xcc + ny * g.tiles_x + nx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ok |= (w == me ? 1 : 0) << b;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < HO::NPUB; ++q) {
+        const int e = tab_pub[q * NT + (int)threadIdx.x];
+        if (e >= 0) tab_pub[q * NT + (int)threadIdx.x] = (e & HO::PUB_POS) | ((((e >> 16) & HO::PUB_READERS) & ~ok) == 0 ? HO::PUB_LOCAL : 0);
+    }
+}
 
 // int rows of NT the split sweep keeps in LDS behind the moments: 13 of hand-over tables + 6 of strip geometry (+ the abort word)
 constexpr int PERSIST_SPLIT_TABLE_ROWS = 19;
@@ -2373,10 +2469,12 @@ pi_adj2d_persist_split_kernel(const T* __restrict__ hframe_t, const T* __restric
         // ---- publish my band (the border 2K points of the tile, complete since the barrier that ended P5) ----
         const unsigned ep1 = (unsigned)grp + 1u;
         const size_t mine = (size_t)(ep1 & 1u) * (size_t)ntiles * (2 * BANDU) + (size_t)tile * (2 * BANDU);
+        // (written through, all of it: with local granules -- option handover_local, the resident forward -- the sweep's ring landed
+        // no earlier, 3.16 -> 3.24 us into the group, and the two registers the choice cost made every pass slower: docs/NOTEBOOK.md section 22)
 #pragma unroll
         for (int q = 0; q < NPUB; ++q) {
             const int pl = tab_pub[q * NT + (int)threadIdx.x];
-            if (pl >= 0) gio.put(mine + (size_t)((int)threadIdx.x + q * NT), ep1, b0 + pl);
+            if (pl >= 0) gio.put(mine + (size_t)((int)threadIdx.x + q * NT), ep1, b0 + pl, /*local*/ false);
         }
         PI_PSTAMP(8);
         // (no barrier: the next pass, P0, reads b0 -- complete -- and writes b1's centre, which nobody reads any more)
@@ -2614,6 +2712,7 @@ pi_fwd2d_persist_kernel(T* __restrict__ frames /* frame t0; t0+1 .. t0 + K * ngr
         *wg_abort = 0;
         const unsigned n = __hip_atomic_fetch_add(pa.sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
         if (n == (unsigned)ntiles && pa.host) __hip_atomic_store(pa.host, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        handover_announce(pa, tile);
     }
     tab_geo[0 * NT + (int)threadIdx.x] = persist_pass_geo<K, BX, BY, NT, 0>(g, ty0, tx0);
     tab_geo[1 * NT + (int)threadIdx.x] = persist_pass_geo<K, BX, BY, NT, 1>(g, ty0, tx0);
@@ -2621,8 +2720,9 @@ pi_fwd2d_persist_kernel(T* __restrict__ frames /* frame t0; t0+1 .. t0 + K * ngr
     tab_geo[3 * NT + (int)threadIdx.x] = persist_pass_geo<K, BX, BY, NT, 3>(g, ty0, tx0);
     tab_geo[4 * NT + (int)threadIdx.x] = persist_pass_geo<K, BX, BY, NT, 4>(g, ty0, tx0);
     tab_geo[5 * NT + (int)threadIdx.x] = persist_pass_geo<K, BX, BY, NT, 5>(g, ty0, tx0);
+    const int same = pa.xcc ? HO::same_xcd(g, tyi, txi, tiles_y) : 0;  // neighbours the map places on my XCD (handover_local)
 #pragma unroll
-    for (int q = 0; q < NPUB; ++q) tab_pub[q * NT + (int)threadIdx.x] = HO::pub_pos((int)threadIdx.x + q * NT);
+    for (int q = 0; q < NPUB; ++q) tab_pub[q * NT + (int)threadIdx.x] = HO::pub_entry((int)threadIdx.x + q * NT, same);
 #pragma unroll
     for (int q = 0; q < NGAT; ++q) {
         int gl, gs;
@@ -2778,10 +2878,11 @@ pi_fwd2d_persist_kernel(T* __restrict__ frames /* frame t0; t0+1 .. t0 + K * ngr
         // ---- publish my band of level 4 (complete since the barrier) ----
         const unsigned ep1 = (unsigned)grp + 1u;
         const size_t mine = (size_t)(ep1 & 1u) * (size_t)ntiles * (2 * BANDU) + (size_t)tile * (2 * BANDU);
+        if (grp == 0) handover_confirm<HO, NT>(pa, g, tyi, txi, tiles_y, tab_pub);    // which neighbours share my L2: once, now
 #pragma unroll
         for (int q = 0; q < NPUB; ++q) {
             const int pl = tab_pub[q * NT + tid];
-            if (pl >= 0) gio.put(mine + (size_t)(tid + q * NT), ep1, b0 + pl);
+            if (pl >= 0) gio.put(mine + (size_t)(tid + q * NT), ep1, b0 + (pl & HO::PUB_POS), (pl & HO::PUB_LOCAL) != 0);
         }
         PI_PSTAMP(8);
         // (no barrier: P0 reads b0 -- complete -- and writes b1 inside I_0's square; the store of level 3 from b1 was issued before
@@ -2914,7 +3015,7 @@ pi_fwd2d_persist_small_kernel(T* __restrict__ frames /* frame t0; t0+1 .. t0 + K
                 const int sp = i / (OWN / GV), e = (i - sp * (OWN / GV)) * GV, y = e / BX, x = e - y * BX;
                 const T* src = b0 + sp * TL::PLANE + (HW + y) * LXW + HW + x;
                 if constexpr (PAIRS) {
-                    gio.put(halfu + (size_t)tile * (2 * OWN / GV) + (size_t)i, epoch, src);
+                    gio.put(halfu + (size_t)tile * (2 * OWN / GV) + (size_t)i, epoch, src, /*local*/ false);
                 } else {
                     const unsigned v = __builtin_bit_cast(unsigned, *src);
                     __hip_atomic_store(mine + i, ((unsigned long long)epoch << 32) | v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

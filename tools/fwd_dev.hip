@@ -2,6 +2,8 @@
 // headline geometry (512^2, float32 pre-contracted block, K = 4 steps per launch, XCD-aware tile map) and their whole trajectory
 // is checked bit for bit against the shipped variant's; -DPI_TILE_TIMING adds the device timeline of a launch.  Not part of the product; build and run on the GPU box:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -o fwd_dev tools/fwd_dev.hip && ./fwd_dev [T=1000] [reps=5]
+// The resident forward runs both ways of option handover_local (PersistArgs::xcc null | set); -DPI_PERSIST_STAMPS=<group> prints
+// the group timeline of each.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -94,64 +96,77 @@ int main(int argc, char** argv)
         constexpr int NT = 512, BAND = 2 * (B * B - (B - 16) * (B - 16));
         const int tiles = (N / B) * (N / B), ngroups = T / K;
         const size_t outbox_bytes = (size_t)2 * tiles * BAND * sizeof(unsigned long long);
-        unsigned long long* outbox; unsigned* sync; int* host;
+        unsigned long long* outbox; unsigned *sync, *xcc; int* host;
         CK(hipMalloc(&outbox, outbox_bytes));
         CK(hipMalloc(&sync, 64));
+        CK(hipMalloc(&xcc, tiles * sizeof(unsigned)));      // placement words (handover_local)
         CK(hipHostMalloc(&host, 64, hipHostMallocMapped | hipHostMallocCoherent));
         auto* kp = pi::pi_fwd2d_persist_kernel<float, K, B, B, NT, 1>;
         const size_t lds_p = pi::tile_state_bytes<float, K, B, B>() + (size_t)pi::PERSIST_SPLIT_TABLE_ROWS * NT * sizeof(int) + 16;
         CK(hipFuncSetAttribute(reinterpret_cast<const void*>(kp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
-        auto run_p = [&]() {
+        auto run_p = [&](bool local) {
             CK(hipMemsetAsync(outbox, 0, outbox_bytes, st));
             CK(hipMemsetAsync(sync, 0, 64, st));
+            CK(hipMemsetAsync(xcc, 0, tiles * sizeof(unsigned), st));
             host[0] = 0; host[3] = 0;
             pi::PersistArgs pa{};
             pa.outbox = outbox; pa.sync = sync; pa.host = host; pa.ngroups = ngroups;
             pa.timeout_ticks = 200000000ull; pa.first_timeout_ticks = 200000000ull;
+            pa.xcc = local ? xcc : nullptr;
             hipLaunchKernelGGL(kp, dim3(tiles), dim3(NT), lds_p, st, dB, fs, dP, g, pa);
         };
-        run_p();
+        run_p(false);
         check("persistent forward");
         std::printf("  host state: roll call %d, aborted %d\n", host[0], host[3]);
+        run_p(true);
+        check("... local granules");
+        std::printf("  host state: roll call %d, aborted %d\n", host[0], host[3]);
         for (int rep = 0; rep < reps; ++rep) {
-            float ms0, ms1;
+            float ms0, ms1, ms2;
             CK(hipEventRecord(e0, st)); launch<512>(dB, fs, dP, g, T, st); CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
             CK(hipEventElapsedTime(&ms0, e0, e1));
-            CK(hipEventRecord(e0, st)); run_p(); CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
+            CK(hipEventRecord(e0, st)); run_p(false); CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
             CK(hipEventElapsedTime(&ms1, e0, e1));
-            std::printf("persistent round %d: us per group of %d steps: launch per group %.2f | one resident launch %.2f   (us per step %.3f | %.3f)\n",
-                        rep, K, 1e3 * ms0 / ngroups, 1e3 * ms1 / ngroups, 1e3 * ms0 / T, 1e3 * ms1 / T);
+            CK(hipEventRecord(e0, st)); run_p(true); CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
+            CK(hipEventElapsedTime(&ms2, e0, e1));
+            std::printf("persistent round %d: us per group of %d steps: launch per group %.2f | one resident launch %.2f | with local granules %.2f   (us per step %.3f | %.3f | %.3f)\n",
+                        rep, K, 1e3 * ms0 / ngroups, 1e3 * ms1 / ngroups, 1e3 * ms2 / ngroups, 1e3 * ms0 / T, 1e3 * ms1 / T, 1e3 * ms2 / T);
         }
-    }
 #ifdef PI_PERSIST_STAMPS
-    {   // device timeline of one group of the resident launch: medians over the workgroups of wave 0's / wave 7's stamps
-        static long long hs[256 * 8 * 16];
-        CK(hipMemcpyFromSymbol(hs, HIP_SYMBOL(pi::pi_persist_stamps), sizeof(hs)));
-        const char* names[9] = {"group start", "P0", "P1 computed", "ring in LDS", "P2", "P3", "P4", "P5", "published"};
-        for (int w = 0; w < 8; w += 7) {
-            std::printf("wave %d:", w);
-            for (int i = 0; i < 9; ++i) {
-                std::vector<double> v;
-                for (int b = 0; b < 256; ++b) v.push_back((hs[(b * 8 + w) * 16 + i] - hs[(b * 8 + 0) * 16 + 0]) * 0.01);
-                std::sort(v.begin(), v.end());
-                std::printf(" %s %.2f", names[i], v[128]);
+        for (int local = 0; local < 2; ++local) {
+            // device timeline of one group of the resident launch, written through and with local granules: medians over the
+            // workgroups of wave 0's / wave 7's stamps
+            run_p(local != 0);
+            CK(hipStreamSynchronize(st));
+            std::printf("handover_local = %d\n", local);
+            static long long hs[256 * 8 * 16];
+            CK(hipMemcpyFromSymbol(hs, HIP_SYMBOL(pi::pi_persist_stamps), sizeof(hs)));
+            const char* names[9] = {"group start", "P0", "P1 computed", "ring in LDS", "P2", "P3", "P4", "P5", "published"};
+            for (int w = 0; w < 8; w += 7) {
+                std::printf("wave %d:", w);
+                for (int i = 0; i < 9; ++i) {
+                    std::vector<double> v;
+                    for (int b = 0; b < 256; ++b) v.push_back((hs[(b * 8 + w) * 16 + i] - hs[(b * 8 + 0) * 16 + 0]) * 0.01);
+                    std::sort(v.begin(), v.end());
+                    std::printf(" %s %.2f", names[i], v[128]);
+                }
+                std::printf("\n");
             }
-            std::printf("\n");
-        }
-        // what pass P3 (A_1: one strip on waves 0-3, the rest of level 1 stored by waves 4-7) is made of, per wave: us since the
-        // barrier that ended P2 -- frame stores issued | strip computed and stored to LDS | through the barrier
-        for (int w = 0; w < 8; ++w) {
-            std::printf("P3 wave %d:", w);
-            for (int i : {9, 10, 5}) {
-                std::vector<double> v;
-                for (int b = 0; b < 256; ++b) v.push_back((hs[(b * 8 + w) * 16 + i] - hs[(b * 8 + w) * 16 + 4]) * 0.01);
-                std::sort(v.begin(), v.end());
-                std::printf("  %s %.2f", i == 9 ? "stores issued" : i == 10 ? "strip done" : "barrier passed", v[128]);
+            // what pass P3 (A_1: one strip on waves 0-3, the rest of level 1 stored by waves 4-7) is made of, per wave: us since the
+            // barrier that ended P2 -- frame stores issued | strip computed and stored to LDS | through the barrier
+            for (int w = 0; w < 8; ++w) {
+                std::printf("P3 wave %d:", w);
+                for (int i : {9, 10, 5}) {
+                    std::vector<double> v;
+                    for (int b = 0; b < 256; ++b) v.push_back((hs[(b * 8 + w) * 16 + i] - hs[(b * 8 + w) * 16 + 4]) * 0.01);
+                    std::sort(v.begin(), v.end());
+                    std::printf("  %s %.2f", i == 9 ? "stores issued" : i == 10 ? "strip done" : "barrier passed", v[128]);
+                }
+                std::printf("\n");
             }
-            std::printf("\n");
         }
-    }
 #endif
+    }
     // the same 250 launches as ONE graph launch (does a captured chain shorten the dependent-kernel boundary?)
     {
         hipGraph_t graph; hipGraphExec_t exec;
