@@ -6,6 +6,7 @@ update, their adjoint, and the T-step rollout -- as hand-written HIP kernels beh
 (``include/percnn_pi.h``), with drop-in ``RCNNCell`` / ``RCNN`` modules on top.
 
 Layout:  ``csrc/`` HIP kernels + the C-ABI translation units (pi_abi.hip: base block, slabs, physics residual;
+pi_host.hip: the host runtime they share -- option table, launch geometry, residency guard -- no kernel;
 pi_s1_abi.hip: Stage-1 block on the matrix cores; pi_up3d_abi.hip: 3D IC-generator contraction; pi_disc_abi.hip: Stage-2 library moments; pi_lib_abi.hip: library cell) ->
 ``libpercnn_pi.so``;  ``_lib`` ctypes binding + build;  ``ops`` the registered ``torch.ops.percnn.*`` operators;
 ``functional`` raw calls + autograd front-end;  ``modules`` the reference's

@@ -19,6 +19,7 @@ _INC = os.path.join("..", "..", "include")
 # translation unit -> headers it depends on (all under csrc/ unless a path is given)
 SOURCES = {
     "pi_abi.hip": ["pi_kernels.h", "pi_tile2d.h", "pi_stream3d.h", "pi_brick3d.h", "pi_res3d.h", "pi_adv.h", "pi_contract.h", "pi_peer.h", "pi_device.h", "pi_host.h", os.path.join(_INC, "percnn_pi.h")],
+    "pi_host.hip": ["pi_host.h", "pi_kernels.h", "pi_device.h", os.path.join(_INC, "percnn_pi.h")],    # host runtime: no kernel
     "pi_s1_abi.hip": ["pi_s1.h", "pi_device.h", "pi_host.h", os.path.join(_INC, "percnn_pi.h"), os.path.join(_INC, "percnn_pi_stage1.h")],
     "pi_up3d_abi.hip": ["pi_up3d.h", "pi_device.h", os.path.join(_INC, "percnn_pi.h")],
     "pi_disc_abi.hip": ["pi_disc.h", os.path.join(_INC, "percnn_pi.h"), os.path.join(_INC, "percnn_pi_discovery.h")],

@@ -1,6 +1,8 @@
 // pi_abi.hip -- C-ABI entry points of libpercnn_pi.so (declared in include/percnn_pi.h).
 // Host side only validates arguments, picks a kernel instantiation and enqueues launches on the
 // caller's stream: no allocation, no synchronisation, no exceptions across the boundary.
+// What launches nothing and names no kernel -- the option table, Problem and the geometry of the direct kernels, the side
+// stream, the residency guard -- is the host runtime, pi_host.h / pi_host.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -8,10 +10,6 @@
 #include <chrono>
 #include <cstdio>
 #include <cstring>
-#include <map>
-#include <mutex>
-#include <thread>
-#include <tuple>
 #include <vector>
 
 #include "../../include/percnn_pi.h"
@@ -25,361 +23,17 @@
 #include "pi_adv.h"
 #include "pi_host.h"
 
+using namespace pi_host;
+
 namespace {
 
 using pi::Geom;
-
-struct Options {
-    int block = 256;
-    int vec = 0;            // 0 = widest legal (16 B per lane); 1/2/4 = cap (tuning aid)
-    int wgrad_blocks = 1024;
-    int tile = 1;           // 2D: temporally blocked LDS kernels where the shape allows
-    int tile_k = 4;         // sub-steps per launch (2 or 4)
-    int tile_nt = 512;      // workgroup size of the tile kernels (256 or 512)
-    int stream3d = 1;       // 3D: plane-streaming kernels where the shape allows (W = 64*VEC)
-    int tile_fuse = 1;      // 2D tile sweep (float32 poly, K = 4, 32x32 tiles, 512 threads): reduce the 20 coefficient moments
-                            // inside the sweep launches and keep only the hand-over adjoint frames (no moments pass)
-    int bwd_cpl = 2;        // direct adjoint kernel: chunks per lane (grid-stride) while >= 512 workgroups remain; measured
-                            // 1 -> 2: 128^3 22.9 -> 21.6, 192^3 76.9 -> 64.7, 2048^2 43.8 -> 37.9 us per fused backward step
-    int zc = 8;             // planes per workgroup of the streaming kernels
-    int overlap = 0;        // 1: run the gradient reduction on a side stream, chunk by chunk, under the sweep (measured: no gain on MI355X)
-    int overlap_chunk = 128; // time steps per chunk
-    int fuse_wgrad = 2;     // rollout sweep with the fused per-step kernel (all gradients reduced in the sweep launches)
-                            // instead of sweep + one time-parallel reduction: 0 never, 1 whenever the per-step direct kernels
-                            // sweep, 2 = where it measured faster: float32 poly mode on the direct-kernel path (128^3:
-                            // 26.0 -> 23.3 us per step, 2048^2: 45.4 -> 39.8; fp64 and the factored mode lose)
-    int skip_wgrad = 0;     // diagnostics: rollout_bwd runs the adjoint sweep only (bench uses it to time the sweep alone)
-    int tile_xcd = 1;       // XCD-aware block -> tile map of the 2D tile kernels (0 = identity)
-    int handover_local = 1; // 32 x 32 resident FORWARD: band granules whose readers all run on the publisher's XCD (by that map,
-                            // confirmed by the hardware's XCC ids at run time) are published with plain stores and stay in the
-                            // XCD's L2; 0: every granule is written through (the resident sweeps always do: measured, no gain)
-    int debug_handover_local = 0;   // per call, percnn_pi_debug_plan only: N > 0 = write the bitmaps of local band granules into
-                                    // an `out` of N ints instead of the plan (the entry-point count is pinned, hence no entry of its own)
-    int tile_by = 0;        // tile height of the 2D tile kernels: 32, 16, or 0 = by grid size (see tile_by_for)
-    int slab_fused_put_adj = 0; // ... and the adjoint sweep's faces by the sweep launch (to self: no gain; across xGMI: bench.py decides)
-    int peer_upb = 2048;    // mailbox put / take launches: 16-byte units per workgroup and species (peer_prepare)
-    int peer_upb_take = 0;  // ... of the take alone (0 = as the put)
-    int tile_persist = 2;   // float32 poly blocks on whole 32 x 32 tiles, <= one tile per CU: the whole tile sweep
-                            // of a rollout in ONE launch of resident workgroups (pi_adj2d_persist_kernel).  2 = plain launch (one
-                            // workgroup fills a CU's LDS, so a grid of <= #CUs is resident as long as no OTHER kernel holds whole
-                            // CUs: calls on other streams of this process are detected and take the launch-per-group path;
-                            // processes that share one GPU must set 0); 1 = cooperative launch (residency guaranteed by the
-                            // runtime, but ~0.4 ms per launch on ROCm 7.2: slower than what it saves at T = 1000); 0 = off
-    int persist_handshake = 1;  // persistent sweep: the entry point waits (host spin on a host-mapped word, no stream sync) until
-                            // the launch reports that every workgroup is resident -- or that it aborted, in which case the
-                            // launch-per-group sweep is enqueued in the same call and the persistent path is switched off for
-                            // this device (percnn_pi_persist_status).  0: no wait; an aborted launch is reported by the NEXT
-                            // entry point (PERCNN_PI_EASYNC) instead
-    int fwd_small_half = 1;     // small-tile resident forward (32 x 8 tiles) on half-strips: 512 lanes, two waves per SIMD
-    int adj_small_half = 1;     // small-tile resident sweep (32 x 8 tiles) on half-strips: 512 lanes, two waves per SIMD
-    // small-tile resident kernels: 64-clock units between publish and the first ring request (PersistArgs::pause); -1 = by tile count.
-    // Re-swept with the half-strip / pair-granule kernels of round 6 (us per step at pause 12 | 16 | 20 | 24 | 28 | 32):
-    //   forward  100^2 (52 tiles) .873 .867 .821 .819 .843 .871 | 160^2 .921 .916 .901 .886 .874 .874 | 256^2 .978 .941 .921 .865 .851 .878
-    //   sweep    100^2 1.159 1.145 1.123 1.130 1.155 1.182 | 160^2 1.216 1.206 1.201 1.183 1.179 1.206 | 256^2 1.539 1.517 1.480 1.432 1.373 1.377
-    int adj_small_pause = -1;   // -> 20 up to 64 tiles, 28 above
-    int fwd_small_pause = -1;   // -> 24 up to 64 tiles, 28 above
-    int persist_small = 1;      // the 32 x 8-tile regime (grids below ~300^2, split schedule) as one persistent launch too
-    int fwd_persist_per_cu = 1; // ... on grids of up to this many tiles per CU (1 or 2)
-    int fwd_persist_f64 = 1;    // ... float64 too (lambda-omega; 16-byte granules)
-    int adj_persist_f64 = 1;    // the float64 tile SWEEP as one resident launch as well (split flavour, moments in shared LDS rows)
-    int fwd_persist = 1;        // the FORWARD rollout of such a grid as one launch of resident workgroups too (pi_fwd2d_persist_kernel;
-                            // same residency check / abort / fallback; its granule outbox is a per-device scratch of the library)
-    int persist_split = 1;      // persistent sweep: 1 = split flavour (pi_adj2d_persist_split_kernel: the halo-independent
-                            // "pyramid" of the next group runs while the granules of the hand-over travel), 0 = round 3's kernel
-    int persist_timeout_ms = 2000;       // bound of one hand-over wait inside the persistent sweep
-    int persist_first_timeout_ms = 100;  // ... of the first one (residency check)
-    int tile_wide = 3;      // float32 poly blocks: 3 = 32x40 / 40x40 tiles where they keep the grid in one round (tile_wide_for),
-                            // 0 = never, 1 / 2 = force 32x40 / 40x40
-    int fwd_blocks = 0;     // direct forward kernel: grid cap (0 = none; measured: a bounded persistent grid loses, 384^3 376 -> 416 us)
-    int xcd_window = 0;     // direct forward kernel: XCD-contiguous block remap inside windows of this many blocks (0 = whole grid)
-    int block_small = 1;    // direct kernels: 64-thread workgroups while 256-thread ones would leave CUs idle (small grids)
-    int rz = 0;             // direct 3D kernels, pre-contracted blocks: planes per workgroup pass sharing their plane neighbours in
-                            // registers (1, 2, 4; 0 = by size, see direct_rz)
-    int l2_tile_kb = 128;   // direct 3D kernels: y-tile of a plane (both species, KiB) whose five stencil planes stay in the L2
-                            // (0 = whole planes, the pre-round-2 order): see set_blockmap
-    int l2_tile_min_kb = 1536;  // ... applied once four neighbour planes x two species exceed this many KiB (0: always; tests)
-    int peer_wire_us = 0;   // MEASUREMENT AID: every put over the peer mailboxes holds its arrival flag back this many microseconds
-                            // (pi_peer.h PeerXfer::wire_ticks): a stand-in for the link time of an xGMI hop when the ring runs to self
-    int slab_put_blocks = 16; // ... workgroups per direction of that fused put (a multiple of 4)
-    int slab_fused_put = 1; // native slab rollouts over the peer mailboxes: the step kernel that writes a frame about to be exchanged
-                            // also carries its faces into the neighbours' mailboxes (pi_peer.h "put fused into the step kernel")
-    int slab_local_index = 1;   // native slab rollouts of ONE rank (ring == NULL): 1 = the periodic wrap is resolved by index inside the
-                            // step launches (no face copies, no recomputed halo planes: 32 x 256^2, us per fwd+bwd step: 34.6 with one
-                            // copy launch per exchange -> see profiles/r05_slab_local_wrap.txt); 0 = by face copies into the halo
-                            // planes -- the launches of a multi-rank run minus its transport (what bench.py's compute / exchange
-                            // split times; also selected per call by bit 1 of the `overlap` argument)
-    int slab_wide_adjoint = 0;  // native slab backward over RCCL: one exchange per TWO adjoint steps (4 adjoint planes + 2 dL/dtraj
-                            // planes per side in one group call), the 2-plane strips next to the faces recomputed locally.
-                            // Built for VERDICT r1 #3, measured SLOWER on MI355X (RCCL to self, 32 x 256^2 slab: 74.0 -> 79.6 us
-                            // per fwd+bwd step): an ncclGroup costs per operation (~3 us each of its 8 sends / receives), not per
-                            // call, so 16 operations every second step save nothing and the two strip launches come on top
-    int lane_x = 0;         // direct kernels: log2 of the lanes along x per row segment (2..6), 0 = fewest idle lanes (set_blockmap),
-                            // -1 = the pre-round-2 rule (next power of two >= chunks per row)
-    int brick3d = 1;        // 3D: brick kernels (pi_brick3d.h) for one-step launches where the shape allows: 0 never, 1 by
-                            // size (brick_ok), 2 whenever eligible
-    int res3d = 1;          // 3D float32 pre-contracted blocks: the whole reverse sweep of a rollout as ONE launch of resident
-                            // workgroups with the adjoint state in LDS (pi_res3d.h; round 6): 0 never, 1 where it measured faster than
-                            // the brick sweep (whole 16 x 16 x 32 blocks, at least 7/8 of the CUs busy: 128^3, 112 x 128^2), 2 on
-                            // every grid of whole blocks that fits the device (tests)
-    int brick_rz = 0;       // planes per brick (1, 2, 4; 0 = by size)
-    int brick_xcd = 1;      // brick kernels: XCD regions split in y as well as in z where the counts divide (BrickGeom::xny):
-                            // 0 never, 1 where it measured no worse (make_brick_geom), 2 always
-    int brick_xny = 0;      // ... 0 = regions sized by the L2 (make_brick_geom), 1 = contiguous plane ranges, 2 / 4 / 8 = force that many
-                            // row strips (tuning aid); -1 = the round-4 rule for forward steps of >= 8 M points (contiguous)
-    int brick_wide = 1;     // 3D rows of 65 .. 128 chunks on 512-lane bricks (0: the direct kernels, as before round 4)
-    int brick_nt = 0;       // lanes per brick workgroup: 512 = the wide flavour (pre-contracted blocks; see brick_nt_for), else 256
-    int brick_wgs = 0;      // adjoint brick kernel: resident workgroups per CU that walk the bricks (0 = 4 / 2 by planes per brick)
-    int brick_wt = 1;       // brick kernels store their output frame write-through (BrickGeom::wt)
-    int lds_pad = 0;        // extra dynamic LDS per workgroup (bytes): lowers workgroups/CU so that a
-                            // small grid is spread over all CUs instead of being packed onto a few
-};
-// The ONLY process-wide mutable state of the library: the table of tuning defaults.  Every entry point copies it once,
-// under the lock, into its Problem (p.opt), overlays the call's own overrides ("key=value,..." of the *_opt entry
-// points) and reads nothing else afterwards -- concurrent calls with different options do not interact.
-Options g_defaults;
-std::mutex g_defaults_mu;
-int apply_option(Options& o, const char* key, long value);
-int apply_overrides(Options& o, const char* spec);
-void persist_reset();
-int persist_async_error();
 
 template <typename F>
 hipError_t allow_lds(F* f, size_t bytes)
 {
     if (bytes <= 64 * 1024) return hipSuccess;
     return hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
-// One side stream + a small event ring per host thread and device for sweep || reduction overlap (created lazily, released when
-// the thread ends: applications that churn worker threads do not accumulate streams; fork/join through events only -- no host
-// synchronisation).
-struct SideStream {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[8] = {};
-    hipEvent_t done = nullptr;
-    int next = 0;
-    bool ok = false;
-    SideStream() = default;
-    SideStream(const SideStream&) = delete;
-    SideStream& operator=(const SideStream&) = delete;
-    ~SideStream()
-    {
-        // (thread-local destructors of the main thread run inside exit() before the runtime's own teardown; errors are ignored --
-        // work still queued on the stream completes, hipStreamDestroy only releases the handle)
-        for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (done) (void)hipEventDestroy(done);
-        if (stream) (void)hipStreamDestroy(stream);
-        (void)hipGetLastError();
-    }
-};
-SideStream* side_stream()
-{
-    // per host THREAD and device: two threads that drive two streams of one device must not share the event ring
-    static thread_local SideStream per_dev[16];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-    SideStream& s = per_dev[dev];
-    if (!s.ok) {
-        if (hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) != hipSuccess) return nullptr;
-        for (auto& e : s.ev)
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr;
-        if (hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) return nullptr;
-        s.ok = true;
-    }
-    return &s;
-}
-
-constexpr int MAX_BWD_BLOCKS = 4096;   // bounds the per-workgroup gradient partials (grid-stride beyond)
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-struct Problem {
-    int ndim, hc;
-    int64_t n0, n1, W;
-    int64_t n;          // points per species (interior)
-    bool slab;
-    int halo = 2;       // slab layout: planes present on each side of axis 0 (even, >= 2)
-    int skip = 0;       // slab layout: outermost planes per side that this call neither reads nor writes
-    int lo = -1, hi = -1;   // slab layout, plane-range calls: padded plane indices [lo, hi) this call computes
-    bool slab_periodic = false; // slab layout of ONE rank: the n0 interior planes are a periodic domain of their own -- the wrap is
-                                // resolved by index inside the step launches (plane -1 = interior plane n0 - 1), the halo planes
-                                // are neither read nor written
-    Options opt;            // this call's tuning options: process defaults at entry + per-call overrides
-    pi::LossInj loss{0.0, nullptr, 0};   // adjoint calls: what the injection pointer means (pi_device.h); mode 0 = dL/dout itself
-};
-
-int make_problem(int hc, int ndim, const int64_t* shape, bool slab, Problem& p, const char* overrides = nullptr,
-                 bool launches = true)                      // launches = false: a pure size / plan query
-{
-    {
-        std::lock_guard<std::mutex> lk(g_defaults_mu);
-        p.opt = g_defaults;
-    }
-    if (int rc = apply_overrides(p.opt, overrides)) return rc;
-    if (launches)
-        if (int rc = persist_async_error()) return rc;      // an earlier persistent sweep aborted and nobody has been told yet
-    if (!shape || (ndim != 2 && ndim != 3) || hc < -1 || hc > 64) return PERCNN_PI_EINVAL;   // hc == 0: poly, -1: advective
-    if (hc == -1 && slab) return PERCNN_PI_EINVAL;
-    for (int a = 0; a < ndim; ++a)
-        if (shape[a] < 2 || shape[a] > (1 << 30)) return PERCNN_PI_EINVAL;
-    p.ndim = ndim; p.hc = hc; p.slab = slab;
-    p.n0 = shape[0];
-    p.n1 = ndim == 3 ? shape[1] : 1;
-    p.W = shape[ndim - 1];
-    p.n = p.n0 * p.n1 * p.W;
-    if (p.n > (int64_t(1) << 40)) return PERCNN_PI_EINVAL;
-    return 0;
-}
-
-pi::FastDiv make_fastdiv(unsigned d)
-{
-    pi::FastDiv f{0u, 0u};
-    if (d <= 1) return f;
-    unsigned l = 0;
-    while ((1ull << l) < d) ++l;                                   // l = ceil(log2 d) >= 1
-    f.m = (unsigned)((((unsigned long long)1 << (31 + l)) + d - 1) / d);
-    f.s = l - 1;
-    return f;
-}
-
-// chunk-id decomposition of the time-parallel / residual / advective kernels without integer division (vec = points per lane)
-void set_fastdiv(Geom& g, int vec)
-{
-    const long nchunks = (long)g.rows * (g.W / vec);
-    g.fastdiv = nchunks < (1L << 31) ? 1 : 0;
-    g.dcpr = make_fastdiv((unsigned)(g.W / vec));
-    g.dn1 = make_fastdiv((unsigned)g.n1);
-}
-
-// block-uniform decomposition of the direct step kernels (pi_kernels.h "Direct step kernels, addressing"): lanes along x
-// = the power of two that wastes the fewest lanes on this row length; false if the grid is outside what 32-bit byte
-// offsets / 31-bit block ids address (2D: the whole local field + 4 rows, 3D: one plane, must stay below 4 GiB)
-bool set_blockmap(Geom& g, int ndim, int vec, int block, size_t elem, int l2_tile_bytes = 128 * 1024, int rz = 1,
-                  long l2_tile_min_bytes = 3L << 19, int lane_x = 0)
-{
-    const long cpr = g.W / vec;
-    // lanes along x: 2^lxs consecutive chunks of a row per wave row-segment.  A row of cpr chunks is covered by
-    // ceil(cpr / 2^lxs) segments, so a width that is not a power of two leaves lanes idle (cpr = 48 on 64 lanes: 25 %; the
-    // reference's 48^3: 12 chunks on 16 lanes).  Pick the power of two with the most useful lanes, weighted by what a
-    // narrower contiguous segment costs (fitted to 96^3 .. 224^3 on MI355X, profiles/r02_lanes_along_x.txt: 128-byte
-    // segments run at ~0.8 of 1 KiB ones, 256 / 512-byte ones at ~0.95): 160^3 13.8 k -> 17.0 k, 192^3 8.4 k -> 10.6 k steps/s.
-    static const double seg_weight[5] = {0.70, 0.82, 0.95, 0.95, 1.0};     // 2^lxs = 4, 8, 16, 32, 64 chunks of 16 bytes
-    int lxs = 2;
-    double best_pow2 = 1.0;                               // score of the chosen power of two (forced / old rule: never flat)
-    if (lane_x >= 2 && lane_x <= 6) {
-        lxs = lane_x;                                     // tuning aid / A-B tests
-    } else if (lane_x == -1) {                            // the pre-round-2 rule
-        if (cpr <= 64) { while ((1L << lxs) < cpr) ++lxs; }
-        else {
-            lxs = 6;
-            double best = 0.0;
-            for (int c = 6; c >= 4; --c) {
-                const long lx = 1L << c;
-                const double eff = (double)cpr / (double)(((cpr + lx - 1) / lx) * lx);
-                if (eff > best + 1e-9) { best = eff; lxs = c; }
-            }
-        }
-    } else {
-        const long rows = ndim == 3 ? g.n1 : g.n0;
-        double best = 0.0;
-        for (int c = 6; c >= 2; --c) {
-            const long lx = 1L << c, rb = block >> c;     // rb rows of lx chunks per workgroup
-            if (lx > block) continue;
-            double eff = (double)cpr / (double)(((cpr + lx - 1) / lx) * lx) *
-                         (double)rows / (double)(((rows + rb - 1) / rb) * rb);
-            eff *= seg_weight[c - 2];
-            // a row pitch that is not a multiple of 128 bytes leaves the segments straddling cache lines: S bytes touch
-            // (S + 128) / 128 lines on average instead of S / 128 (200^3 with 128-byte segments: forward 39 -> 66 us)
-            const long seg = lx * 16;
-            if (((long)g.W * (long)elem) % 128 != 0) eff *= (double)seg / (double)(seg + 128);
-            if (eff > best + 1e-9) { best = eff; lxs = c; }
-        }
-        best_pow2 = best;
-    }
-    while ((1 << lxs) > block) --lxs;
-    const long nrow = ndim == 3 ? g.n1 : g.n0;
-    // ... or none of them: consecutive chunks of the plane across row ends (`flat`; one multiply-shift per lane, rows follow
-    // each other in memory so a wave still moves 1 KiB pieces) -- taken where the best power of two leaves > ~10 % idle
-    bool flat = lane_x == 7;
-    if (lane_x == 0 && nrow * cpr < (1L << 31)) {
-        const long total = nrow * cpr, nb = (total + block - 1) / block;
-        double eff = 0.97 * (double)total / (double)(nb * block);
-        if (((long)g.W * (long)elem) % 128 != 0) eff *= 1024.0 / (1024.0 + 128.0);
-        // (not with four planes per pass: 208^3 forward 41 -> 51 us, 240^3 65 -> 69 us when forced, while the two-plane
-        // adjoint of the same grids gains 7 %)
-        // and only below 8 M points, where the kernels are latency-bound and idle lanes are what costs: beyond that the
-        // outcome follows the DRAM access pattern instead (same-box A/B: 288^3 +10 %, 224^3 -3 %, 352^3 -5 %)
-        const long npts = (long)g.n0 * g.n1 * g.W;
-        flat = eff > best_pow2 + 0.08 && rz <= 2 && npts < (8L << 20);
-    }
-    if (flat && nrow * cpr >= (1L << 31)) return false;
-    const long lx = flat ? block : 1L << lxs, rpb = flat ? 1 : block >> lxs;
-    g.lxs = flat ? -1 : lxs;
-    g.nxb = flat ? 1 : (int)((cpr + lx - 1) / lx);
-    g.nrg = flat ? (int)((nrow * cpr + block - 1) / block) : (int)((nrow + rpb - 1) / rpb);
-    if (flat) g.dcpr = make_fastdiv((unsigned)cpr);
-    g.rz = ndim == 3 ? rz : 1;
-    const long ngroups = ndim == 3 ? (g.n0 + g.rz - 1) / g.rz : 1;          // plane groups of rz planes
-    const long nblk = (long)g.nxb * g.nrg * ngroups;
-    const unsigned long long span = (unsigned long long)(ndim == 3 ? (long)g.n1 : (long)g.n0 + 4) * g.W * elem;
-    if (nblk <= 0 || nblk >= (1L << 31) || span >= (1ull << 32)) return false;
-    g.nblk = (unsigned)nblk;
-    g.dnxb = make_fastdiv((unsigned)g.nxb);
-    g.dnrg = make_fastdiv((unsigned)g.nrg);
-    // 3D y-tiling for L2 residency (Geom::rgt): a tile's plane section, both species, is held to ~128 KiB so that the four
-    // neighbour planes of everything in flight on an XCD (~2 MiB) fit its 4 MiB L2 next to the streams themselves
-    g.rgt = 0; g.nlast = 0; g.per_tile = 0;
-    // (only where whole planes do not fit anyway: four neighbour planes x two species above ~1.5 MiB; measured on
-    // MI355X: 384^3 backward 726 -> 513 us, 256^3 171 -> 148 us per step, 192^3 -- 1.2 MB of neighbour planes -- loses 3-8 %)
-    if (ndim == 3 && l2_tile_bytes > 0 && 8L * g.n1 * g.W * (long)elem > l2_tile_min_bytes) {
-        const long tile_rows = (long)l2_tile_bytes / (2 * (long)g.W * (long)elem);
-        long rgt = flat ? (long)l2_tile_bytes / (2 * (long)block * vec * (long)elem) : tile_rows / rpb;
-        if (rgt < 1) rgt = 1;
-        if (rgt < g.nrg && (long)rgt * ngroups < (1L << 31)) {
-            const long ntile = (g.nrg + rgt - 1) / rgt;
-            g.rgt = (int)rgt;
-            g.nlast = (int)(g.nrg - (ntile - 1) * rgt);
-            g.per_tile = (unsigned)(rgt * ngroups);
-            g.dper = make_fastdiv(g.per_tile);
-            g.drgt = make_fastdiv((unsigned)g.rgt);
-            g.dlast = make_fastdiv((unsigned)g.nlast);
-        }
-    }
-    return true;
-}
-
-Geom make_geom(const Problem& p)
-{
-    Geom g;
-    g.fastdiv = 0; g.dcpr = pi::FastDiv{0u, 0u}; g.dn1 = pi::FastDiv{0u, 0u};
-    g.lxs = 0; g.nxb = g.nrg = 0; g.nblk = 0; g.dnxb = pi::FastDiv{0u, 0u}; g.dnrg = pi::FastDiv{0u, 0u};
-    g.rgt = g.nlast = 0; g.per_tile = 0; g.dper = g.drgt = g.dlast = pi::FastDiv{0u, 0u};
-    g.xwin = 0; g.rz = 1;
-    g.loss = p.loss;
-    g.n0 = (int)p.n0; g.n1 = (int)p.n1; g.W = (int)p.W;
-    g.rows = (int)(p.n0 * p.n1);
-    g.s0 = (long)(p.n1 * p.W);
-    if (p.slab && p.slab_periodic) {
-        g.ss = (long)(p.n0 + 2 * p.halo) * g.s0;
-        g.off = (long)p.halo * g.s0;
-        g.wrap0 = 1;
-    } else if (p.slab) {
-        // local array: n0 + 2*halo planes; this call computes planes [skip+2, n0+2*halo-skip-2)
-        g.ss = (long)(p.n0 + 2 * p.halo) * g.s0;
-        if (p.lo >= 0) {                                   // explicit plane range (communication overlap: faces first)
-            g.off = (long)p.lo * g.s0;
-            g.n0 = p.hi - p.lo;
-        } else {
-            g.off = (long)(p.skip + 2) * g.s0;
-            g.n0 = (int)(p.n0 + 2 * p.halo - 2 * p.skip - 4);
-        }
-        g.rows = g.n0 * (int)p.n1;
-        g.wrap0 = 0;
-    } else {
-        g.ss = (long)p.n0 * g.s0; g.off = 0; g.wrap0 = 1;
-    }
-    return g;
 }
 
 template <typename T>
@@ -391,15 +45,6 @@ int pick_vec(const Problem& p, std::initializer_list<const void*> ptrs)
     for (const void* q : ptrs)
         if (q && (reinterpret_cast<uintptr_t>(q) % 16)) return 1;
     return V;
-}
-
-// workgroup size of the direct kernels: the "block" option, or 128 threads while 256-thread workgroups would leave
-// CUs idle (a 48^3 grid is 108 workgroups of 256 threads on 256 CUs)
-int direct_block(const Problem& p, const Geom& g, int vec)
-{
-    const long chunks = (long)g.rows * (g.W / vec);
-    if (p.opt.block_small && p.opt.block == 256 && chunks < 1024L * 256) return 128;   // measured 48^3 .. 96^3: +0-10 %
-    return p.opt.block;
 }
 
 // Which samples a launch covers ("batched rollouts" and "ensembles" further down); the default is the unbatched launch.
@@ -1293,19 +938,6 @@ hipError_t adj_tile(const T* hframe_t, const T* gframe_t, T* aframe_t, unsigned 
 }
 
 // ---- persistent fused sweep (pi_tile2d.h "PERSISTENT fused sweep") ---------------------------------------------------------
-int device_cu_count()
-{
-    static int cu_count[16] = {};                           // per device, asked once (benign race: same value)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 0;
-    if (!cu_count[dev]) {
-        int n = 0;
-        cu_count[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : -1;
-    }
-    return cu_count[dev] > 0 ? cu_count[dev] : 0;
-}
-
-bool persist_disabled_here();
 constexpr int PERSIST_BAND = 2 * (TILE_B * TILE_B - (TILE_B - 16) * (TILE_B - 16));     // granules per tile and parity (K = 4)
 size_t persist_outbox_bytes(const Problem& p, int elem = 4)     // per band value: 8 bytes (float32: 16-byte granules of two values -- or the
                                                                 // 8-byte words of the unsplit sweep), 16 bytes (float64: one value per granule)
@@ -1335,153 +967,6 @@ bool persist_ok(const Problem& p, const unsigned char* mask, int t_top, int ngro
     return true;
 }
 
-// Two persistent sweeps in flight on ONE device would each hold part of the CUs and wait for workgroups that cannot become
-// resident.  Within a process: the last persistent launch per device leaves an event behind; a call on ANOTHER stream while that
-// event is not ready takes the launch-per-group path (same stream: ordered behind it anyway).
-// Anything ELSE that keeps workgroups from becoming resident -- another process on the GPU, a CU mask (HSA_CU_MASK, a CU-masked
-// stream), a long kernel on another stream -- is caught by the launch itself: its workgroups give up within a bound, write
-// nothing, and say so in a host-mapped status slot (pi_tile2d.h, PersistArgs::host).  With the handshake (default) the entry
-// point waits for that word -- "all resident" normally arrives a few microseconds after the kernel starts -- and enqueues the
-// launch-per-group sweep itself on an abort; the device then keeps the launch-per-group path until persist_reset.
-// The host side of that protocol is the functions below, once for every resident launcher (2D tile sweeps and forwards, the
-// 3D adjoint sweep, and through pi_host.h the Stage-1 unit): persist_enter -> [persist_fits] -> [persist_scratch] ->
-// persist_claim -> the launch -> persist_launched.
-constexpr int PERSIST_SLOTS = 32;
-struct PersistHost {                                      // host-mapped (hipHostMalloc): written by the device, read here
-    volatile int slot[PERSIST_SLOTS][4];                  // {roll call complete, group, tile, aborted}: see PersistArgs::host
-};
-struct PersistGuard {
-    std::mutex mu;
-    hipEvent_t ev[16] = {};
-    hipStream_t st[16] = {};
-    bool armed[16] = {};
-    bool disabled[16] = {};                               // a launch aborted on this device: launch-per-group until persist_reset
-    PersistHost* host = nullptr;
-    bool host_tried = false;
-    bool watch[PERSIST_SLOTS] = {};                       // slots of launches nobody has looked at since (no-handshake mode)
-    int next_slot = 0;
-    long launches = 0, aborts = 0;
-    int last_group = -1, last_tile = -1;
-    bool warned = false;
-    void* fwd_scratch[16] = {};                           // per device: sync words + granule outbox (persist_scratch)
-    size_t fwd_scratch_bytes[16] = {};
-    std::map<std::tuple<int, const void*, size_t>, int> fits;   // (device, kernel, LDS bytes) -> workgroups per CU (persist_fits)
-};
-PersistGuard g_persist;
-
-bool persist_disabled_here()
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return true;
-    std::lock_guard<std::mutex> lk(g_persist.mu);
-    return g_persist.disabled[dev];
-}
-
-void persist_reset()
-{
-    std::lock_guard<std::mutex> lk(g_persist.mu);
-    for (bool& d : g_persist.disabled) d = false;
-    for (bool& w : g_persist.watch) w = false;
-    g_persist.warned = false;
-}
-
-// the launches of no-handshake callers: has one of them aborted since anybody looked?  (reads of cached host memory)
-int persist_async_error()
-{
-    if (!g_persist.host) return 0;
-    std::lock_guard<std::mutex> lk(g_persist.mu);
-    int rc = 0;
-    for (int i = 0; i < PERSIST_SLOTS; ++i)
-        if (g_persist.watch[i] && g_persist.host->slot[i][3] != 0) {
-            g_persist.watch[i] = false;
-            g_persist.last_group = g_persist.host->slot[i][1];
-            g_persist.last_tile = g_persist.host->slot[i][2];
-            ++g_persist.aborts;
-            for (bool& d : g_persist.disabled) d = true;
-            rc = PERCNN_PI_EASYNC;
-        }
-    return rc;
-}
-
-bool persist_enter(hipStream_t st, int& dev)
-{
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return false;
-    std::lock_guard<std::mutex> lk(g_persist.mu);
-    if (g_persist.disabled[dev]) return false;
-    if (g_persist.armed[dev] && g_persist.st[dev] != st && hipEventQuery(g_persist.ev[dev]) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    if (!g_persist.host_tried) {
-        g_persist.host_tried = true;
-        void* hp = nullptr;
-        if (hipHostMalloc(&hp, sizeof(PersistHost), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess && hp) {
-            std::memset(hp, 0, sizeof(PersistHost));
-            g_persist.host = static_cast<PersistHost*>(hp);
-        } else (void)hipGetLastError();
-    }
-    return g_persist.host != nullptr;                      // no status word, no persistent launch
-}
-void persist_leave(hipStream_t st, int dev)
-{
-    std::lock_guard<std::mutex> lk(g_persist.mu);
-    if (!g_persist.ev[dev] && hipEventCreateWithFlags(&g_persist.ev[dev], hipEventDisableTiming) != hipSuccess) return;
-    if (hipEventRecord(g_persist.ev[dev], st) == hipSuccess) { g_persist.st[dev] = st; g_persist.armed[dev] = true; }
-}
-
-// workgroups of kernel `k` (NT lanes, `lds` bytes) that fit a CU of device `dev`, the current one; 0: none, or the runtime
-// would not say.  Asked once per (device, kernel, lds) -- after allow_lds, which the answer depends on.
-template <typename F>
-int persist_fits(F* k, int NT, size_t lds, int dev)
-{
-    std::lock_guard<std::mutex> lk(g_persist.mu);
-    auto [it, fresh] = g_persist.fits.try_emplace({dev, reinterpret_cast<const void*>(k), lds}, 0);
-    if (fresh) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, NT, lds) != hipSuccess || nb < 1) { (void)hipGetLastError(); nb = 0; }
-        it->second = nb;
-    }
-    return it->second;
-}
-
-// the per-device scratch of the launchers that bring no workspace: 256 B of sync words | outbox of `outbox_bytes` (the caller
-// counts what it keeps behind its granules -- the resident forward's placement words, persist_xcc_bytes -- into them), allocated
-// once (sized for this launch or larger) and zeroed on the stream
-hipError_t persist_scratch(size_t outbox_bytes, hipStream_t st, pi_host::Resident& r)
-{
-    const size_t need = 256 + outbox_bytes;
-    {
-        std::lock_guard<std::mutex> lk(g_persist.mu);
-        if (g_persist.fwd_scratch_bytes[r.dev] < need) {
-            if (g_persist.fwd_scratch[r.dev]) {             // (a launch that still uses the old one is ordered before this call's
-                (void)hipFree(g_persist.fwd_scratch[r.dev]);// work only on its own stream: hipFree synchronises the device)
-                g_persist.fwd_scratch[r.dev] = nullptr;
-                g_persist.fwd_scratch_bytes[r.dev] = 0;
-            }
-            void* q = nullptr;
-            if (hipMalloc(&q, need) != hipSuccess || !q) { (void)hipGetLastError(); return hipErrorOutOfMemory; }
-            g_persist.fwd_scratch[r.dev] = q;
-            g_persist.fwd_scratch_bytes[r.dev] = need;
-        }
-        r.scratch = static_cast<unsigned char*>(g_persist.fwd_scratch[r.dev]);
-    }
-    return hipMemsetAsync(r.scratch, 0, need, st);
-}
-
-// a status slot for the launch about to be made (r.dev: from persist_enter), reset, and the bounds of its hand-over waits
-void persist_claim(const Options& o, pi_host::Resident& r)
-{
-    {
-        std::lock_guard<std::mutex> lk(g_persist.mu);
-        r.slot = g_persist.next_slot++ % PERSIST_SLOTS;
-        g_persist.watch[r.slot] = false;
-    }
-    r.hs = g_persist.host->slot[r.slot];
-    r.hs[0] = 0; r.hs[1] = -1; r.hs[2] = -1; r.hs[3] = 0;
-    r.timeout_ticks = (unsigned long long)o.persist_timeout_ms * 100000ull;                 // 100 MHz clock
-    r.first_timeout_ticks = (unsigned long long)o.persist_first_timeout_ms * 100000ull;
-}
-
 // the PersistArgs every 2D resident kernel takes; the launcher adds what is its own (t_top, pause, masked, frames)
 pi::PersistArgs persist_args(const pi_host::Resident& r, unsigned long long* outbox, unsigned* sync, int ngroups)
 {
@@ -1491,63 +976,6 @@ pi::PersistArgs persist_args(const pi_host::Resident& r, unsigned long long* out
     pa.timeout_ticks = r.timeout_ticks;
     pa.first_timeout_ticks = r.first_timeout_ticks;
     return pa;
-}
-
-// wait for the roll call of a resident launch (not for the launch itself): normally a few microseconds after the kernel
-// starts, i.e. this returns when the stream has reached it.  The bound only guards against a device that never runs the
-// launch at all.  An abort is dealt with here -- the caller recomputes launch by launch.
-hipError_t persist_wait_roll_call(volatile int* hs, int slot, int dev, unsigned grid, const char* what)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    while (hs[0] == 0 && hs[3] == 0) {
-        if ((++spins & 0x3ff) == 0) {
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(600)) return hipErrorLaunchTimeOut;
-            std::this_thread::yield();
-        }
-    }
-    if (hs[3] != 0) {
-        std::lock_guard<std::mutex> lk(g_persist.mu);
-        g_persist.watch[slot] = false;
-        ++g_persist.aborts;
-        g_persist.last_group = hs[1];
-        g_persist.last_tile = hs[2];
-        g_persist.disabled[dev] = true;
-        if (!g_persist.warned) {
-            g_persist.warned = true;
-            std::fprintf(stderr, "percnn_pi: %s could not keep all %u workgroups resident on device %d (group %d, tile %d: another "
-                                 "process / kernel holds CUs, or a CU mask is set); using one launch per group of steps from now on "
-                                 "(percnn_pi_set_option(\"persist_reset\", 1) re-arms it)\n", what, grid, dev, (int)hs[1], (int)hs[2]);
-        }
-        return hipErrorLaunchFailure;
-    }
-    return hipSuccess;
-}
-
-// after a launch that was enqueued without error.  hipSuccess: resident and running (handshake), or fire and forget (an abort
-// nobody has dealt with surfaces at the next entry point: PERCNN_PI_EASYNC); hipErrorLaunchFailure: it ran and ABORTED;
-// hipErrorLaunchTimeOut: fatal.  In the first two cases the launch is on the stream: persist_leave records it for persist_enter.
-hipError_t persist_launched(hipStream_t st, const pi_host::Resident& r, int handshake, unsigned grid, const char* what)
-{
-    {
-        std::lock_guard<std::mutex> lk(g_persist.mu);
-        g_persist.watch[r.slot] = true;
-        ++g_persist.launches;
-    }
-    const hipError_t e = handshake ? persist_wait_roll_call(r.hs, r.slot, r.dev, grid, what) : hipSuccess;
-    if (e == hipSuccess || e == hipErrorLaunchFailure) persist_leave(st, r.dev);
-    return e;
-}
-
-// what the caller of a resident launcher does with its return value
-enum class ResidentRun { ran, fall_back, fall_back_clear, fatal };
-ResidentRun resident_outcome(hipError_t e)
-{
-    if (e == hipSuccess) return ResidentRun::ran;
-    if (e == hipErrorLaunchTimeOut) return ResidentRun::fatal;       // the device never ran the launch: the stream is stuck behind it
-    (void)hipGetLastError();                                      // not resident / not supported / aborted: launch by launch
-    // it RAN and gave up: workgroups that were already through may have added to their partial rows -- start the rows over
-    return e == hipErrorLaunchFailure ? ResidentRun::fall_back_clear : ResidentRun::fall_back;
 }
 
 // ---- RESIDENT 3D reverse sweep (pi_res3d.h, round 6) ------------------------------------------------------------------
@@ -1600,7 +1028,7 @@ hipError_t launch_adj_res3d(const float* traj, const float* g_traj, const unsign
     if (hipError_t e = allow_lds(k, (size_t)LDS_BYTES)) return e;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) { (void)hipGetLastError(); return hipErrorNotSupported; }
-    if (persist_fits(k, NT, (size_t)LDS_BYTES, dev) < 1) return hipErrorCooperativeLaunchTooLarge;
+    if (persist_fits(reinterpret_cast<const void*>(k), NT, (size_t)LDS_BYTES, dev) < 1) return hipErrorCooperativeLaunchTooLarge;
     pi_host::Resident r;
     const size_t outbox_bytes = (size_t)2 * (size_t)pl.nblk * Shape<NT>::BOX_BYTES;
     if (hipError_t e = pi_host::resident_begin(st, outbox_bytes, r)) return e == hipErrorLaunchFailure ? hipErrorNotSupported : e;
@@ -1652,7 +1080,7 @@ hipError_t launch_adj_persist(const T* hframe_t, const T* gframe_t, T* aframe_t,
         if (!p.opt.persist_split) k = pi::pi_adj2d_persist_kernel<T, K, TILE_B, TILE_B, NT>;
     }
     if (hipError_t e = allow_lds(k, lds)) return e;
-    if (persist_fits(k, NT, lds, r.dev) < 1) return hipErrorCooperativeLaunchTooLarge;      // one workgroup per CU (persist_ok)
+    if (persist_fits(reinterpret_cast<const void*>(k), NT, lds, r.dev) < 1) return hipErrorCooperativeLaunchTooLarge;      // one workgroup per CU (persist_ok)
     if (hipError_t e = hipMemsetAsync(outbox, 0, persist_outbox_bytes(p, (int)sizeof(T)), st)) return e;
     long frame_stride = (long)(2 * p.n);
     int np = pi::nparams(p.hc);
@@ -1714,7 +1142,7 @@ hipError_t launch_fwd_persist(T* frame_t0, int ngroups, const T* P, const Proble
     const int two = (int64_t)grid > (int64_t)device_cu_count() ? 1 : 0;
     auto* k = two ? pi::pi_fwd2d_persist_kernel<T, K, TILE_B, TILE_B, NT, 2> : pi::pi_fwd2d_persist_kernel<T, K, TILE_B, TILE_B, NT, 1>;
     if (hipError_t e = allow_lds(k, lds)) return e;
-    const int nb = persist_fits(k, NT, lds, r.dev);
+    const int nb = persist_fits(reinterpret_cast<const void*>(k), NT, lds, r.dev);
     if (nb < 1 || (int64_t)grid > (int64_t)device_cu_count() * nb) return hipErrorCooperativeLaunchTooLarge;
     const size_t outbox_bytes = persist_outbox_bytes(p, (int)sizeof(T));                    // ... | placement words behind it
     if (hipError_t e = persist_scratch(outbox_bytes + persist_xcc_bytes(p), st, r)) return e;
@@ -1858,7 +1286,7 @@ hipError_t launch_fwd_persist_small_t(T* frame_t0, int ngroups, const T* P, cons
     const size_t lds = pi::tile_state_bytes<T, K, TILE_B, BY>() + (size_t)(2 * NGAT + K) * NT * sizeof(int) + 16;
     auto* k = pi::pi_fwd2d_persist_small_kernel<T, K, TILE_B, BY, NT, HALFS>;
     if (hipError_t e = allow_lds(k, lds)) return e;
-    const int nb = persist_fits(k, NT, lds, r.dev);
+    const int nb = persist_fits(reinterpret_cast<const void*>(k), NT, lds, r.dev);
     if (nb < 1 || (int64_t)grid > (int64_t)device_cu_count() * nb) return hipErrorCooperativeLaunchTooLarge;
     // per-device scratch (shared with the 32 x 32 resident forward): granule outbox of 2 parities x tiles x 2 x 32 x BY
     if (hipError_t e = persist_scratch((size_t)2 * grid * (2 * TILE_B * BY) * sizeof(unsigned long long), st, r)) return e;
@@ -3633,231 +3061,6 @@ int batch_residual_sqloss_bwd_impl(const T* traj, const T* g_loss, const T* Q, i
 }  // namespace
 
 namespace {
-
-int apply_option(Options& o, const char* key, long value)
-{
-    if (!key) return PERCNN_PI_EINVAL;
-    if (!std::strcmp(key, "vec")) {
-        if (value != 0 && value != 1) return PERCNN_PI_EINVAL;
-        o.vec = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "tile")) {                       // 0 = never, 1 = size heuristic, 2 = whenever eligible
-        if (value < 0 || value > 2) return PERCNN_PI_EINVAL;
-        o.tile = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "tile_xcd")) { o.tile_xcd = value != 0; return 0; }
-    if (!std::strcmp(key, "handover_local")) { o.handover_local = value != 0; return 0; }
-    if (!std::strcmp(key, "debug_handover_local")) {   // (per call only: set_option refuses it)
-        if (value < 0 || value > (1 << 24)) return PERCNN_PI_EINVAL;
-        o.debug_handover_local = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "tile_by")) {
-        if (value != 0 && value != 8 && value != 16 && value != 32) return PERCNN_PI_EINVAL;
-        o.tile_by = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "slab_fused_put_adj")) { o.slab_fused_put_adj = value != 0; return 0; }
-    if (!std::strcmp(key, "peer_upb") || !std::strcmp(key, "peer_upb_take")) {
-        const bool take = key[8] == '_';
-        if ((value < 256 && !(take && value == 0)) || value > 65536) return PERCNN_PI_EINVAL;
-        (take ? o.peer_upb_take : o.peer_upb) = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "tile_persist")) {
-        if (value < 0 || value > 2) return PERCNN_PI_EINVAL;
-        o.tile_persist = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "persist_handshake")) { o.persist_handshake = value != 0; return 0; }
-    if (!std::strcmp(key, "persist_split")) { o.persist_split = value != 0; return 0; }
-    if (!std::strcmp(key, "persist_small")) { if (value < 0 || value > 2) return PERCNN_PI_EINVAL; o.persist_small = (int)value; return 0; }
-    if (!std::strcmp(key, "fwd_persist")) { o.fwd_persist = value != 0; return 0; }
-    if (!std::strcmp(key, "fwd_persist_f64")) { o.fwd_persist_f64 = value != 0; return 0; }
-    if (!std::strcmp(key, "adj_persist_f64")) { o.adj_persist_f64 = value != 0; return 0; }
-    if (!std::strcmp(key, "fwd_persist_per_cu")) {
-        if (value < 1 || value > 2) return PERCNN_PI_EINVAL;
-        o.fwd_persist_per_cu = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "persist_timeout_ms") || !std::strcmp(key, "persist_first_timeout_ms")) {
-        if (value < 1 || value > 600000) return PERCNN_PI_EINVAL;
-        (key[8] == 'f' ? o.persist_first_timeout_ms : o.persist_timeout_ms) = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "persist_reset")) { persist_reset(); return 0; }
-    if (!std::strcmp(key, "tile_wide")) {
-        if (value < 0 || value > 3) return PERCNN_PI_EINVAL;
-        o.tile_wide = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "skip_wgrad")) { o.skip_wgrad = value != 0; return 0; }
-    if (!std::strcmp(key, "fuse_wgrad")) {
-        if (value < 0 || value > 2) return PERCNN_PI_EINVAL;
-        o.fuse_wgrad = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "overlap")) { o.overlap = value != 0; return 0; }
-    if (!std::strcmp(key, "overlap_chunk")) {
-        if (value < 1 || value > (1 << 20)) return PERCNN_PI_EINVAL;
-        o.overlap_chunk = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "tile_fuse")) {                        // 0 split, 1 fused for float32 (default), 2 fused for float64 too
-        if (value < 0 || value > 2) return PERCNN_PI_EINVAL;
-        o.tile_fuse = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "bwd_cpl")) {
-        if (value < 1 || value > 16) return PERCNN_PI_EINVAL;
-        o.bwd_cpl = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "stream3d")) {                         // 0 = never, 1 = size heuristic, 2 = whenever eligible
-        if (value < 0 || value > 2) return PERCNN_PI_EINVAL;
-        o.stream3d = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "zc")) {
-        if (value < 1 || value > 1024) return PERCNN_PI_EINVAL;
-        o.zc = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "fwd_blocks")) {
-        if (value < 0 || value > (1 << 24)) return PERCNN_PI_EINVAL;
-        o.fwd_blocks = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "xcd_window")) {
-        if (value < 0 || value > (1 << 24) || value % 8) return PERCNN_PI_EINVAL;
-        o.xcd_window = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "block_small")) { o.block_small = value != 0; return 0; }
-    if (!std::strcmp(key, "slab_wide_adjoint")) { o.slab_wide_adjoint = value != 0; return 0; }
-    if (!std::strcmp(key, "slab_local_index")) { o.slab_local_index = value != 0; return 0; }
-    if (!std::strcmp(key, "fwd_small_half")) { if (value < 0 || value > 1) return PERCNN_PI_EINVAL; o.fwd_small_half = (int)value; return 0; }
-    if (!std::strcmp(key, "adj_small_half")) { if (value < 0 || value > 1) return PERCNN_PI_EINVAL; o.adj_small_half = (int)value; return 0; }
-    if (!std::strcmp(key, "adj_small_pause")) { if (value < -1 || value > 200) return PERCNN_PI_EINVAL; o.adj_small_pause = (int)value; return 0; }
-    if (!std::strcmp(key, "fwd_small_pause")) { if (value < -1 || value > 200) return PERCNN_PI_EINVAL; o.fwd_small_pause = (int)value; return 0; }
-    if (!std::strcmp(key, "brick_xny")) { if (value < -1 || value > 8 || value == 3 || (value > 4 && value < 8)) return PERCNN_PI_EINVAL; o.brick_xny = (int)value; return 0; }
-    if (!std::strcmp(key, "slab_fused_put")) { o.slab_fused_put = value != 0; return 0; }
-    if (!std::strcmp(key, "peer_wire_us")) {
-        if (value < 0 || value > 100000) return PERCNN_PI_EINVAL;
-        o.peer_wire_us = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "slab_put_blocks")) {
-        if (value < 4 || value > 256 || value % 4) return PERCNN_PI_EINVAL;
-        o.slab_put_blocks = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "lane_x")) {
-        if (value != 0 && value != -1 && (value < 2 || value > 7)) return PERCNN_PI_EINVAL;     // 7 = flat
-        o.lane_x = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "rz")) {
-        if (value != 0 && value != 1 && value != 2 && value != 4) return PERCNN_PI_EINVAL;
-        o.rz = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "l2_tile_min_kb")) {
-        if (value < 0 || value > (1 << 22)) return PERCNN_PI_EINVAL;
-        o.l2_tile_min_kb = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "l2_tile_kb")) {
-        if (value < 0 || value > 16384) return PERCNN_PI_EINVAL;
-        o.l2_tile_kb = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "brick3d")) {                          // 0 = never, 1 = size heuristic, 2 = whenever eligible
-        if (value < 0 || value > 2) return PERCNN_PI_EINVAL;
-        o.brick3d = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "res3d")) {                            // 0 = never, 1 = where it measured faster, 2 = whenever eligible
-        if (value < 0 || value > 2) return PERCNN_PI_EINVAL;
-        o.res3d = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "brick_wt")) { o.brick_wt = value != 0; return 0; }
-    if (!std::strcmp(key, "brick_xcd")) {
-        if (value < 0 || value > 2) return PERCNN_PI_EINVAL;
-        o.brick_xcd = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "brick_wide")) { o.brick_wide = value != 0; return 0; }
-    if (!std::strcmp(key, "brick_nt")) {
-        if (value != 0 && value != 256 && value != 512) return PERCNN_PI_EINVAL;
-        o.brick_nt = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "brick_wgs")) {
-        if (value < 0 || value > 16) return PERCNN_PI_EINVAL;
-        o.brick_wgs = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "brick_rz")) {
-        if (value != 0 && value != 1 && value != 2 && value != 4) return PERCNN_PI_EINVAL;
-        o.brick_rz = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "lds_pad")) {
-        if (value < 0 || value > 80 * 1024 || value % 16) return PERCNN_PI_EINVAL;
-        o.lds_pad = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "tile_k")) {
-        if (value != 2 && value != 4 && value != 8) return PERCNN_PI_EINVAL;   // 8: poly mode only (else 4)
-        o.tile_k = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "tile_nt")) {
-        if (value != 256 && value != 512 && value != 1024) return PERCNN_PI_EINVAL;   // 1024: poly mode only
-        o.tile_nt = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "wgrad_blocks")) {
-        if (value < 1 || value > MAX_BWD_BLOCKS / 2) return PERCNN_PI_EINVAL;
-        o.wgrad_blocks = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "block")) {
-        if (value < 64 || value > 256 || value % 64) return PERCNN_PI_EINVAL;
-        o.block = (int)value;
-        return 0;
-    }
-    if (!std::strcmp(key, "graph")) return value == 0 ? 0 : PERCNN_PI_EINVAL;   // reserved
-    return PERCNN_PI_EINVAL;
-}
-
-// "key=value,key=value" (whitespace-free); empty / NULL = no overrides
-int apply_overrides(Options& o, const char* spec)
-{
-    if (!spec) return 0;
-    char key[32];
-    while (*spec) {
-        const char* eq = std::strchr(spec, '=');
-        if (!eq || eq == spec || (size_t)(eq - spec) >= sizeof(key)) return PERCNN_PI_EINVAL;
-        std::memcpy(key, spec, (size_t)(eq - spec));
-        key[eq - spec] = 0;
-        char* end = nullptr;
-        const long v = std::strtol(eq + 1, &end, 10);
-        if (end == eq + 1 || (*end && *end != ',')) return PERCNN_PI_EINVAL;
-        if (int rc = apply_option(o, key, v)) return rc;
-        spec = *end ? end + 1 : end;
-    }
-    return 0;
-}
-
-}  // namespace
-
-
-namespace {
 // loss value of the squared-error losses the sweep differentiates in place (pi::LossInj): scale * sum over the frames with
 // mask[f] != 0 of sum_x (traj - target)^2, written to out[0] (compute type).  ws: >= 1024 doubles.
 template <typename T>
@@ -4103,38 +3306,6 @@ int debug_handover_local(const Problem& p, int elem_size, int* out)
 }  // namespace
 
 // ---- exported symbols ---------------------------------------------------------------------------
-// ---- resident launches of the Stage-1 block (pi_s1_abi.hip, the library's second translation unit) ---------------------------
-// They share the residency guard of the 2D resident kernels: one resident grid per device at a time (calls on other streams
-// are detected and refused), host-mapped status slots, a per-device scratch (sync words + granule outbox), the handshake on the
-// roll call and the "disabled after an abort" state (percnn_pi_persist_status / persist_reset report and re-arm both).
-// No step of the protocol is written here: these are the functions at PersistGuard, under the process-wide options (the 2D
-// launchers take a call's own).
-namespace pi_host {
-int resident_async_error() { return persist_async_error(); }
-int resident_cu_count() { return device_cu_count(); }
-// hipSuccess: launch; anything else: take the launch-per-step path (nothing has been enqueued but the memset)
-hipError_t resident_begin(void* stream, size_t outbox_bytes, Resident& r)
-{
-    auto st = static_cast<hipStream_t>(stream);
-    Options o;
-    { std::lock_guard<std::mutex> lk(g_defaults_mu); o = g_defaults; }
-    if (!o.tile_persist || !o.fwd_persist) return hipErrorNotSupported;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return hipErrorNotSupported; }
-    if (!persist_enter(st, r.dev)) return hipErrorNotSupported;
-    if (hipError_t e = persist_scratch(outbox_bytes, st, r)) return e;
-    persist_claim(o, r);
-    return hipSuccess;
-}
-// after the launch: hipSuccess = resident and running; hipErrorLaunchFailure = it aborted (the caller recomputes launch by launch)
-hipError_t resident_launched(void* stream, Resident& r, unsigned grid, const char* what)
-{
-    int handshake;
-    { std::lock_guard<std::mutex> lk(g_defaults_mu); handshake = g_defaults.persist_handshake; }
-    return persist_launched(static_cast<hipStream_t>(stream), r, handshake, grid, what);
-}
-}  // namespace pi_host
-
 extern "C" {
 
 #ifdef PI_TILE_TIMING
@@ -4326,25 +3497,6 @@ size_t percnn_pi_rollout_bwd_workspace_bytes(int hc, int ndim, const int64_t* sh
     return need;
 }
 
-int percnn_pi_set_option(const char* key, long value)
-{
-    if (key && !std::strcmp(key, "debug_handover_local")) return PERCNN_PI_EINVAL;       // a query of one call, never a default
-    std::lock_guard<std::mutex> lk(g_defaults_mu);
-    return apply_option(g_defaults, key, value);
-}
-
-// host-mapped words the device can write and the host can read without synchronising (pack guard slots)
-int percnn_pi_host_words_alloc(void** p, size_t bytes)
-{
-    if (!p || bytes == 0) return PERCNN_PI_EINVAL;
-    void* hp = nullptr;
-    if (hipError_t e = hipHostMalloc(&hp, bytes, hipHostMallocMapped | hipHostMallocCoherent)) return (int)e;
-    std::memset(hp, 0, bytes);
-    *p = hp;
-    return 0;
-}
-int percnn_pi_host_words_free(void* p) { return p ? (int)hipHostFree(p) : 0; }
-
 // diagnostics (tests of the persistent sweep's abort path): `blocks` workgroups that each hold `lds_bytes` of a CU's LDS for
 // `ms` milliseconds on `stream` -- what "another kernel holds whole CUs" looks like
 namespace {
@@ -4387,34 +3539,6 @@ int percnn_pi_debug_hog(int blocks, int lds_bytes, int ms, void* stream)
         }
     }
     return 0;
-}
-
-int percnn_pi_persist_status(long* info)
-{
-    if (!info) return PERCNN_PI_EINVAL;
-    int dev = 0;
-    const bool have_dev = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16;
-    if (!have_dev) (void)hipGetLastError();
-    std::lock_guard<std::mutex> lk(g_persist.mu);
-    info[0] = g_persist.launches;
-    info[1] = g_persist.aborts;
-    info[2] = have_dev && g_persist.disabled[dev] ? 1 : 0;
-    info[3] = g_persist.last_group;
-    info[4] = g_persist.last_tile;
-    // state word of the most recent launch as the device left it: 0 not started, 1 every workgroup resident, 2 aborted
-    if (g_persist.host && g_persist.next_slot > 0) {
-        volatile int* hs = g_persist.host->slot[(g_persist.next_slot - 1) % PERSIST_SLOTS];
-        info[5] = hs[3] ? 2 : hs[0];
-    } else info[5] = -1;
-    return 0;
-}
-
-// Fence for callers that run the resident launches fire-and-forget (persist_handshake = 0) and hand their outputs to code
-// that is not this library: waits for `stream`, then reports -- once -- whether a resident launch aborted since anybody looked
-int percnn_pi_persist_fence(void* stream)
-{
-    if (hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(stream))) return (int)e;
-    return persist_async_error();
 }
 
 #define PI_EXPORT(SUF, T)                                                                                           \

@@ -1,6 +1,6 @@
 // step3d_probe.hip -- standalone probe of the direct 3D step kernels at ONE shape (default 128^3, float32, pre-contracted
 // block): per-step time of kernel variants in a ping-pong rollout, bit-identity between variants, and (built with
-// -DPI_3D_TIMING) a per-wave device timeline.  The host side re-states just enough of pi_abi.hip's set_blockmap for a
+// -DPI_3D_TIMING) a per-wave device timeline.  The host side re-states just enough of pi_host.hip's set_blockmap for a
 // power-of-two row (whole rows per workgroup).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off [-DPI_3D_TIMING] -o step3d_probe step3d_probe.hip && ./step3d_probe
 #include <hip/hip_runtime.h>
