@@ -2152,6 +2152,15 @@ template <typename T, int PASS> struct sweep_half_pass {
     static constexpr int HALF_PASS_MASK = 0x39;
     static constexpr bool value = PASS != 2 && ((HALF_PASS_MASK >> PASS) & 1) != 0;
 };
+// WHEN a pass of the split sweep asks for the next pass's pointwise operands: before its own arithmetic, so that the loads travel
+// under it -- or, P1, after it.  P1 runs while the halo ring is in flight, and P2's operands are the largest request of a group
+// (388 strips, 25 KB per CU): issued next to the ring request they share the CU's memory pipeline with it for the whole flight.
+// Behind P1's arithmetic the three waves that have any leave the ring alone meanwhile, and the wait for the ring (which counts
+// requests, see the group loop) no longer includes them: 8.1 -> 7.8 us per group (docs/NOTEBOOK.md section 24).
+enum : int { OPS_AHEAD_FIRST = 0, OPS_AHEAD_LAST = 1 };
+template <typename T, int PASS> struct sweep_ops_ahead {
+    static constexpr int value = PASS == 1 ? OPS_AHEAD_LAST : OPS_AHEAD_FIRST;
+};
 constexpr int SWEEP_HALF_P5_SPLIT = 128;                   // P5 on half-strips: I_3 = 64 strips on lanes 0 .. 127, A_3 = 192 from lane 128 on
 
 // The six passes of a group: which sub-step / part the waves below SPLIT work on (M1, PART1; strips indexed from lane 0) and
@@ -2235,8 +2244,11 @@ __device__ __forceinline__ void persist_pass(T* b0, T* b1, const T* const (&hf)[
 {
     using PP = PersistPass<PASS>;
     constexpr bool HALF_HERE = sweep_half_pass<T, PASS>::value, HALF_NEXT = sweep_half_pass<T, (PASS + 1) % 6>::value;
-    if constexpr (HALF_NEXT) persist_load_ops_half<T>(ahead, hn, gn, g, so_next.o0);
-    else persist_load_ops<T>(ahead, hn, gn, g, so_next);
+    constexpr int AHEAD = sweep_ops_ahead<T, PASS>::value;
+    if constexpr (AHEAD == OPS_AHEAD_FIRST) {
+        if constexpr (HALF_NEXT) persist_load_ops_half<T>(ahead, hn, gn, g, so_next.o0);
+        else persist_load_ops<T>(ahead, hn, gn, g, so_next);
+    }
     constexpr int LACC = sizeof(T) == 8 ? NT / 2 : NT;     // float64: moments straight into the shared LDS rows (adj_substep)
     if constexpr (HALF_HERE) {
         // every lane a half-strip of sub-step M (P5: both parts are sub-step 3 and share the injection frame)
@@ -2259,6 +2271,11 @@ __device__ __forceinline__ void persist_pass(T* b0, T* b1, const T* const (&hf)[
         for (int s = 0; s < 2; ++s)
 #pragma unroll
             for (int m = 0; m < 10; ++m) asm volatile("" : "+v"(mom.a[s][m]));
+    }
+    if constexpr (AHEAD == OPS_AHEAD_LAST) {
+        __builtin_amdgcn_sched_barrier(0);                 // (the scheduler would lift the loads to the top of the pass again)
+        if constexpr (HALF_NEXT) persist_load_ops_half<T>(ahead, hn, gn, g, so_next.o0);
+        else persist_load_ops<T>(ahead, hn, gn, g, so_next);
     }
     lds_barrier();
 }
@@ -2393,23 +2410,34 @@ pi_adj2d_persist_split_kernel(const T* __restrict__ hframe_t, const T* __restric
             int gl[NGAT];
 #pragma unroll
             for (int q = 0; q < NGAT; ++q) gl[q] = tab_gl[q * NT + (int)threadIdx.x];
-            const unsigned long long t0 = wall_clock64();
-            const unsigned long long bound = grp == 1 ? pa.first_timeout_ticks : pa.timeout_ticks;
             bool failed = false;
-            for (;;) {
-                bool ok = true;
+            // The FIRST look at the granules stands outside the loop.  A wave's loads return in order and the wait for one is a
+            // count of the requests issued after it: here, the eight operand loads P1 has just issued for P2 may stay in flight.
+            // Inside a loop that also re-requests granules the count is unknown and the compiler waits for EVERY load of the wave,
+            // P2's operands included (it did: the ring "landed" when they had, 0.2 us later).  The loop is the rare case -- a
+            // request sent after P0 nearly always comes back current.
+            bool ok = true;
 #pragma unroll
-                for (int q = 0; q < NGAT; ++q)
-                    if (gl[q] >= 0) ok &= GranuleIO<T>::ok(gx[q], epoch);
-                if (__all(ok)) break;
-                // give up when the wait is over its bound (the first to do so raises the abort flag below) or when another
-                // workgroup already has: a launch whose workgroups are not all resident ends within the bound
-                if (wall_clock64() - t0 > bound ||
-                    __hip_atomic_load(pa.sync + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { failed = true; break; }
-                __builtin_amdgcn_s_sleep(1);
+            for (int q = 0; q < NGAT; ++q)
+                if (gl[q] >= 0) ok &= GranuleIO<T>::ok(gx[q], epoch);
+            if (!__all(ok)) {
+                const unsigned long long t0 = wall_clock64();
+                const unsigned long long bound = grp == 1 ? pa.first_timeout_ticks : pa.timeout_ticks;
+                for (;;) {
+                    // give up when the wait is over its bound (the first to do so raises the abort flag below) or when another
+                    // workgroup already has: a launch whose workgroups are not all resident ends within the bound
+                    if (wall_clock64() - t0 > bound ||
+                        __hip_atomic_load(pa.sync + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { failed = true; break; }
+                    __builtin_amdgcn_s_sleep(1);
 #pragma unroll
-                for (int q = 0; q < NGAT; ++q)
-                    if (gl[q] >= 0 && !GranuleIO<T>::ok(gx[q], epoch)) gx[q] = gio.get(half + (size_t)gs[q]);
+                    for (int q = 0; q < NGAT; ++q)
+                        if (gl[q] >= 0 && !GranuleIO<T>::ok(gx[q], epoch)) gx[q] = gio.get(half + (size_t)gs[q]);
+                    ok = true;
+#pragma unroll
+                    for (int q = 0; q < NGAT; ++q)
+                        if (gl[q] >= 0) ok &= GranuleIO<T>::ok(gx[q], epoch);
+                    if (__all(ok)) break;
+                }
             }
             if (failed) {
                 if (threadIdx.x % WAVE == 0) *wg_abort = 1;

@@ -17,6 +17,20 @@
 
 #include "../percnn_amd/csrc/pi_tile2d.h"
 
+// Schedule variants of the split sweep.  These are switches of THIS file -- the header carries what ships and no build-time
+// switch; its schedule constants are traits, specialised here before the kernel is instantiated (docs/NOTEBOOK.md section 24):
+//   -DDEV_OPS_AHEAD_P1=0  pass P1 asks for P2's pointwise operands before its arithmetic, next to the ring request
+//   -DDEV_OPS_AHEAD_P1=1  ... after its arithmetic (what ships)
+//   -DDEV_OPS_AHEAD_P1=2  ... not at all: TIMING ONLY, P2 computes with stale operands and the results are wrong -- what the
+//                         ring's flight is when it has the CU's memory pipeline to itself
+//   -DDEV_HALF_P1=1       P1 on half-strips (0: whole strips, what ships)
+#ifdef DEV_OPS_AHEAD_P1
+template <> struct pi::sweep_ops_ahead<float, 1> { static constexpr int value = DEV_OPS_AHEAD_P1; };
+#endif
+#ifdef DEV_HALF_P1
+template <> struct pi::sweep_half_pass<float, 1> { static constexpr bool value = DEV_HALF_P1 != 0; };
+#endif
+
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { std::printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); std::exit(1); } } while (0)
 
 namespace {
@@ -175,7 +189,15 @@ int main(int argc, char** argv)
                 std::sort(v.begin(), v.end());
                 std::printf(" %s %.2f", i == 8 ? last : names[i == 0 ? 0 : (i == 1 ? 1 : (i == 2 ? 3 : (i == 3 ? 4 : i + 1)))], v[128]);
             }
-            std::printf("\n");
+            // the ring: requested at the end of P0 (stamp 1), landed at stamp 3, waited for since the end of P1 (stamp 2)
+            std::vector<double> fl, wt;
+            for (int b = 0; b < 256; ++b) {
+                fl.push_back((hs[(b * 8 + w) * 16 + 3] - hs[(b * 8 + w) * 16 + 1]) * 0.01);
+                wt.push_back((hs[(b * 8 + w) * 16 + 3] - hs[(b * 8 + w) * 16 + 2]) * 0.01);
+            }
+            std::sort(fl.begin(), fl.end());
+            std::sort(wt.begin(), wt.end());
+            std::printf(" | request -> landed %.2f, wait after P1 %.2f\n", fl[128], wt[128]);
         }
     }
 #endif
