@@ -628,19 +628,89 @@ hipError_t brick_bwd(int rz, bool mom, const T* h, const T* G, const T* inj, T* 
 #undef CALL_BB
 }
 
+// brick3d = 1: which batches take the bricks by default (brick3d = 2: every eligible one).
+// Measured on one MI355X (profiles/batch_brick_throughput.json, tools/batch_brick_throughput.py: pi_rollout_batched + backward,
+// float32, k sample-steps/s, brick3d=0 -> brick3d=2, the routes alternating in one process, best of two 1 s regions; brick3d=0
+// against itself: within 0.12 % on every row):
+//   pre-contracted blocks   48^3 x 300, B = 8: 422.7 -> 443.2 (+4.9 %); B = 64: 724.2 -> 787.8 (+8.8 %); 128^3 x 32, B = 4: 40.06 -> 46.63 (+16.4 %)
+//   factored blocks, Hc = 2 48^3 x 300, B = 8: 372.3 -> 329.9 (-11.4 %); B = 64: 568.1 -> 512.7 (-9.8 %); 128^3 x 32, B = 4: 30.64 -> 29.72 (-3.0 %)
+// -> pre-contracted blocks of 48^3 .. 128^3 points per sample (110592 .. 2097152) in launches of at least 8 x 48^3 points, the
+// smallest batch that was measured; factored blocks lose everywhere and stay direct, as does every class without a figure
+// (smaller or larger samples, smaller launches): brick3d = 2 reaches the bricks there.  The class is (block kind, points per
+// sample, points per launch); float64 batches follow the float32 figures and have none of their own.
+bool batch_brick_default(const Problem& p, int batch)
+{
+    constexpr int64_t N_MIN = 48 * 48 * 48, N_MAX = 128 * 128 * 128;
+    return p.hc == 0 && p.n >= N_MIN && p.n <= N_MAX && (int64_t)batch * p.n >= 8 * N_MIN;
+}
+
+// Planes per brick of a batched / ensemble step launch, 0 = the direct kernels.  Per sample the rule is brick_rz_for's (256-lane
+// bricks: rows of up to 64 chunks); on top of it the lanes must be the 16-byte ones (`vec` is pick_vec's answer over the call's
+// pointers), the sample stride must keep every sample's base 16-byte aligned, the sparse-observation form (`obs`) and factored
+// blocks that need all gradients in the launch (`wgrad`, the rule of step_route) stay direct, and four-plane bricks have no sample
+// flavour.  brick_nt and brick_wide do not apply.  One function for step_route and ens_rows_for.
+template <typename T>
+int batch_brick_rz(const Problem& p, int vec, int batch, bool adjoint, bool wgrad, bool obs)
+{
+    if (obs || batch < 2 || (adjoint && wgrad && p.hc != 0)) return 0;
+    if (((size_t)2 * p.n * sizeof(T)) % 16) return 0;
+    const int rz = brick_rz_for<T>(p, vec, adjoint, /*wide=*/false);
+    if (rz < 1 || rz > 2) return 0;
+    if (p.opt.brick3d == 1 && !batch_brick_default(p, batch)) return 0;
+    return rz;
+}
+
+// ---- which kernel family one step runs on -------------------------------------------------------
+// The one statement of "advective block, else plane streaming, else bricks, else the direct kernels" for the four step
+// dispatchers (step_fwd, step_bwd and their sample flavours) and the plan queries.  The numbers are those percnn_pi_debug_plan
+// reports; TILES is a rollout's answer (plan_fwd / plan_sweep), never a step's.
+enum Family { DIRECT = 0, TILES = 1, STREAM = 2, BRICKS = 3, ADVECTIVE = 4 };
+struct StepRoute {
+    Family family;
+    int planes;                          // planes per pass of the brick and direct kernels (1 elsewhere)
+    int vec;                             // lanes: elements per lane of the launch (streaming: stream3d_vec's, else pick_vec's)
+};
+
+// the plane-streaming adjoint with all gradients in the launch exists for float32 pre-contracted blocks only
+template <typename T>
+bool stream_fuses(const Problem& p) { return p.hc == 0 && sizeof(T) == 4; }
+
+// ptrs: the buffers of the launch (alignment picks the lanes; none = 16-byte aligned).  wgrad: an adjoint step that carries ALL
+// parameter gradients (else adjoint state + diffusion-coefficient sums) -- factored blocks then run on the direct kernel.
+// s.on: a sample launch (no advective, streaming, 512-lane or four-plane flavour; one plane per pass of the direct kernels);
+// obs: its sparse-observation form.
+template <typename T>
+StepRoute step_route(const Problem& p, std::initializer_list<const void*> ptrs, bool adjoint, bool wgrad, const Samples& s = {},
+                     bool obs = false)
+{
+    if (p.hc == -1) return {ADVECTIVE, 1, 1};
+    if (!s.on && (!adjoint || !wgrad || stream_fuses<T>(p)))
+        if (const int sv = stream3d_vec<T>(p, ptrs, adjoint)) return {STREAM, 1, sv};
+    const int vec = pick_vec<T>(p, ptrs);
+    if (s.on) {
+        const int brz = batch_brick_rz<T>(p, vec, s.batch, adjoint, wgrad, obs);
+        return {brz ? BRICKS : DIRECT, brz ? brz : 1, vec};
+    }
+    if (!adjoint || !wgrad || p.hc == 0)
+        if (const int brz = brick_rz_for<T>(p, vec, adjoint)) return {BRICKS, brz, vec};
+    return {DIRECT, direct_rz<T>(p, vec, adjoint), vec};
+}
+
 template <typename T>
 hipError_t step_fwd(const T* h, T* out, const T* P, const Problem& p, hipStream_t st)
 {
-    if (p.hc == -1) return adv_fwd<T>(h, out, P, p, st);
-    if (const int sv = stream3d_vec<T>(p, {h, out}, false))
-        return stream3d<T, false>(sv, h, out, nullptr, nullptr, nullptr, P, p, st, nullptr);
-    const int vec = pick_vec<T>(p, {h, out});
-    if (const int brz = brick_rz_for<T>(p, vec, false)) return brick_fwd<T>(brz, h, out, P, p, st);
+    const StepRoute r = step_route<T>(p, {h, out}, false, false);
+    switch (r.family) {
+        case ADVECTIVE: return adv_fwd<T>(h, out, P, p, st);
+        case STREAM:    return stream3d<T, false>(r.vec, h, out, nullptr, nullptr, nullptr, P, p, st, nullptr);
+        case BRICKS:    return brick_fwd<T>(r.planes, h, out, P, p, st);
+        default:        break;
+    }
+    const int vec = r.vec;
     {
         constexpr int V = pi::vec_width<T>::value;
-        const int rz = direct_rz<T>(p, vec, false);
-        if (rz == 2) return launch_fwd<T, 3, pi::POLY, V, 2>(h, out, P, p, st);
-        if (rz == 4) return launch_fwd<T, 3, pi::POLY, V, 4>(h, out, P, p, st);
+        if (r.planes == 2) return launch_fwd<T, 3, pi::POLY, V, 2>(h, out, P, p, st);
+        if (r.planes == 4) return launch_fwd<T, 3, pi::POLY, V, 4>(h, out, P, p, st);
     }
 #define CALL_FWD(NDIM, HC, VEC) launch_fwd<T, NDIM, HC, VEC>(h, out, P, p, st)
     PI_DISPATCH(CALL_FWD);
@@ -654,17 +724,16 @@ template <typename T, bool WGRAD>
 hipError_t step_bwd(const T* h, const T* G, const T* inj, T* Gp, double* partials, const T* P, const Problem& p,
                     hipStream_t st, unsigned* grid_out)
 {
-    if (p.hc == -1) return adv_bwd<T>(h, G, inj, Gp, partials, P, p, st, grid_out);   // always fused (tiny grids)
-    if (!WGRAD || (p.hc == 0 && sizeof(T) == 4))            // fused flavour of the streaming kernel: float32 poly mode only
-        if (const int sv = stream3d_vec<T>(p, {h, G, inj, Gp}, true))
-            return stream3d<T, true>(sv, G, Gp, h, inj, partials, P, p, st, grid_out, WGRAD ? 1 : 0);
-    const int vec = pick_vec<T>(p, {h, G, inj, Gp});
-    if (!WGRAD || p.hc == 0)                                  // factored blocks with all gradients in the launch: direct kernel
-        if (const int brz = brick_rz_for<T>(p, vec, true)) {
-            if (grid_out) *grid_out = brick_bwd_grid(p, vec, brz);
-            return brick_bwd<T>(brz, WGRAD, h, G, inj, Gp, partials, P, p, st);
-        }
-    const int rz = direct_rz<T>(p, vec, true);
+    const StepRoute r = step_route<T>(p, {h, G, inj, Gp}, true, WGRAD);
+    const int vec = r.vec, rz = r.planes;
+    switch (r.family) {
+        case ADVECTIVE: return adv_bwd<T>(h, G, inj, Gp, partials, P, p, st, grid_out);   // always fused (tiny grids)
+        case STREAM:    return stream3d<T, true>(vec, G, Gp, h, inj, partials, P, p, st, grid_out, WGRAD ? 1 : 0);
+        case BRICKS:
+            if (grid_out) *grid_out = brick_bwd_grid(p, vec, rz);
+            return brick_bwd<T>(rz, WGRAD, h, G, inj, Gp, partials, P, p, st);
+        default: break;
+    }
     if (grid_out) *grid_out = bwd_grid(p, vec, sizeof(T), rz);
     {
         constexpr int V = pi::vec_width<T>::value;
@@ -727,21 +796,43 @@ int tile_wide_for(const Problem& p, bool adjoint)
     return 0;
 }
 
-struct TileShape { int bx, by, nt; };
+// The tile kernel a launch-per-group call runs: steps per launch, lanes, tile height and width, and (adjoint) whether it is the
+// flavour that sums all gradients in the launch.  fwd_tile / adj_tile launch exactly this; tile geometry, eligibility, the partial
+// rows, the resident predicates and the plan queries read it.  tile_wide_for and tile_by_for are its inputs.  Precedence: the wide
+// shapes; steps per launch by option (two; eight, pre-contracted blocks only); 1024 lanes (pre-contracted blocks only); the
+// 16- and 8-row tiles of tile_by_for (it answers 32 for factored blocks); 256 lanes; else 512.  An explicit tile_by next to
+// tile_k = 2, tile_k = 8 or tile_nt = 1024 has no kernel and is ignored: those run on 32 rows.
+struct TileVariant { int k, nt, by, bx; bool mom; };
 template <typename T>
-TileShape tile_shape_for(const Problem& p, bool adjoint)
+TileVariant tile_variant_for(const Problem& p, bool adjoint)
 {
-    switch (tile_wide_for<T>(p, adjoint)) {
-        case 1: return {32, 40, 640};
-        case 2: return {40, 40, 768};
-        default: return {TILE_B, tile_by_for(p), 0};
-    }
+    const int wide = tile_wide_for<T>(p, adjoint);
+    const bool poly = p.hc == 0;
+    TileVariant v{4, 512, TILE_B, TILE_B, false};
+    if (wide == 1) v = {4, 640, 40, 32, false};
+    else if (wide == 2) v = {4, 768, 40, 40, false};
+    else if (p.opt.tile_k == 2) v.k = 2, v.nt = 256;
+    else if (poly && p.opt.tile_k == 8) v.k = 8, v.nt = 1024;
+    else if (poly && p.opt.tile_nt == 1024) v.nt = 1024;
+    else if (poly && tile_by_for(p) == 16) v.nt = 320, v.by = 16;
+    else if (poly && tile_by_for(p) == 8) v.nt = 256, v.by = 8;
+    else if (p.opt.tile_nt == 256) v.nt = 256;
+    // the fused-moments flavour exists for pre-contracted blocks, K = 4, on 32 x 32 tiles of 512 threads and on the wide shapes
+    // measured on MI355X (backward us per step, split -> fused): 384^2 3.37 -> 3.20, 512^2 3.90 -> 3.29, 1000^2 13.4 -> 11.3;
+    // in the 16-row-tile regime (<= 128 tiles of 32x32, e.g. the reference's 100^2) the extra VALU work sits on the one
+    // critical workgroup chain and loses (2.26 -> 2.66), so it keeps the split schedule
+    // float64 (lambda-omega): the per-lane moment sums live in LDS and are updated with ds_add_f64 (pi_tile2d.h) -- a register
+    // flavour needed more than the 256 registers of a 512-thread workgroup (57 spilled doubles, 5.98 -> 9.13 us per step,
+    // profiles/r02_fp64_fused_tile_sweep.txt); with LDS accumulators: 186 VGPRs, no scratch, lambda-omega 512^2 backward
+    // 5.45 -> 4.48 us per step, 1024^2 19.1 -> 15.9 (profiles/r02_fp64_fused_lds_accumulators.txt)
+    v.mom = adjoint && p.opt.tile_fuse && !p.opt.skip_wgrad && poly && v.k == 4 && (wide || (v.nt == 512 && v.by == TILE_B));
+    return v;
 }
 template <typename T>
 int64_t tile_count(const Problem& p, bool adjoint)
 {
-    const TileShape s = tile_shape_for<T>(p, adjoint);
-    return ((p.n0 + s.by - 1) / s.by) * ((p.W + s.bx - 1) / s.bx);
+    const TileVariant v = tile_variant_for<T>(p, adjoint);
+    return ((p.n0 + v.by - 1) / v.by) * ((p.W + v.bx - 1) / v.bx);
 }
 
 template <typename T>
@@ -750,7 +841,7 @@ bool tile_eligible(const Problem& p, std::initializer_list<const void*> ptrs, bo
     if (!p.opt.tile || p.opt.vec == 1 || p.ndim != 2 || p.slab) return false;
     if (p.hc != 0 && p.hc != 2 && p.hc != 4 && p.hc != 8) return false;
     // ragged grids (e.g. the reference's 100^2) run with partial edge tiles; the window must not wrap onto itself
-    const TileShape shp = tile_shape_for<T>(p, adjoint);
+    const TileVariant shp = tile_variant_for<T>(p, adjoint);
     auto fits = [](int64_t n, int64_t b) { return (n + b - 1) / b * b + 16 <= 2 * n; };        // one wrap per window coordinate
     if (p.W % pi::vec_width<T>::value || !fits(p.n0, shp.by < TILE_B ? TILE_B : shp.by) || !fits(p.W, shp.bx)) return false;
     // the adjoint tile kernel owns one partial row per workgroup: beyond MAX_BWD_BLOCKS tiles the grid-stride
@@ -764,6 +855,16 @@ bool tile_eligible(const Problem& p, std::initializer_list<const void*> ptrs, bo
     if (p.opt.tile == 1 && p.n >= (adjoint ? (5 << 18) : (3 << 20))) return false;
     for (const void* q : ptrs)
         if (q && (reinterpret_cast<uintptr_t>(q) % 16)) return false;
+    return true;
+}
+
+// tiles for the B samples of one launch (B = 1: tile_eligible): the per-sample rules, with the size limits of the "tile = 1" rule
+// applied to the points of the whole batch (the tile kernels pay while the launches are latency-bound: 100^2 x 64 still is)
+template <typename T>
+bool batch_tile(const Problem& p, int batch, std::initializer_list<const void*> ptrs, bool adjoint)
+{
+    if (!tile_eligible<T>(p, ptrs, adjoint)) return false;
+    if (p.opt.tile == 1 && (int64_t)batch * p.n >= (adjoint ? (5 << 18) : (3 << 20))) return false;
     return true;
 }
 
@@ -858,16 +959,17 @@ hipError_t launch_adj_tile(const T* hframe_t, const T* gframe_t, T* aframe_t, un
     return s.ens() ? go(ens, s.ens_rows) : go(pi::pi_adj2d_tile_kernel<T, HC, K, BX, BY, NT, MOM, long>);
 }
 
+// from the TileVariant `v` of the launch to its specialisation (the 32-wide ones; the order is tile_variant_for's)
 #define PI_TILE_VARIANTS(CALL, HC)                                              \
     do {                                                                        \
-        if (p.opt.tile_k == 2) return CALL(HC, 2, 256);                         \
+        if (v.k == 2) return CALL(HC, 2, 256);                                  \
         if constexpr (HC == pi::POLY) {                                         \
-            if (p.opt.tile_k == 8) return CALL(HC, 8, 1024);                    \
-            if (p.opt.tile_nt == 1024) return CALL(HC, 4, 1024);                \
-            if (tile_by_for(p) == 16) return CALL(HC, 4, 320, 16);              \
-            if (tile_by_for(p) == 8) return CALL(HC, 4, 256, 8);                \
+            if (v.k == 8) return CALL(HC, 8, 1024);                             \
+            if (v.nt == 1024) return CALL(HC, 4, 1024);                         \
+            if (v.by == 16) return CALL(HC, 4, 320, 16);                        \
+            if (v.by == 8) return CALL(HC, 4, 256, 8);                          \
         }                                                                       \
-        if (p.opt.tile_nt == 256) return CALL(HC, 4, 256);                      \
+        if (v.nt == 256) return CALL(HC, 4, 256);                               \
         return CALL(HC, 4, 512);                                                \
     } while (0)
 #define PI_TILE_DISPATCH(CALL)                                                  \
@@ -884,10 +986,11 @@ hipError_t launch_adj_tile(const T* hframe_t, const T* gframe_t, T* aframe_t, un
 template <typename T>
 hipError_t fwd_tile(T* frame_t, const T* P, const Problem& p, hipStream_t st, const Samples& s = {})
 {
+    const TileVariant v = tile_variant_for<T>(p, false);
     if constexpr (sizeof(T) == 4) {
-        switch (tile_wide_for<T>(p, false)) {
-            case 1: return launch_fwd_tile<T, pi::POLY, 4, 640, 40, 32>(frame_t, P, p, st, s);
-            case 2: return launch_fwd_tile<T, pi::POLY, 4, 768, 40, 40>(frame_t, P, p, st, s);
+        switch (v.nt) {                                        // the wide shapes
+            case 640: return launch_fwd_tile<T, pi::POLY, 4, 640, 40, 32>(frame_t, P, p, st, s);
+            case 768: return launch_fwd_tile<T, pi::POLY, 4, 768, 40, 40>(frame_t, P, p, st, s);
             default: break;
         }
     }
@@ -896,39 +999,24 @@ hipError_t fwd_tile(T* frame_t, const T* P, const Problem& p, hipStream_t st, co
 #undef CALL_FT
 }
 
-// the fused-moments flavour exists for one variant: float32 poly blocks, K = 4, 32 x 32 tiles, 512 threads
-template <typename T>
-bool tile_fuse_ok(const Problem& p)
-{
-    // measured on MI355X (backward us per step, split -> fused): 384^2 3.37 -> 3.20, 512^2 3.90 -> 3.29, 1000^2 13.4 -> 11.3;
-    // in the 16-row-tile regime (<= 128 tiles of 32x32, e.g. the reference's 100^2) the extra VALU work sits on the one
-    // critical workgroup chain and loses (2.26 -> 2.66), so it keeps the split schedule
-    // float64 (lambda-omega): the per-lane moment sums live in LDS and are updated with ds_add_f64 (pi_tile2d.h) -- a register
-    // flavour needed more than the 256 registers of a 512-thread workgroup (57 spilled doubles, 5.98 -> 9.13 us per step,
-    // profiles/r02_fp64_fused_tile_sweep.txt); with LDS accumulators: 186 VGPRs, no scratch, lambda-omega 512^2 backward
-    // 5.45 -> 4.48 us per step, 1024^2 19.1 -> 15.9 (profiles/r02_fp64_fused_lds_accumulators.txt)
-    return p.opt.tile_fuse && !p.opt.skip_wgrad && p.hc == 0 &&
-           p.opt.tile_k == 4 && p.opt.tile_nt == 512 && (tile_by_for(p) == TILE_B || tile_wide_for<T>(p, true) != 0);
-}
-
 template <typename T>
 hipError_t adj_tile(const T* hframe_t, const T* gframe_t, T* aframe_t, unsigned inj_mask, T* g_h0, int steps_to_zero,
                     double* partials, const T* P, const Problem& p, hipStream_t st, const Samples& s = {},
                     const pi::ObsTile* ob = nullptr)
 {
+    const TileVariant v = tile_variant_for<T>(p, true);
     if constexpr (sizeof(T) == 4) {
-        const bool fused = tile_fuse_ok<T>(p);
 #define CALL_WIDE(NT, BY, BX, MOM)                                                                                                  \
     launch_adj_tile<T, pi::POLY, 4, NT, BY, MOM, BX>(hframe_t, gframe_t, aframe_t, inj_mask, g_h0, steps_to_zero, partials, P, p, st, \
                                                      s, ob)
-        switch (tile_wide_for<T>(p, true)) {
-            case 1: return fused ? CALL_WIDE(640, 40, 32, true) : CALL_WIDE(640, 40, 32, false);
-            case 2: return fused ? CALL_WIDE(768, 40, 40, true) : CALL_WIDE(768, 40, 40, false);
+        switch (v.nt) {                                        // the wide shapes
+            case 640: return v.mom ? CALL_WIDE(640, 40, 32, true) : CALL_WIDE(640, 40, 32, false);
+            case 768: return v.mom ? CALL_WIDE(768, 40, 40, true) : CALL_WIDE(768, 40, 40, false);
             default: break;
         }
 #undef CALL_WIDE
     }
-    if (tile_fuse_ok<T>(p))
+    if (v.mom)
         return launch_adj_tile<T, pi::POLY, 4, 512, TILE_B, true>(hframe_t, gframe_t, aframe_t, inj_mask, g_h0,
                                                                   steps_to_zero, partials, P, p, st, s, ob);
 #define CALL_AT(HC, K, NT, ...) \
@@ -948,22 +1036,24 @@ size_t persist_outbox_bytes(const Problem& p, int elem = 4)     // per band valu
 // placement words of the 32 x 32 resident forward (PersistArgs::xcc): one per tile, zeroed before the launch
 size_t persist_xcc_bytes(const Problem& p) { return align_up((size_t)((p.n0 / TILE_B) * (p.W / TILE_B)) * sizeof(unsigned), 16); }
 
+// The four predicates below (persist_ok, fwd_persist_ok, persist_small_ok, fwd_persist_small_by) say what a resident 2D kernel
+// assumes of the problem, of the tile variant `v` the launch-per-group path would run and of the device.  What the CALL adds --
+// tiles apply at all, the loss form, a stream that is not being captured -- is plan_fwd's / plan_sweep's, their only caller.
+
 // can the tile sweep of this rollout run as one cooperative launch?  (everything the kernel assumes, checked here)
 template <typename T>
-bool persist_ok(const Problem& p, const unsigned char* mask, int t_top, int ngroups, hipStream_t st)
+bool persist_ok(const Problem& p, const TileVariant& v, bool masked, int t_top, int ngroups)
 {
     // (float64 since round 5: the split flavour on 16-byte granules, moments in shared LDS rows; option adj_persist_f64)
     if (!p.opt.tile_persist || ngroups < 2) return false;
     if (sizeof(T) != 4 && (!p.opt.adj_persist_f64 || !p.opt.persist_split)) return false;
     if (persist_disabled_here()) return false;               // a launch aborted on this device (see PersistGuard)
-    if (mask && t_top >= 4096) return false;                 // the frame mask travels as a kernel argument (4096 bits)
-    if (!tile_fuse_ok<T>(p) || tile_wide_for<T>(p, true) != 0 || tile_by_for(p) != TILE_B) return false;
+    if (masked && t_top >= 4096) return false;               // the frame mask travels as a kernel argument (4096 bits)
+    if (!v.mom || v.by != TILE_B) return false;              // the fused-moments sweep on 32 x 32 tiles
     if (p.n0 % TILE_B || p.W % TILE_B) return false;
     const int64_t tiles = (p.n0 / TILE_B) * (p.W / TILE_B);
     const int cus = device_cu_count();
     if (tiles < 16 || cus <= 0 || tiles > cus) return false;          // (tiny grids: the 8-row tile kernels are faster anyway)
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return false;
     return true;
 }
 
@@ -1106,7 +1196,7 @@ hipError_t launch_adj_persist(const T* hframe_t, const T* gframe_t, T* aframe_t,
 
 // ---- resident FORWARD (pi_fwd2d_persist_kernel): the same grids, the same residency protocol ----------------------------------
 template <typename T>
-bool fwd_persist_ok(const Problem& p, int ngroups, hipStream_t st)
+bool fwd_persist_ok(const Problem& p, const TileVariant& v, int ngroups)
 {
     // (eight groups at least: short rollouts -- the step loop's speculative groups of 8 / 16 steps among them -- keep the
     // launch-per-group kernel and with it a host that never waits for the stream)
@@ -1114,14 +1204,12 @@ bool fwd_persist_ok(const Problem& p, int ngroups, hipStream_t st)
     if (!p.opt.tile_persist || !p.opt.fwd_persist || (sizeof(T) != 4 && !p.opt.fwd_persist_f64) || ngroups < 8) return false;
     if (persist_disabled_here()) return false;
     // what the launch-per-group path would run as pi_fwd2d_tile_kernel<float, poly, 4, 32, 32, 512> (the trajectory is that kernel's)
-    if (p.hc != 0 || p.opt.tile_k != 4 || p.opt.tile_nt != 512 || tile_by_for(p) != TILE_B || tile_wide_for<T>(p, false) != 0) return false;
+    if (p.hc != 0 || v.k != 4 || v.nt != 512 || v.by != TILE_B) return false;
     if (p.n0 % TILE_B || p.W % TILE_B) return false;
     const int64_t tiles = (p.n0 / TILE_B) * (p.W / TILE_B);
     const int cus = device_cu_count();
     // (its 77 KB workgroups fit two per CU: up to 2 x #CUs tiles, option fwd_persist_per_cu; the launch asks the runtime)
     if (tiles < 16 || cus <= 0 || tiles > (int64_t)cus * p.opt.fwd_persist_per_cu) return false;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st && (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)) return false;
     return true;
 }
 
@@ -1176,18 +1264,16 @@ size_t persist_small_outbox_bytes(const Problem& p, int elem)
 }
 
 template <typename T>
-bool persist_small_ok(const Problem& p, const unsigned char* mask, int t_top, int ngroups, hipStream_t st)
+bool persist_small_ok(const Problem& p, const TileVariant& v, bool masked, int t_top, int ngroups)
 {
     if (!p.opt.tile_persist || !p.opt.persist_small || sizeof(T) != 4 || ngroups < 2 || p.hc != 0) return false;
     if (persist_disabled_here()) return false;
-    if (mask && t_top >= 4096) return false;
-    const int by = tile_by_for(p);
-    if (p.opt.tile_k != 4 || p.opt.tile_nt != 512 || tile_wide_for<T>(p, true) != 0 || by >= TILE_B || tile_fuse_ok<T>(p)) return false;
-    const int64_t tiles = persist_small_tiles(p, by);
+    if (masked && t_top >= 4096) return false;
+    // (the 8- and 16-row tiles tile_by_for picks, not those an explicit tile_by sets next to tile_nt = 256)
+    if (p.opt.tile_k != 4 || p.opt.tile_nt != 512 || v.by >= TILE_B || v.mom) return false;
+    const int64_t tiles = persist_small_tiles(p, v.by);
     const int cus = device_cu_count();
     if (tiles < 2 || cus <= 0 || tiles > cus || tiles > 256) return false;    // one workgroup per CU at most: resident for sure
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return false;
     return true;
 }
 
@@ -1232,24 +1318,24 @@ hipError_t launch_adj_persist_small_t(const T* hframe_t, const T* gframe_t, T* a
 // 1.20 -> 1.01, 384 x 320 1.20 -> 1.01, 352^2 1.33 -> 1.20) while the 32-row sweep still wins (1.93 vs 2.04): the forward alone
 // takes 16 rows.  Every kernel's trajectory is the same bit for bit.
 template <typename T>
-bool fwd_prefers_16_rows(const Problem& p)
+bool fwd_prefers_16_rows(const Problem& p, const TileVariant& v)
 {
     if (sizeof(T) != 4 || !p.opt.persist_small || !p.opt.fwd_small_half || p.opt.tile_by != 0 || p.hc != 0) return false;
-    if (p.n0 % TILE_B || p.W % TILE_B || tile_by_for(p) != TILE_B) return false;
+    if (p.n0 % TILE_B || p.W % TILE_B || v.by != TILE_B) return false;
     const int64_t tiles32 = (p.n0 / TILE_B) * (p.W / TILE_B), tiles16 = (p.n0 / 16) * (p.W / TILE_B);
     const int cus = device_cu_count();
     return tiles32 > 112 && tiles32 <= 128 && cus > 0 && tiles16 <= std::min<int64_t>(cus, 256);
 }
 
 template <typename T>
-int fwd_persist_small_by(const Problem& p, int ngroups, hipStream_t st)
+int fwd_persist_small_by(const Problem& p, const TileVariant& v, int ngroups)
 {
     // (eight groups at least, as the 32 x 32 resident forward: short rollouts -- the step loop's speculative groups among them --
     // keep the launch-per-group kernel and a host that never waits for the stream)
     if (!p.opt.tile_persist || !p.opt.persist_small || !p.opt.fwd_persist || sizeof(T) != 4 || ngroups < 8 || p.hc != 0) return 0;
     if (persist_disabled_here()) return 0;
-    if (p.opt.tile_k != 4 || p.opt.tile_nt != 512 || tile_wide_for<T>(p, false) != 0) return 0;
-    const int by = tile_by_for(p);
+    if (p.opt.tile_k != 4 || p.opt.tile_nt != 512 || v.by > TILE_B) return 0;       // (nor the wide shapes)
+    const int by = v.by;
     // Measured (profiles/r05_small_tile_resident_forward.txt, us per forward step, launch per group -> resident): 32 x 8 tiles
     // 100^2 1.23 -> 1.08, 256^2 1.22 -> 1.14; 32 x 16 tiles (300 x 320) 1.46 -> 1.63 and ragged 32 x 32 tiles (500^2) 1.92 -> 2.28:
     // whole-tile granules and an un-overlapped hand-over only pay where the sub-steps are short -> the 8-row regime by default,
@@ -1266,8 +1352,6 @@ int fwd_persist_small_by(const Problem& p, int ngroups, hipStream_t st)
     // the launch asks the runtime how many fit, the roll call decides)
     const int64_t max_tiles = p.opt.persist_small >= 2 ? (int64_t)cus * 2 * p.opt.fwd_persist_per_cu : std::min<int64_t>(cus, 256);
     if (tiles < 2 || cus <= 0 || tiles > max_tiles) return 0;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st && (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)) return 0;
     return by;
 }
 
@@ -1325,6 +1409,114 @@ hipError_t launch_adj_persist_small(const T* hframe_t, const T* gframe_t, T* afr
     if (p.opt.adj_small_half)
         return launch_adj_persist_small_t<T, 8, 512, true>(hframe_t, gframe_t, aframe_t, g_h0, t_top, mask, ngroups, partials, outbox, sync, P, p, st);
     return launch_adj_persist_small_t<T, 8, 256>(hframe_t, gframe_t, aframe_t, g_h0, t_top, mask, ngroups, partials, outbox, sync, P, p, st);
+}
+
+// ---- the rollout plan ------------------------------------------------------------------------------
+// What a rollout call runs on, decided once: the forward entry points ask plan_fwd, the sweeps plan_sweep, each at its top, and
+// then only follow the answer; the plan queries print the same answers (plan_rollout).  Nothing here names a kernel: whether a
+// resident grid really fits is asked by its launcher (persist_fits), whose refusal the callers treat as ResidentRun::fall_back.
+// (The slab rollouts plan for themselves: slab_rollout_bwd_impl sums gradients in the sweep by a rule of its own.)
+enum class FwdResident { none, tile32, small };                 // pi_fwd2d_persist_kernel | pi_fwd2d_persist_small_kernel
+enum class SweepResident { none, tile32, tile_small, res3d };   // pi_adj2d_persist[_split]_kernel | ..._small_kernel | pi_res3d.h
+
+// no resident 2D launch into a stream that is being captured (the host waits for its roll call)
+inline bool stream_capturing(hipStream_t st)
+{
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    return st && (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone);
+}
+
+struct FwdPlan {
+    bool tiles;                          // groups of tile.k steps per launch while they fit, the rest step by step
+    TileVariant tile;
+    FwdResident resident;                // the first ngroups groups as ONE launch (small: on tiles of small_by rows)
+    int small_by, ngroups;
+};
+
+// ptrs: the call's buffers (alignment), none = aligned; nsteps: the steps of the call; s: the samples of its launches
+template <typename T>
+FwdPlan plan_fwd(const Problem& p, std::initializer_list<const void*> ptrs, int nsteps, const Samples& s, hipStream_t st)
+{
+    FwdPlan f{batch_tile<T>(p, s.batch, ptrs, false), tile_variant_for<T>(p, false), FwdResident::none, 0, 0};
+    if (!f.tiles || s.on || f.tile.k != 4) return f;           // (the resident kernels have no sample flavour)
+    f.ngroups = nsteps / f.tile.k;
+    // whole groups of four steps as ONE launch of resident workgroups where the grid allows (pi_fwd2d_persist_kernel: the
+    // launch-per-group kernel's trajectory bit for bit), and the grids the 32 x 32 flavour does not take -- small-tile regime,
+    // ragged grids, fewer than 16 tiles -- on pi_fwd2d_persist_small_kernel (round 5; float32)
+    if (fwd_persist_ok<T>(p, f.tile, f.ngroups)) {
+        f.small_by = fwd_prefers_16_rows<T>(p, f.tile) ? 16 : 0;
+        f.resident = f.small_by ? FwdResident::small : FwdResident::tile32;
+    } else if ((f.small_by = fwd_persist_small_by<T>(p, f.tile, f.ngroups)) != 0) {
+        f.resident = FwdResident::small;
+    }
+    if (f.resident != FwdResident::none && stream_capturing(st)) f.resident = FwdResident::none;
+    return f;
+}
+
+struct SweepPlan {
+    bool tiles;                          // groups of tile.k adjoint steps per launch while they fit, the rest step by step
+    TileVariant tile;
+    bool direct_sweep;                   // every step is a launch of its own, of a family that can sum all gradients
+    bool fuse;                           // gradients summed inside the sweep's launches (tiles: tile.mom; steps: WGRAD)
+    bool pass;                           // a time-parallel gradient pass follows the sweep
+    SweepResident resident;              // the whole sweep (tiles: its first ngroups groups) as ONE launch
+    int ngroups;
+    Res3dPlan res3d;
+};
+
+// ptrs: the call's buffers; t_top: the frame the sweep starts from; masked: a frame mask selects the injected frames; loss: the
+// sweep forms dL/dtraj itself (pi::LossInj, already in p.loss); s: the samples of its launches
+template <typename T>
+SweepPlan plan_sweep(const Problem& p, std::initializer_list<const void*> ptrs, int t_top, bool masked, bool loss, const Samples& s,
+                     hipStream_t st)
+{
+    SweepPlan w{batch_tile<T>(p, s.batch, ptrs, true), tile_variant_for<T>(p, true)};
+    // fused gradient reduction only where the per-step kernels sweep EVERY step (no tile launches) on a family that has a
+    // fused flavour (the plane-streaming one: stream_fuses; the sample launches never stream)
+    const bool streams = !s.on && stream3d_vec<T>(p, ptrs, true) != 0;
+    w.direct_sweep = !w.tiles && (!streams || stream_fuses<T>(p));
+    const bool tile_fused = w.tiles && w.tile.mom;
+    // (float64 pre-contracted blocks too since round 2: per-lane double accumulators; lambda-omega beyond the tile regime,
+    // backward per step 1200^2 29.0 -> 25.1 us, 2048^2 71.5 -> 60.4, 3072^2 187 -> 143 -- no pi_moments_kernel pass)
+    w.fuse = tile_fused || (w.direct_sweep && !p.opt.skip_wgrad && p.hc != -1 &&
+                            (p.opt.fuse_wgrad == 1 || (p.opt.fuse_wgrad == 2 && p.hc == 0)));
+    w.pass = !p.opt.skip_wgrad && p.hc != -1 && !w.fuse;
+    w.resident = SweepResident::none;
+    if (s.on) return w;                                        // (the resident kernels have no sample flavour)
+    if (w.tiles) {
+        w.ngroups = w.tile.k == 4 ? t_top / 4 : 0;
+        // the whole tile sweep as ONE cooperative launch where that applies (pi_adj2d_persist_kernel); its granule outbox lives
+        // in the three adjoint frames between the hand-over frame and the group above it, which nobody touches then
+        if (tile_fused && persist_ok<T>(p, w.tile, masked, t_top, w.ngroups) &&
+            persist_outbox_bytes(p, (int)sizeof(T)) <= (size_t)(w.tile.k - 1) * 2 * p.n * sizeof(T))
+            w.resident = SweepResident::tile32;
+        // the small-tile regime (32 x 8 / 32 x 16 tiles, split schedule): the same, with every adjoint frame written and the
+        // granule outbox behind the partial rows
+        else if (!tile_fused && !loss && persist_small_ok<T>(p, w.tile, masked, t_top, w.ngroups))
+            w.resident = SweepResident::tile_small;
+        if (w.resident != SweepResident::none && stream_capturing(st)) w.resident = SweepResident::none;
+    } else if (w.direct_sweep && w.fuse && !loss && res3d_plan(p, t_top, sizeof(T), w.res3d)) {
+        // 3D float32 pre-contracted blocks on whole 16 x 16 x 32 blocks: the whole sweep as ONE resident launch (pi_res3d.h), the
+        // gradient sums carried along (resident_begin refuses a stream that is being captured)
+        w.resident = SweepResident::res3d;
+    }
+    return w;
+}
+
+// both halves for the queries: 16-byte-aligned buffers, no frame mask, the plain injection form, the null stream, and one length
+// that every resident kernel accepts (ngroups >= 8, 16 <= nsteps < 4096)
+struct RolloutPlan { FwdPlan fwd; SweepPlan sweep; };
+template <typename T>
+RolloutPlan plan_rollout(const Problem& p, const Samples& s = {})
+{
+    return {plan_fwd<T>(p, {}, 1024, s, nullptr), plan_sweep<T>(p, {}, 1024, false, false, s, nullptr)};
+}
+
+// the family and planes per pass percnn_pi_debug_plan reports for one direction: the tile groups', else the step launches'
+template <typename T>
+StepRoute rollout_route(const Problem& p, bool tiles, bool adjoint, bool wgrad)
+{
+    return tiles ? StepRoute{TILES, 1, (int)pi::vec_width<T>::value} : step_route<T>(p, {}, adjoint, wgrad);
 }
 
 // ---- workspace carving -------------------------------------------------------------------------
@@ -1874,29 +2066,21 @@ int rollout_fwd_impl(T* traj, const T* P, int hc, int ndim, const int64_t* shape
     auto st = static_cast<hipStream_t>(stream);
     const size_t frame = (size_t)2 * p.n;
     int t = 0;
-    if (tile_eligible<T>(p, {traj}, false)) {
-        const int K = (p.opt.tile_k == 8 && p.hc != 0) ? 4 : p.opt.tile_k;
-        // whole groups of four steps as ONE launch of resident workgroups where the grid allows (pi_fwd2d_persist_kernel: the
-        // launch-per-group kernel's trajectory bit for bit); an aborted launch is recomputed below, launch by launch
-        {
-            const int ngroups = K == 4 ? T_steps / K : 0;
-            const bool big = fwd_persist_ok<T>(p, ngroups, st);
-            // ... and the grids the 32 x 32 flavour does not take -- small-tile regime, ragged grids, fewer than 16 tiles -- on
-            // pi_fwd2d_persist_small_kernel (round 5; float32)
-            int small_by = 0;
-            if constexpr (sizeof(T) == 4) small_by = big ? (fwd_prefers_16_rows<T>(p) ? 16 : 0) : fwd_persist_small_by<T>(p, ngroups, st);
-            if (big || small_by) {
-                hipError_t e;
-                if constexpr (sizeof(T) == 4)
-                    e = (big && !small_by) ? launch_fwd_persist<T>(traj, ngroups, P, p, st)
-                            : launch_fwd_persist_small<T>(small_by, traj, ngroups, P, p, st);
-                else
-                    e = launch_fwd_persist<T>(traj, ngroups, P, p, st);
-                switch (resident_outcome(e)) {
-                case ResidentRun::ran: t = K * ngroups; break;
-                case ResidentRun::fatal: return (int)e;
-                default: break;                             // frames it may have written are recomputed below
-                }
+    const FwdPlan plan = plan_fwd<T>(p, {traj}, T_steps, Samples{}, st);
+    if (plan.tiles) {
+        const int K = plan.tile.k;
+        // the resident launch of the first groups; an aborted one is recomputed below, launch by launch
+        if (plan.resident != FwdResident::none) {
+            hipError_t e;
+            if constexpr (sizeof(T) == 4)
+                e = plan.resident == FwdResident::tile32 ? launch_fwd_persist<T>(traj, plan.ngroups, P, p, st)
+                        : launch_fwd_persist_small<T>(plan.small_by, traj, plan.ngroups, P, p, st);
+            else
+                e = launch_fwd_persist<T>(traj, plan.ngroups, P, p, st);
+            switch (resident_outcome(e)) {
+            case ResidentRun::ran: t = K * plan.ngroups; break;
+            case ResidentRun::fatal: return (int)e;
+            default: break;                             // frames it may have written are recomputed below
             }
         }
         for (; t + K <= T_steps; t += K)
@@ -1973,17 +2157,8 @@ int rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* mask, 
     //    stream (the sweep is latency-bound, the reduction HBM-bound); partial rows are disjoint columns.
     const bool vec_ok = (p.n % pi::vec_width<T>::value == 0) && p.opt.vec != 1 &&
                         (reinterpret_cast<uintptr_t>(traj) % 16 == 0);
-    // fused gradient reduction only where the per-step direct kernels sweep EVERY step (no tile launches, no plane
-    // streaming): the other kernel families have no fused flavour
-    // (the streaming kernel's fused flavour exists for float32 poly mode)
-    const bool f32poly = hc == 0 && sizeof(T) == 4;
-    const bool direct_sweep = !tile_eligible<T>(p, {traj, g_traj, g_h0, adj}, true) &&
-                              (f32poly || !stream3d_vec<T>(p, {traj, g_traj, g_h0, adj}, true));
-    const bool tile_fused = !direct_sweep && tile_eligible<T>(p, {traj, g_traj, g_h0, adj}, true) && tile_fuse_ok<T>(p);
-    // (float64 pre-contracted blocks too since round 2: per-lane double accumulators; lambda-omega beyond the tile regime,
-    // backward per step 1200^2 29.0 -> 25.1 us, 2048^2 71.5 -> 60.4, 3072^2 187 -> 143 -- no pi_moments_kernel pass)
-    const bool fuse = tile_fused || (direct_sweep && !p.opt.skip_wgrad && hc != -1 &&
-                                     (p.opt.fuse_wgrad == 1 || (p.opt.fuse_wgrad == 2 && hc == 0)));
+    const SweepPlan plan = plan_sweep<T>(p, {traj, g_traj, g_h0, adj}, t_top, mask != nullptr, loss != nullptr, Samples{}, st);
+    const bool direct_sweep = plan.direct_sweep, fuse = plan.fuse;
     // The top frame's dL/dh is dL/dtraj[t_top] itself.  Where every step is its own launch and nobody else reads the adjoint
     // trajectory (fused gradient sums), the first step reads it where it lies instead of from a copy in adj[t_top] -- at 256^3
     // that copy is 128 MiB, ~45 us of a 10-step rollout (round 5)
@@ -1992,15 +2167,14 @@ int rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* mask, 
         if (hipError_t e = top_frame(t_top, adj + (size_t)t_top * frame)) return (int)e;
     unsigned rows = 0, wrows = 0;
     auto reduce_range = [&](int lo, int hi, hipStream_t s2) -> hipError_t {      // steps (lo, hi]
-        if (hi <= lo || p.opt.skip_wgrad || fuse) return hipSuccess;
+        if (hi <= lo || !plan.pass) return hipSuccess;
         unsigned r = 0;
         hipError_t e = vec_ok ? launch_wgrad<T, pi::vec_width<T>::value>(traj, adj, w.partials, P, p, lo, hi, &r, s2)
                               : launch_wgrad<T, 1>(traj, adj, w.partials, P, p, lo, hi, &r, s2);
         if (r > wrows) wrows = r;
         return e;
     };
-    SideStream* ss = (p.opt.overlap && !p.opt.skip_wgrad && !fuse && t_top >= 2 * p.opt.overlap_chunk)
-                         ? side_stream() : nullptr;
+    SideStream* ss = (p.opt.overlap && plan.pass && t_top >= 2 * p.opt.overlap_chunk) ? side_stream() : nullptr;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (ss && (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)) ss = nullptr;
     int reduced_above = t_top;                       // steps (reduced_above, t_top] are already handed to the reduction
@@ -2029,34 +2203,22 @@ int rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* mask, 
         default: return 0;
         }
     };
-    if (tile_eligible<T>(p, {traj, g_traj, g_h0, adj}, true)) {
-        const int K = (p.opt.tile_k == 8 && p.hc != 0) ? 4 : p.opt.tile_k;
+    if (plan.tiles) {
+        const int K = plan.tile.k, ngroups = plan.ngroups;
+        const int t_end = t_top - K * ngroups;                   // where a resident launch of the first groups hands over
+        // roll-call / abort words: the last partial row (zeroed above; tiles <= #CUs << MAX_BWD_BLOCKS rows are in use)
+        unsigned* sync = reinterpret_cast<unsigned*>(w.partials + (size_t)(MAX_BWD_BLOCKS - 1) * pi::nparams(p.hc));
         rows = (unsigned)tile_count<T>(p, true);
-        // the whole tile sweep as ONE cooperative launch where that applies (pi_adj2d_persist_kernel); its granule outbox
-        // lives in the three adjoint frames between the hand-over frame and the group above it, which nobody touches then
-        {
-            const int ngroups = K == 4 ? t_cur / K : 0;
-            if (tile_fused && ngroups >= 2 && persist_ok<T>(p, mask, t_cur, ngroups, st) &&
-                persist_outbox_bytes(p, (int)sizeof(T)) <= (size_t)(K - 1) * frame_bytes) {
-                const int t_end = t_cur - K * ngroups;
-                auto* outbox = reinterpret_cast<unsigned long long*>(adj + (size_t)(t_end + 1) * frame);
-                // roll-call / abort words: the last partial row (zeroed above; tiles <= #CUs << MAX_BWD_BLOCKS rows are in use)
-                unsigned* sync = reinterpret_cast<unsigned*>(w.partials + (size_t)(MAX_BWD_BLOCKS - 1) * pi::nparams(p.hc));
-                if (int rc = resident_sweep(launch_adj_persist<T>(traj + (size_t)t_cur * frame, g_traj + (size_t)t_cur * frame,
-                                                                  adj + (size_t)t_cur * frame, t_end == 0 ? g_h0 : nullptr, t_cur,
-                                                                  mask, ngroups, w.partials, outbox, sync, P, p, st), t_end))
-                    return rc;
-            }
+        if (plan.resident == SweepResident::tile32) {           // granule outbox: the three adjoint frames above the hand-over frame
+            auto* outbox = reinterpret_cast<unsigned long long*>(adj + (size_t)(t_end + 1) * frame);
+            if (int rc = resident_sweep(launch_adj_persist<T>(traj + (size_t)t_cur * frame, g_traj + (size_t)t_cur * frame,
+                                                              adj + (size_t)t_cur * frame, t_end == 0 ? g_h0 : nullptr, t_cur,
+                                                              mask, ngroups, w.partials, outbox, sync, P, p, st), t_end))
+                return rc;
         }
-        // the small-tile regime (32 x 8 tiles, split schedule): the same, with every adjoint frame written and the granule
-        // outbox behind the partial rows
         if constexpr (sizeof(T) == 4) {
-            const int ngroups = K == 4 ? t_cur / K : 0;
-            if (t_cur == t_top && !tile_fused && !loss && ngroups >= 2 && persist_small_ok<T>(p, mask, t_cur, ngroups, st) &&
-                ws_bytes >= rollout_workspace_bytes(p, T_steps, sizeof(T))) {
-                const int t_end = t_cur - K * ngroups;
+            if (plan.resident == SweepResident::tile_small) {   // granule outbox: behind the partial rows (rollout_workspace_bytes)
                 auto* outbox = reinterpret_cast<unsigned long long*>(reinterpret_cast<unsigned char*>(w.partials) + w.partials_bytes);
-                unsigned* sync = reinterpret_cast<unsigned*>(w.partials + (size_t)(MAX_BWD_BLOCKS - 1) * pi::nparams(p.hc));
                 if (int rc = resident_sweep(launch_adj_persist_small<T>(traj + (size_t)t_cur * frame, g_traj + (size_t)t_cur * frame,
                                                                         adj + (size_t)t_cur * frame, t_end == 0 ? g_h0 : nullptr, t_cur,
                                                                         mask, ngroups, w.partials, outbox, sync, P, p, st), t_end))
@@ -2073,14 +2235,12 @@ int rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* mask, 
             if (hipError_t e = hand_over(t_cur - K)) return (int)e;
         }
     }
-    // 3D float32 pre-contracted blocks on whole 16 x 16 x 32 blocks: the whole sweep as ONE resident launch (pi_res3d.h), the
-    // gradient sums carried along; aborted / not resident / not supported: the launch-per-step bricks below
+    // the resident 3D sweep; aborted / not resident / not supported: the launch-per-step kernels below
     if constexpr (sizeof(T) == 4) {
-        Res3dPlan rp;
-        if (t_cur == t_top && direct_sweep && fuse && !loss && res3d_plan(p, t_top, sizeof(T), rp)) {
+        if (plan.resident == SweepResident::res3d) {
             const T* gin = top_in_place ? top_in_place : adj + (size_t)t_top * frame;
-            if (int rc = resident_sweep(launch_adj_res3d(traj, g_traj, mask, gin, g_h0, t_top, w.partials, P, p, rp, st), 0)) return rc;
-            if (t_cur == 0) rows = (unsigned)rp.nblk;       // it ran (t_top >= 16 here): one partial row per block
+            if (int rc = resident_sweep(launch_adj_res3d(traj, g_traj, mask, gin, g_h0, t_top, w.partials, P, p, plan.res3d, st), 0)) return rc;
+            if (t_cur == 0) rows = (unsigned)plan.res3d.nblk;   // it ran (t_top >= 16 here): one partial row per block
         }
     }
     for (int t = t_cur; t >= 1; --t) {
@@ -2095,8 +2255,7 @@ int rollout_bwd_impl(const T* traj, const T* g_traj, const unsigned char* mask, 
         if (r2 > rows) rows = r2;
         if (hipError_t e2 = hand_over(t - 1)) return (int)e2;
     }
-    if (p.opt.skip_wgrad || hc == -1 || fuse)
-        return (int)finish_grads(w, rows, hc, param_grad, st);
+    if (!plan.pass) return (int)finish_grads(w, rows, hc, param_grad, st);
     if (ss) {
         // remaining steps (0, reduced_above] on the side stream too (ordered behind the earlier chunks), then join
         hipEvent_t ev = ss->ev[ss->next++ % 8];
@@ -2136,16 +2295,7 @@ int batch_problem(int hc, int ndim, const int64_t* shape, int batch, Problem& p,
 // tile launchers and the gradient pass are the unbatched ones (launch_fwd_tile, launch_adj_tile, launch_wgrad) given a
 // `Samples`; the direct and the brick launchers below are sample launchers of their own (no RZ, grid cap, XCD window, fused put).
 // Below its argument checks every batched / ensemble entry point runs one body: sample_rollout_fwd, sample_rollout_bwd.
-
-// tile vs direct: the per-sample rules of tile_eligible, with the size limits of the "tile = 1" rule applied to the points of
-// the whole batch (the tile kernels pay while the launches are latency-bound: 100^2 x 64 still is)
-template <typename T>
-bool batch_tile(const Problem& p, int batch, std::initializer_list<const void*> ptrs, bool adjoint)
-{
-    if (!tile_eligible<T>(p, ptrs, adjoint)) return false;
-    if (p.opt.tile == 1 && (int64_t)batch * p.n >= (adjoint ? (5 << 18) : (3 << 20))) return false;
-    return true;
-}
+// (tile vs direct: batch_tile, next to tile_eligible)
 
 template <typename T, int NDIM, int HC, int VEC>
 hipError_t launch_fwd_b(const T* h, T* out, const T* P, const Problem& p, hipStream_t st, const Samples& s)
@@ -2195,39 +2345,8 @@ hipError_t launch_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* par
     return e;
 }
 
-// brick3d = 1: which batches take the bricks by default (brick3d = 2: every eligible one).
-// Measured on one MI355X (profiles/batch_brick_throughput.json, tools/batch_brick_throughput.py: pi_rollout_batched + backward,
-// float32, k sample-steps/s, brick3d=0 -> brick3d=2, the routes alternating in one process, best of two 1 s regions; brick3d=0
-// against itself: within 0.12 % on every row):
-//   pre-contracted blocks   48^3 x 300, B = 8: 422.7 -> 443.2 (+4.9 %); B = 64: 724.2 -> 787.8 (+8.8 %); 128^3 x 32, B = 4: 40.06 -> 46.63 (+16.4 %)
-//   factored blocks, Hc = 2 48^3 x 300, B = 8: 372.3 -> 329.9 (-11.4 %); B = 64: 568.1 -> 512.7 (-9.8 %); 128^3 x 32, B = 4: 30.64 -> 29.72 (-3.0 %)
-// -> pre-contracted blocks of 48^3 .. 128^3 points per sample (110592 .. 2097152) in launches of at least 8 x 48^3 points, the
-// smallest batch that was measured; factored blocks lose everywhere and stay direct, as does every class without a figure
-// (smaller or larger samples, smaller launches): brick3d = 2 reaches the bricks there.  The class is (block kind, points per
-// sample, points per launch); float64 batches follow the float32 figures and have none of their own.
-bool batch_brick_default(const Problem& p, int batch)
-{
-    constexpr int64_t N_MIN = 48 * 48 * 48, N_MAX = 128 * 128 * 128;
-    return p.hc == 0 && p.n >= N_MIN && p.n <= N_MAX && (int64_t)batch * p.n >= 8 * N_MIN;
-}
-
 // ---- batch on bricks: the sample flavours of pi_fwd3d_brick_kernel / pi_adj3d_brick_kernel, grid (bricks of one sample, B) ----
-// Planes per brick of a batched / ensemble step launch, 0 = the direct kernels.  Per sample the rule is brick_rz_for's (256-lane
-// bricks: rows of up to 64 chunks); on top of it the lanes must be the 16-byte ones (`vec` is pick_vec's answer over the call's
-// pointers), the sample stride must keep every sample's base 16-byte aligned, the sparse-observation form (`obs`) and factored
-// blocks that need all gradients in the launch (`wgrad`, the rule of step_bwd) stay direct, and four-plane bricks have no sample
-// flavour.  brick_nt and brick_wide do not apply.  One function for the launchers, ens_rows_for and percnn_pi_debug_batch_plan.
-template <typename T>
-int batch_brick_rz(const Problem& p, int vec, int batch, bool adjoint, bool wgrad, bool obs)
-{
-    if (obs || batch < 2 || (adjoint && wgrad && p.hc != 0)) return 0;
-    if (((size_t)2 * p.n * sizeof(T)) % 16) return 0;
-    const int rz = brick_rz_for<T>(p, vec, adjoint, /*wide=*/false);
-    if (rz < 1 || rz > 2) return 0;
-    if (p.opt.brick3d == 1 && !batch_brick_default(p, batch)) return 0;
-    return rz;
-}
-
+// (which launches take them: batch_brick_rz, next to step_route)
 // workgroups per sample of the adjoint brick launch: brick_bwd_grid's rule with its cap spread over the batch -- max(1, cap / B)
 // per sample, never more than a sample has bricks, every workgroup about the same number of them; the whole launch plays the
 // part of the one sample there (more than two bricks per workgroup: the partial rows bound the grid, not the CUs)
@@ -2325,8 +2444,9 @@ hipError_t brick_bwd_b(int rz, bool mom, const T* h, const T* G, const T* inj, T
 template <typename T>
 hipError_t step_fwd_b(const T* h, T* out, const T* P, const Problem& p, hipStream_t st, const Samples& s)
 {
-    const int vec = pick_vec<T>(p, {h, out});
-    if (const int brz = batch_brick_rz<T>(p, vec, s.batch, false, false, false)) return brick_fwd_b<T>(brz, h, out, P, p, st, s);
+    const StepRoute r = step_route<T>(p, {h, out}, false, false, s);
+    const int vec = r.vec;
+    if (r.family == BRICKS) return brick_fwd_b<T>(r.planes, h, out, P, p, st, s);
 #define CALL_FWDB(NDIM, HC, VEC) launch_fwd_b<T, NDIM, HC, VEC>(h, out, P, p, st, s)
     PI_DISPATCH(CALL_FWDB);
 #undef CALL_FWDB
@@ -2337,9 +2457,9 @@ hipError_t step_bwd_b(const T* h, const T* G, const T* inj, T* Gp, double* parti
                       const Samples& s, unsigned* rows_out, const pi::ObsLat* ol = nullptr)
 {
     // (the compact target of the sparse-observation flavours is read element-wise: its alignment does not pick the lanes)
-    const int vec = pick_vec<T>(p, {h, G, ol ? nullptr : inj, Gp});
-    if (const int brz = batch_brick_rz<T>(p, vec, s.batch, true, WGRAD, ol != nullptr))
-        return brick_bwd_b<T>(brz, WGRAD, h, G, inj, Gp, partials, P, p, st, s, rows_out);
+    const StepRoute r = step_route<T>(p, {h, G, ol ? nullptr : inj, Gp}, true, WGRAD, s, ol != nullptr);
+    const int vec = r.vec;
+    if (r.family == BRICKS) return brick_bwd_b<T>(r.planes, WGRAD, h, G, inj, Gp, partials, P, p, st, s, rows_out);
 #define CALL_BWDB(NDIM, HC, VEC) launch_bwd_b<T, NDIM, HC, VEC, WGRAD>(h, G, inj, Gp, partials, P, p, st, s, rows_out, ol)
     PI_DISPATCH(CALL_BWDB);
 #undef CALL_BWDB
@@ -2396,8 +2516,9 @@ int sample_rollout_fwd(T* traj, const T* P, const Problem& p, int T_steps, hipSt
 {
     const size_t frame = (size_t)s.batch * 2 * p.n;        // frame t of all samples: [B][2][*S]
     int t = 0;
-    if (batch_tile<T>(p, s.batch, {traj}, false)) {
-        const int K = (p.opt.tile_k == 8 && p.hc != 0) ? 4 : p.opt.tile_k;
+    const FwdPlan plan = plan_fwd<T>(p, {traj}, T_steps, s, st);
+    if (plan.tiles) {
+        const int K = plan.tile.k;
         for (; t + K <= T_steps; t += K)
             if (hipError_t e = fwd_tile<T>(traj + (size_t)t * frame, P, p, st, s)) return (int)e;
     }
@@ -2613,10 +2734,8 @@ int sample_rollout_bwd(const T* traj, const T* g_traj, const unsigned char* mask
         if (has(0)) return (int)top_frame(0, g_h0);
         return (int)hipMemsetAsync(g_h0, 0, frame_bytes, st);
     }
-    const bool tile = batch_tile<T>(p, batch, {traj, g_traj, g_h0, adj}, true);
-    const bool fuse = tile ? tile_fuse_ok<T>(p)
-                           : (!p.opt.skip_wgrad && (p.opt.fuse_wgrad == 1 || (p.opt.fuse_wgrad == 2 && hc == 0)));
-    const bool pass = !p.opt.skip_wgrad && !fuse;          // time-parallel gradient pass after the sweep
+    const SweepPlan plan = plan_sweep<T>(p, {traj, g_traj, g_h0, adj}, t_top, mask != nullptr, loss != nullptr, s, st);
+    const bool tile = plan.tiles, fuse = plan.fuse, pass = plan.pass;
     // (1) the partial rows: batched -- all of them, the launches say how many they wrote (`rows`); ensemble -- ens_rows per sample
     if (ens) s.ens_rows = ens_rows_for<T>(p, batch, tile, pass ? t_top : 0);
     if (hipError_t e = hipMemsetAsync(w.partials, 0, ens ? (size_t)batch * s.ens_rows * pi::nparams(hc) * sizeof(double) : w.partials_bytes, st))
@@ -2629,7 +2748,7 @@ int sample_rollout_bwd(const T* traj, const T* g_traj, const unsigned char* mask
     unsigned rows = 0;
     int t_cur = t_top;
     if (tile) {
-        const int K = (p.opt.tile_k == 8 && p.hc != 0) ? 4 : p.opt.tile_k;
+        const int K = plan.tile.k;
         rows = (unsigned)tile_count<T>(p, true) * (unsigned)batch;
         for (; t_cur - K >= 0; t_cur -= K) {
             unsigned m = 0;
@@ -3193,13 +3312,14 @@ int batch_obs_sqerr_impl(const T* traj, const T* target_c, const unsigned char* 
 }  // namespace
 
 namespace {
-// Which kernel family a rollout of this problem runs on and how its backward is scheduled -- the library's own dispatch
-// rules, evaluated for 16-byte-aligned buffers (bench.py labels its roofline entries with it instead of mirroring the rules).
+// Which kernel family a rollout of this problem runs on and how its backward is scheduled: the answer of plan_fwd / plan_sweep
+// and step_route, the functions the rollout entry points themselves follow, asked as plan_rollout says (bench.py labels its
+// roofline entries with it).  The two functions below only copy fields; they hold no rule.
 // out = {forward family, adjoint family, gradients reduced inside the sweep launches (0 / 1), time steps per forward launch,
 //        per adjoint launch, planes per pass forward, adjoint, lanes per brick workgroup (0: no bricks), 2D tile width,
-//        height, lanes per tile workgroup of the adjoint (0: no tiles), the same three of the forward, 1 if the tile sweep of a
-//        long unmasked rollout runs as ONE persistent launch}; families: 0 direct, 1 2D tiles, 2 plane streaming, 3 3D bricks,
-//        4 advective block
+//        height, lanes per tile workgroup of the adjoint (0: no tiles), the same three of the forward, bit 0: the sweep runs as
+//        ONE resident launch (2D tiles, or the 3D resident sweep), bit 1: the forward does (both 0 without a device to ask for
+//        its CU count)}; families: enum Family
 int debug_handover_local(const Problem& p, int elem_size, int* out);
 // query_ok: the caller's `out` may be the buffer of the per-call query debug_handover_local = N (percnn_pi_debug_plan only)
 template <typename T>
@@ -3208,52 +3328,19 @@ int debug_plan_impl(int hc, int ndim, const int64_t* shape, const char* options,
     Problem p;
     if (int rc = make_problem(hc, ndim, shape, false, p, options, false)) return rc;
     if (p.opt.debug_handover_local) return query_ok ? debug_handover_local(p, (int)sizeof(T), out) : (int)PERCNN_PI_EINVAL;
-    const int vec = pick_vec<T>(p, {});
-    auto family = [&](bool adjoint, bool wgrad, int& planes) {
-        planes = 1;
-        if (p.hc == -1) return 4;
-        if (tile_eligible<T>(p, {}, adjoint)) return 1;
-        if (!adjoint || !wgrad || (p.hc == 0 && sizeof(T) == 4))
-            if (stream3d_vec<T>(p, {}, adjoint)) return 2;
-        if (!adjoint || !wgrad || p.hc == 0)
-            if (const int brz = brick_rz_for<T>(p, vec, adjoint)) { planes = brz; return 3; }
-        planes = direct_rz<T>(p, vec, adjoint);
-        return 0;
-    };
-    const bool f32poly = hc == 0 && sizeof(T) == 4;
-    const bool tiled_adj = tile_eligible<T>(p, {}, true);
-    const bool direct_sweep = !tiled_adj && (f32poly || !stream3d_vec<T>(p, {}, true));
-    const bool tile_fused = tiled_adj && tile_fuse_ok<T>(p);
-    const bool fuse = tile_fused || (direct_sweep && !p.opt.skip_wgrad && hc != -1 &&
-                                     (p.opt.fuse_wgrad == 1 || (p.opt.fuse_wgrad == 2 && hc == 0)));
-    const int K = (p.opt.tile_k == 8 && p.hc != 0) ? 4 : p.opt.tile_k;
-    out[0] = family(false, false, out[5]);
-    out[1] = family(true, fuse, out[6]);
-    out[2] = fuse ? 1 : 0;
-    out[3] = out[0] == 1 ? K : 1;
-    out[4] = out[1] == 1 ? K : 1;
-    out[7] = (out[0] == 3 || out[1] == 3) ? brick_nt_for(p, vec, out[1] == 3) : 0;     // lanes per brick workgroup (the adjoint's if it runs on bricks)
-    for (int i = 8; i < 15; ++i) out[i] = 0;
-    // the whole tile sweep as one launch of resident workgroups (needs a device to ask for its CU count: 0 without one)
-    if constexpr (sizeof(T) == 4)
-        out[14] = ((out[1] == 1 && (persist_ok<T>(p, nullptr, 1 << 20, 1 << 18, nullptr) ||
-                                    persist_small_ok<T>(p, nullptr, 1 << 20, 1 << 18, nullptr))) ? 1 : 0) |
-                  ((out[0] == 1 && (fwd_persist_ok<T>(p, 1 << 18, nullptr) || fwd_persist_small_by<T>(p, 1 << 18, nullptr) != 0)) ? 2 : 0);
-    else
-        out[14] = ((out[1] == 1 && persist_ok<T>(p, nullptr, 1 << 20, 1 << 18, nullptr)) ? 1 : 0) |
-                  ((out[0] == 1 && fwd_persist_ok<T>(p, 1 << 18, nullptr)) ? 2 : 0);
-    {                                                                      // 3D: the resident sweep (pi_res3d.h) where it applies
-        Res3dPlan rp;
-        if (out[1] == 3 && direct_sweep && fuse && res3d_plan(p, 1 << 10, sizeof(T), rp)) out[14] |= 1;
-    }
-    for (int dir = 0; dir < 2; ++dir) {                                    // 2D tiles: width, height, lanes per workgroup
-        if (out[dir] != 1) continue;
-        const TileShape ts = tile_shape_for<T>(p, dir == 1);
-        int* o = out + (dir == 1 ? 8 : 11);
-        o[0] = ts.bx; o[1] = ts.by;
-        o[2] = ts.nt ? ts.nt : (p.opt.tile_k == 2 ? 256 : (p.hc == 0 && p.opt.tile_k == 8) ? 1024 : (p.hc == 0 && p.opt.tile_nt == 1024) ? 1024 :
-                                (p.hc == 0 && ts.by == 16) ? 320 : (p.hc == 0 && ts.by == 8) ? 256 : p.opt.tile_nt == 256 ? 256 : 512);
-    }
+    const RolloutPlan pl = plan_rollout<T>(p);
+    const StepRoute f = rollout_route<T>(p, pl.fwd.tiles, false, false), a = rollout_route<T>(p, pl.sweep.tiles, true, pl.sweep.fuse);
+    out[0] = f.family; out[1] = a.family;
+    out[2] = pl.sweep.fuse ? 1 : 0;
+    out[3] = pl.fwd.tiles ? pl.fwd.tile.k : 1;
+    out[4] = pl.sweep.tiles ? pl.sweep.tile.k : 1;
+    out[5] = f.planes; out[6] = a.planes;
+    // lanes per brick workgroup (the adjoint's if it runs on bricks)
+    out[7] = a.family == BRICKS ? brick_nt_for(p, a.vec, true) : f.family == BRICKS ? brick_nt_for(p, f.vec, false) : 0;
+    auto tile = [](bool tiles, const TileVariant& v, int* o) { o[0] = tiles ? v.bx : 0; o[1] = tiles ? v.by : 0; o[2] = tiles ? v.nt : 0; };
+    tile(pl.sweep.tiles, pl.sweep.tile, out + 8);
+    tile(pl.fwd.tiles, pl.fwd.tile, out + 11);
+    out[14] = (pl.sweep.resident != SweepResident::none ? 1 : 0) | (pl.fwd.resident != FwdResident::none ? 2 : 0);
     return 0;
 }
 
@@ -3271,11 +3358,10 @@ int debug_batch_plan_impl(int hc, int ndim, const int64_t* shape, int batch, con
     }
     Problem p;
     if (int rc = batch_problem(hc, ndim, shape, batch, p, options, false)) return rc;
-    const int vec = pick_vec<T>(p, {});
-    const bool fuse = !p.opt.skip_wgrad && (p.opt.fuse_wgrad == 1 || (p.opt.fuse_wgrad == 2 && hc == 0));   // the direct sweep's rule
-    const int fz = batch_brick_rz<T>(p, vec, batch, false, false, false), az = batch_brick_rz<T>(p, vec, batch, true, fuse, false);
-    out[0] = fz ? 3 : 0; out[1] = az ? 3 : 0;
-    out[2] = fz ? fz : 1; out[3] = az ? az : 1;              // (the batched direct kernels take one plane per pass)
+    const Samples s{batch, -1, true};
+    const StepRoute f = step_route<T>(p, {}, false, false, s), a = step_route<T>(p, {}, true, plan_rollout<T>(p, s).sweep.fuse, s);
+    out[0] = f.family; out[1] = a.family;
+    out[2] = f.planes; out[3] = a.planes;
     return 0;
 }
 

@@ -8,7 +8,7 @@ T_SWEEP = 9                     # two K = 4 tile launches plus one direct leftov
 FACTORS = [0.5, 0.0, -1.25]     # per-sample factors handed to the sweep: distinct, a zero among them, also for B = 2
 
 # (shape, dtype, hc, options): the sweep families.  (64, 96) float32 poly by default dispatch runs 8-row tiles, whose sweep has
-# no fused-moments flavour (tile_fuse_ok of csrc/pi_abi.hip); "tile_by": 32 is the same grid on the 32 x 32 tiles that do fuse.
+# no fused-moments flavour (TileVariant::mom, tile_variant_for of csrc/pi_abi.hip); "tile_by": 32 is the same grid on the 32 x 32 tiles that do fuse.
 SWEEP_KINDS = [
     ((64, 96), np.float32, 0, None),
     ((64, 96), np.float32, 0, {"tile_fuse": 0}),

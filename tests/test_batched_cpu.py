@@ -130,7 +130,7 @@ def _hc_class(hc):
 
 def _tile_variant(c, adjoint):
     """The tile kernel a case's sample takes (None: direct kernels) -- the rules of tile_eligible, tile_by_for, tile_wide_for,
-    tile_fuse_ok, batch_tile and PI_TILE_VARIANTS of csrc/pi_abi.hip restated, for 16-byte-aligned buffers.  The library has no
+    tile_variant_for, batch_tile and PI_TILE_VARIANTS of csrc/pi_abi.hip restated, for 16-byte-aligned buffers.  The library has no
     query entry for the batched dispatch, so nothing ties this copy to it: csrc/pi_abi.hip is the source of truth, and a change
     of a rule or a threshold there must be made here too, or the coverage proof below goes stale without failing."""
     o = {"tile": 1, "tile_k": 4, "tile_nt": 512, "tile_by": 0, "vec": 0, "tile_wide": 3, "tile_fuse": 1, "skip_wgrad": 0}
@@ -177,7 +177,7 @@ def _tile_variant(c, adjoint):
                (by_for() == 32 or wide_for(True) != 0))
     if wide:
         return f"wide{wide}" + ("-fused" if fuse_ok else "")
-    if fuse_ok:                                            # (either type: tile_fuse_ok does not look at it)
+    if fuse_ok:                                            # (either type: TileVariant::mom does not look at it)
         return "k4-512-fused"
     if o["tile_k"] == 2:
         return "k2"
